@@ -14,6 +14,10 @@ landmarks / 5 000 000 observations (configs[3]; it fits one GPU).  For N > 1 the
 (and their edges) are sharded across ranks and the Schur contributions are summed with an
 RCCL all-reduce (strong scaling, see openslam_g2o_amd/distributed.py and DESIGN.md).
 
+A plain run does what the headline needs: set-up, warm-up, the timed steps, the outputs of the last timed step
+(--dump-outputs DIR) and the JSON line.  --full adds what costs work of its own: a second, untimed pass of the steps
+with every kernel slot timed (per-kernel table, roofline), the residual check and the CPU oracle beside the GPU.
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 import argparse
@@ -29,6 +33,19 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy peak)
 MFMA_F64_PEAK_TFLOPS = 78.6   # dense fp64 matrix rate: 256 CUs x 4 SIMDs x (v_mfma_f64_16x16x4_f64 = 2048 flops / 64 cycles) x 2.4 GHz
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, x):
+    """--dump-outputs: the increment x of the last timed step as out_dir/x.npy (float64).  Where x is larger than
+    DUMP_LIMIT_BYTES, a fixed sample of its entries (seed 0) goes there instead, their indices in x_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    if x.nbytes > DUMP_LIMIT_BYTES - 4096:
+        idx = np.sort(np.random.default_rng(0).choice(x.size, (DUMP_LIMIT_BYTES - 4096) // 16, replace=False))
+        np.save(os.path.join(out_dir, "x_index.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(out_dir, "x.npy"), x)
 
 
 def algorithmic_bytes(E, P, L, S, pp_nnzb, nnzL, p=6, l=3, d=2, folded=False):
@@ -163,7 +180,14 @@ def main():
                          "backward sweep: one launch per tree level); the HIP timing events sit between the graphs")
     ap.add_argument("--mode", choices=["auto", "subtree", "replicated", "pcg"], default="auto", help="N>1 reduced-solve strategy")
     ap.add_argument("--dump-xp", default="", help="rank 0 saves the pose increment to this .npy (cross-run comparison)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (the increment x, poses then landmarks) to DIR/x.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel table (a second, untimed pass of the steps), roofline, solver statistics, the "
+                         "residual check and the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from openslam_g2o_amd.launch import relaunch_if_needed
     relaunch_if_needed(args.gpus, __file__)       # plain `python bench.py --gpus N`: one rank per GPU via torch.distributed.run
@@ -317,19 +341,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms = 1e3 * dt / args.steps
+    x_gpu = solver.local.x() if rank == 0 else None             # the increment of the last timed step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_gpu)
     dom_timed = {} if no_events else solver.local.kernelTimes(reset=True)   # the dominant slot, from inside the timed region
-    solver.local.setProfiling(True)                            # second pass, not timed: the whole per-kernel table
-    for _ in range(args.steps):
-        ok = step() and ok
-    barrier()
-
-    ktimes = solver.local.kernelTimes(reset=True)
-    ktimes.update(dom_timed)
     rank_tables = None
-    if world > 1:
-        mine = {name: round(1e3 * tot / n, 5) for name, (tot, n) in ktimes.items()}
-        rank_tables = [None] * world
-        dist.all_gather_object(rank_tables, mine)
+    if args.full:
+        solver.local.setProfiling(True)                            # second pass, not timed: the whole per-kernel table
+        for _ in range(args.steps):
+            ok = step() and ok
+        barrier()
+
+        ktimes = solver.local.kernelTimes(reset=True)
+        ktimes.update(dom_timed)
+        if world > 1:
+            mine = {name: round(1e3 * tot / n, 5) for name, (tot, n) in ktimes.items()}
+            rank_tables = [None] * world
+            dist.all_gather_object(rank_tables, mine)
     xp_all = None
     if args.check_oracle and world > 1:
         xp_all = solver.gather_x_poses()            # collective: every rank takes part (x of the last damped solve)
@@ -337,103 +365,10 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    st = solver.local.stats()
-    S_blocks = solver.local.nnzb(capi.HSCHUR)
-    pp_nnzb = solver.local.nnzb(capi.HPP)
-    E_loc, L_loc = shard["E_local"], shard["L_local"]
-    folded = world == 1 and not emulate and not any(kv.replace(" ", "") in ("fuse_schur_reduce=0", "linear_solver=1") for kv in args.opt)
-    kb, stage_b = algorithmic_bytes(E_loc, prob["nP"], L_loc, S_blocks, pp_nnzb, st["choleskyNNZ"], folded=folded)
-    if st.get("bandChains", 0) > 0:
-        # the factorisation is two kernels: the leaf chains of the band (band_wave_kernel) and the tree levels above them
-        # (wave_front_kernel).  Its compulsory bytes are split by what each one factorises: nnz(L) exactly, the matrix
-        # entries and the forward sweep's vectors by the share of the pivot columns.
-        n_sc = 6 * prob["nP"]
-        tot = kb["chol_factor(all levels)"]
-        band = 8 * st["bandCholeskyNNZ"] + (tot - 8 * st["choleskyNNZ"]) * st["bandPivots"] / n_sc
-        kb["chol_factor(band chains)"] = band
-        kb["chol_factor(all levels)"] = tot - band
-    om_bytes = 0 if args.information == "identity" else 8 * 4      # the per-observation information matrix, where it is read
-    fused_kb = {}
-    if fused:
-        kb["assemble_vertex(landmark)"] = kb["fused:assemble_vertex(landmark)"]
-        kb["assemble_vertex(pose)"] = kb["fused:assemble_vertex(pose)"] + E_loc * om_bytes
-        # The fused kernels do not read Hpl: what they move by construction (estimates, measurements, results; index tables
-        # excluded like everywhere) is far below the un-fused stage formulas of SURVEY.md 8d, which stay the yardstick of
-        # `roofline` (work done per second).  back_substitute is reported on ITS OWN bytes -- on the un-fused formula
-        # (an Hpl read it does not make) the slot printed more than the HBM peak.
-        p_, l_, d_ = 6, 3, 2
-        fused_kb["schur_tiles"] = E_loc * (8 * d_ + om_bytes) + L_loc * 8 * (l_ + l_ * l_ + l_) + prob["nP"] * 8 * 12 + S_blocks * 8 * p_ * p_
-        fused_kb["back_substitute"] = E_loc * (8 * d_ + om_bytes) + L_loc * 8 * (l_ + l_ * l_ + 2 * l_) + prob["nP"] * 8 * (12 + p_)
-        kb["back_substitute"] = fused_kb["back_substitute"]
-    per_kernel = {}
-    for name, (tot, n) in ktimes.items():
-        avg = tot / n
-        per_kernel[name] = dict(avg_ms=1e3 * avg, launches_per_step=n / args.steps,
-                                algorithmic_GB=kb.get(name, 0) / 1e9,
-                                achieved_GBs=(kb.get(name, 0) / 1e9 / avg) if avg > 0 else 0.0)
-        if name in fused_kb:
-            per_kernel[name]["fused_algorithmic_GB"] = fused_kb[name] / 1e9   # bytes this (fused) kernel moves by construction
-    dname = dom_name if dom_name in per_kernel else max(per_kernel.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches_per_step"])[0]
-    dk = per_kernel[dname]
-    # HBM bytes per launch from the PMC counters: collected by a separate rocprofv3 --pmc pass of this
-    # same command (profiles/r1_pmc_traffic.json, recipe in its _note); null when that file is absent
-    # or the workload differs from the profiled one.
-    traffic = None
-    pmc_all = {}
-    pmc_path = next((q for q in (os.path.join(ROOT, "profiles", "r%d_pmc_traffic.json" % r) for r in (9, 8, 7, 6, 5, 4, 3, 2, 1))
-                     if os.path.exists(q)), "")
-    if pmc_path and world == 1 and not emulate and (P, L) == (100000, 1000000):   # (the counters were taken on the whole graph on one GPU)
-        pmc_all = json.load(open(pmc_path))
-        pmc = pmc_all.get(dname)
-        if pmc:
-            traffic = pmc["hbm_bytes_per_step"]
-        # next to the rate of WORK (un-fused algorithmic bytes / time, which a fused kernel can push past what any copy
-        # reaches) the rate of TRAFFIC the counters saw for the same kernel: bytes actually moved / time
-        for name, row in per_kernel.items():
-            q = pmc_all.get(name)
-            if isinstance(q, dict) and row["avg_ms"] > 0:
-                per_launch = q["hbm_bytes_per_step"] / max(row["launches_per_step"], 1e-9)   # (per launch of the SLOT, like avg_ms)
-                row["pmc_traffic_GB"] = per_launch / 1e9
-                row["pmc_GBs"] = per_launch / 1e9 / (1e-3 * row["avg_ms"])
-                # matrix cores: v_mfma_f64_16x16x4_f64 wave instructions counted by SQ_INSTS_MFMA (2048 flops each) over this
-                # run's time for the slot, against the dense fp64 matrix peak; the busy-cycle counter beside it
-                n_mfma = q.get("SQ_INSTS_MFMA_per_step", 0)
-                if n_mfma:
-                    step_s = 1e-3 * row["avg_ms"] * row["launches_per_step"]
-                    row["mfma_TFLOPs"] = 2048.0 * n_mfma / step_s / 1e12
-                    row["mfma_util"] = row["mfma_TFLOPs"] / MFMA_F64_PEAK_TFLOPS
-                    if q.get("SQ_BUSY_CYCLES_per_step"):
-                        row["mfma_busy_cycles_over_sq_busy_cycles"] = q.get("SQ_VALU_MFMA_BUSY_CYCLES_per_step", 0) / q["SQ_BUSY_CYCLES_per_step"]
-    roofline = dict(kernel=dname, bound="hbm", achieved=dk["achieved_GBs"], peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=dk["achieved_GBs"] / HBM_PEAK_GBS, traffic=traffic,
-                    # the same fraction on the bytes the counters saw move (traffic / this run's launch time / peak)
-                    frac_traffic=(traffic / (1e-3 * dk["avg_ms"]) / 1e9 / HBM_PEAK_GBS) if traffic and dk["avg_ms"] > 0 else None,
-                    algorithmic_bytes_per_launch=kb.get(dname, 0), avg_launch_ms=dk["avg_ms"],
-                    traffic_source="profiles/%s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE, 2x FETCH correction)" % os.path.basename(pmc_path)
-                    if traffic else None,
-                    # the counters come from a separate rocprofv3 pass (gpurun refuses --pmc next to other tracing), taken at this commit
-                    traffic_commit=(pmc_all.get("_commit") if traffic else None))
-    # the factorisation on its FLOPS (dense-front count of the symbolic analysis, g2ohip_stats.choleskyFlops) over the time of its slots:
-    # where it is the dominant kernel (graphs with real fill: --workload grid) the matrix cores bound the path, not HBM
-    fl = float(st.get("choleskyFlops", 0.0))
-    t_factor = sum(1e-3 * v["avg_ms"] * v["launches_per_step"] for k, v in per_kernel.items() if k.startswith("chol_factor"))
-    if fl > 0 and t_factor > 0:
-        for k, v in per_kernel.items():
-            if k.startswith("chol_factor"):
-                v["factor_TFLOPs(all factor slots)"] = fl / t_factor / 1e12
-        if dname.startswith("chol_factor"):
-            roofline = dict(kernel=dname, bound="mfma", achieved=fl / t_factor / 1e12, peak=MFMA_F64_PEAK_TFLOPS, unit="TFLOP/s",
-                            frac=fl / t_factor / 1e12 / MFMA_F64_PEAK_TFLOPS, traffic=None, flops_per_launch=fl, avg_launch_ms=1e3 * t_factor,
-                            note="dense fp64 matrix peak; flops = dense-front count of this factorisation's symbolic analysis (nnz(L) %d)" % st["choleskyNNZ"],
-                            hbm_view=roofline)
-    mfma_kernels = {k: {"mfma_util": round(v["mfma_util"], 4), "mfma_TFLOPs": round(v["mfma_TFLOPs"], 2)} for k, v in per_kernel.items() if "mfma_util" in v}
-    if mfma_kernels:
-        roofline["mfma"] = dict(peak_TFLOPs=MFMA_F64_PEAK_TFLOPS, unit="TFLOP/s (dense fp64 matrix)", kernels=mfma_kernels)
-
-    x_gpu = solver.local.x()
     if args.dump_xp:
         os.makedirs(os.path.dirname(os.path.abspath(args.dump_xp)), exist_ok=True)
         np.save(args.dump_xp, x_gpu[:6 * prob["nP"]])
+    E_loc, L_loc = shard["E_local"], shard["L_local"]
     out = {
         "metric": "linear-solve ms/iter (buildSystem + setLambda + solve + restoreDiagonal), 100k-pose BA" if args.workload == "chain"
         else "linear-solve ms/iter (buildSystem + setLambda + solve + restoreDiagonal), grid BA (visibility by distance)",
@@ -452,14 +387,104 @@ def main():
                    else "one 2 x 2 matrix per edge, read per observation"},
         "solve_ok": bool(ok),
         "launch": ("hipGraph replay of the launch sequences (elimination-tree levels grouped into dependency-driven launches)" if use_graph else "plain launches") +
-                  "; timed region: HIP events around the dominant kernel slot only (roofline); the other per-kernel times come "
-                  "from a second pass of the same steps with every slot timed",
-        "roofline": roofline,
-        "kernels": per_kernel,
-        "stage_algorithmic_GB": {k: v / 1e9 for k, v in stage_b.items()},
-        "solver_stats": {k: st[k] for k in ("choleskyNNZ", "numFronts", "numLevels", "maxFrontDim", "timeSymbolicDecomposition", "bandChains",
-                                            "bandCholeskyNNZ", "bandPivots", "choleskyFlops")},
+                  "; timed region: HIP events around the dominant kernel slot only (roofline)" +
+                  ("; the other per-kernel times come from a second pass of the same steps with every slot timed" if args.full else ""),
     }
+    if args.full:
+        st = solver.local.stats()
+        S_blocks = solver.local.nnzb(capi.HSCHUR)
+        pp_nnzb = solver.local.nnzb(capi.HPP)
+        folded = world == 1 and not emulate and not any(kv.replace(" ", "") in ("fuse_schur_reduce=0", "linear_solver=1") for kv in args.opt)
+        kb, stage_b = algorithmic_bytes(E_loc, prob["nP"], L_loc, S_blocks, pp_nnzb, st["choleskyNNZ"], folded=folded)
+        if st.get("bandChains", 0) > 0:
+            # the factorisation is two kernels: the leaf chains of the band (band_wave_kernel) and the tree levels above them
+            # (wave_front_kernel).  Its compulsory bytes are split by what each one factorises: nnz(L) exactly, the matrix
+            # entries and the forward sweep's vectors by the share of the pivot columns.
+            n_sc = 6 * prob["nP"]
+            tot = kb["chol_factor(all levels)"]
+            band = 8 * st["bandCholeskyNNZ"] + (tot - 8 * st["choleskyNNZ"]) * st["bandPivots"] / n_sc
+            kb["chol_factor(band chains)"] = band
+            kb["chol_factor(all levels)"] = tot - band
+        om_bytes = 0 if args.information == "identity" else 8 * 4      # the per-observation information matrix, where it is read
+        fused_kb = {}
+        if fused:
+            kb["assemble_vertex(landmark)"] = kb["fused:assemble_vertex(landmark)"]
+            kb["assemble_vertex(pose)"] = kb["fused:assemble_vertex(pose)"] + E_loc * om_bytes
+            # The fused kernels do not read Hpl: what they move by construction (estimates, measurements, results; index tables
+            # excluded like everywhere) is far below the un-fused stage formulas of SURVEY.md 8d, which stay the yardstick of
+            # `roofline` (work done per second).  back_substitute is reported on ITS OWN bytes -- on the un-fused formula
+            # (an Hpl read it does not make) the slot printed more than the HBM peak.
+            p_, l_, d_ = 6, 3, 2
+            fused_kb["schur_tiles"] = E_loc * (8 * d_ + om_bytes) + L_loc * 8 * (l_ + l_ * l_ + l_) + prob["nP"] * 8 * 12 + S_blocks * 8 * p_ * p_
+            fused_kb["back_substitute"] = E_loc * (8 * d_ + om_bytes) + L_loc * 8 * (l_ + l_ * l_ + 2 * l_) + prob["nP"] * 8 * (12 + p_)
+            kb["back_substitute"] = fused_kb["back_substitute"]
+        per_kernel = {}
+        for name, (tot, n) in ktimes.items():
+            avg = tot / n
+            per_kernel[name] = dict(avg_ms=1e3 * avg, launches_per_step=n / args.steps,
+                                    algorithmic_GB=kb.get(name, 0) / 1e9,
+                                    achieved_GBs=(kb.get(name, 0) / 1e9 / avg) if avg > 0 else 0.0)
+            if name in fused_kb:
+                per_kernel[name]["fused_algorithmic_GB"] = fused_kb[name] / 1e9   # bytes this (fused) kernel moves by construction
+        dname = dom_name if dom_name in per_kernel else max(per_kernel.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches_per_step"])[0]
+        dk = per_kernel[dname]
+        # HBM bytes per launch from the PMC counters: collected by a separate rocprofv3 --pmc pass of this
+        # same command (profiles/r1_pmc_traffic.json, recipe in its _note); null when that file is absent
+        # or the workload differs from the profiled one.
+        traffic = None
+        pmc_all = {}
+        pmc_path = next((q for q in (os.path.join(ROOT, "profiles", "r%d_pmc_traffic.json" % r) for r in (9, 8, 7, 6, 5, 4, 3, 2, 1))
+                         if os.path.exists(q)), "")
+        if pmc_path and world == 1 and not emulate and (P, L) == (100000, 1000000):   # (the counters were taken on the whole graph on one GPU)
+            pmc_all = json.load(open(pmc_path))
+            pmc = pmc_all.get(dname)
+            if pmc:
+                traffic = pmc["hbm_bytes_per_step"]
+            # next to the rate of WORK (un-fused algorithmic bytes / time, which a fused kernel can push past what any copy
+            # reaches) the rate of TRAFFIC the counters saw for the same kernel: bytes actually moved / time
+            for name, row in per_kernel.items():
+                q = pmc_all.get(name)
+                if isinstance(q, dict) and row["avg_ms"] > 0:
+                    per_launch = q["hbm_bytes_per_step"] / max(row["launches_per_step"], 1e-9)   # (per launch of the SLOT, like avg_ms)
+                    row["pmc_traffic_GB"] = per_launch / 1e9
+                    row["pmc_GBs"] = per_launch / 1e9 / (1e-3 * row["avg_ms"])
+                    # matrix cores: v_mfma_f64_16x16x4_f64 wave instructions counted by SQ_INSTS_MFMA (2048 flops each) over this
+                    # run's time for the slot, against the dense fp64 matrix peak; the busy-cycle counter beside it
+                    n_mfma = q.get("SQ_INSTS_MFMA_per_step", 0)
+                    if n_mfma:
+                        step_s = 1e-3 * row["avg_ms"] * row["launches_per_step"]
+                        row["mfma_TFLOPs"] = 2048.0 * n_mfma / step_s / 1e12
+                        row["mfma_util"] = row["mfma_TFLOPs"] / MFMA_F64_PEAK_TFLOPS
+                        if q.get("SQ_BUSY_CYCLES_per_step"):
+                            row["mfma_busy_cycles_over_sq_busy_cycles"] = q.get("SQ_VALU_MFMA_BUSY_CYCLES_per_step", 0) / q["SQ_BUSY_CYCLES_per_step"]
+        roofline = dict(kernel=dname, bound="hbm", achieved=dk["achieved_GBs"], peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=dk["achieved_GBs"] / HBM_PEAK_GBS, traffic=traffic,
+                        # the same fraction on the bytes the counters saw move (traffic / this run's launch time / peak)
+                        frac_traffic=(traffic / (1e-3 * dk["avg_ms"]) / 1e9 / HBM_PEAK_GBS) if traffic and dk["avg_ms"] > 0 else None,
+                        algorithmic_bytes_per_launch=kb.get(dname, 0), avg_launch_ms=dk["avg_ms"],
+                        traffic_source="profiles/%s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE, 2x FETCH correction)" % os.path.basename(pmc_path)
+                        if traffic else None,
+                        # the counters come from a separate rocprofv3 pass (--pmc is not combined with other tracing), taken at this commit
+                        traffic_commit=(pmc_all.get("_commit") if traffic else None))
+        # the factorisation on its FLOPS (dense-front count of the symbolic analysis, g2ohip_stats.choleskyFlops) over the time of its slots:
+        # where it is the dominant kernel (graphs with real fill: --workload grid) the matrix cores bound the path, not HBM
+        fl = float(st.get("choleskyFlops", 0.0))
+        t_factor = sum(1e-3 * v["avg_ms"] * v["launches_per_step"] for k, v in per_kernel.items() if k.startswith("chol_factor"))
+        if fl > 0 and t_factor > 0:
+            for k, v in per_kernel.items():
+                if k.startswith("chol_factor"):
+                    v["factor_TFLOPs(all factor slots)"] = fl / t_factor / 1e12
+            if dname.startswith("chol_factor"):
+                roofline = dict(kernel=dname, bound="mfma", achieved=fl / t_factor / 1e12, peak=MFMA_F64_PEAK_TFLOPS, unit="TFLOP/s",
+                                frac=fl / t_factor / 1e12 / MFMA_F64_PEAK_TFLOPS, traffic=None, flops_per_launch=fl, avg_launch_ms=1e3 * t_factor,
+                                note="dense fp64 matrix peak; flops = dense-front count of this factorisation's symbolic analysis (nnz(L) %d)" % st["choleskyNNZ"],
+                                hbm_view=roofline)
+        mfma_kernels = {k: {"mfma_util": round(v["mfma_util"], 4), "mfma_TFLOPs": round(v["mfma_TFLOPs"], 2)} for k, v in per_kernel.items() if "mfma_util" in v}
+        if mfma_kernels:
+            roofline["mfma"] = dict(peak_TFLOPs=MFMA_F64_PEAK_TFLOPS, unit="TFLOP/s (dense fp64 matrix)", kernels=mfma_kernels)
+        out.update(roofline=roofline, kernels=per_kernel, stage_algorithmic_GB={k: v / 1e9 for k, v in stage_b.items()},
+                   solver_stats={k: st[k] for k in ("choleskyNNZ", "numFronts", "numLevels", "maxFrontDim", "timeSymbolicDecomposition",
+                                                    "bandChains", "bandCholeskyNNZ", "bandPivots", "choleskyFlops")})
     if emulate:
         out["emulate"] = "rank %d of %d alone, exchange skipped: timing only" % emulate
     if world > 1 or emulate:
@@ -477,13 +502,13 @@ def main():
             out["shard"].update(boundary_blocks=int(len(solver.boundary)), reduced_blocks=int(solver.nnzb_reduced),
                                 poses_per_rank=np.bincount(solver.pose_owner + 1).tolist())
     # size-independent correctness property at full size: residual of the damped system
-    solver.setLambda(lam, True)
-    if world == 1 and not emulate:
+    if args.full and world == 1 and not emulate:
+        solver.setLambda(lam, True)
         r = solver.local.multiplyHessian(x_gpu) - solver.local.b()
         out["residual_rel"] = float(np.abs(r).max() / np.abs(solver.local.b()).max())
-    solver.restoreDiagonal()
+        solver.restoreDiagonal()
 
-    if world == 1 and not emulate and not args.no_cpu_baseline:
+    if args.full and world == 1 and not emulate and not args.no_cpu_baseline:
         grid = args.workload == "grid"   # (a CPU iteration of the grid graph is minutes, not seconds: one timed repetition, no thread sweep)
         cb, x_cpu = cpu_baseline(prob, lam, include_linearize=fused, reps=1 if grid else 3)
         cpu_ms = 1e3 * (cb["t_assembly"] + cb["t_solve"])

@@ -252,14 +252,15 @@ def test_grid_graph_whole_gpu_passes_against_one_workgroup_per_front():
 
 
 def test_bench_line_contract_on_both_workloads(tmp_path):
-    """bench.py prints ONE JSON line with the contract's keys; `roofline` carries frac_traffic / traffic_commit / the matrix-core block
+    """bench.py --full prints ONE JSON line with the contract's keys; `roofline` carries frac_traffic / traffic_commit / the matrix-core block
     on the chain workload at the metric configuration only (the PMC file is for that size) and switches to the MFMA bound with the
     factorisation's flop count where the factorisation dominates (--workload grid); `cpu_baseline` (the oracle, one repetition on the
     grid) sits beside it with dx / chi2 against it."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for args, bound in ((["--workload", "grid", "--poses", "900"], "mfma"), (["--poses", "3000", "--landmarks", "30000"], "hbm")):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2"] + args, capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "2"] + args, capture_output=True, text=True,
+                           timeout=900)
         assert r.returncode == 0, r.stderr[-1500:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1
@@ -273,3 +274,29 @@ def test_bench_line_contract_on_both_workloads(tmp_path):
         assert d["dx_rel_err"] < 1e-8 and d["chi2_rel_err"] < 1e-9 and d["residual_rel"] < 1e-11
         if bound == "mfma":
             assert d["roofline"]["unit"] == "TFLOP/s" and d["solver_stats"]["choleskyFlops"] > 0 and "visibility by distance" in d["config"]["workload"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline keys only -- no second pass, no residual check, no CPU oracle -- and
+    --dump-outputs writes the increment x of its last timed step (float64).  The --full run on the same arguments dumps the same x,
+    and there x solves the damped system (residual_rel) and equals the CPU oracle's (dx_rel_err)."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--poses", "3000", "--landmarks", "30000",
+                            "--dump-outputs", str(tmp_path / mode)] + extra, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-1500:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs[mode] = (json.loads(lines[0]), np.load(tmp_path / mode / "x.npy"))
+    d, x = runs["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "solve_ok"):
+        assert k in d, k
+    for k in ("roofline", "kernels", "solver_stats", "residual_rel", "cpu_baseline", "dx_rel_err"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["solve_ok"] and d["value"] == d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    assert x.dtype == np.float64 and x.ndim == 1 and x.size >= 3 * 30000 and np.isfinite(x).all()
+    full, xf = runs["full"]
+    assert full["dx_rel_err"] < 1e-8 and full["residual_rel"] < 1e-11
+    assert xf.shape == x.shape and relerr(x, xf) < 1e-12

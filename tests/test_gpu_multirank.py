@@ -426,7 +426,7 @@ def test_bench_launches_its_own_ranks(ranks, poses, comm):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--comm", comm, "--poses", str(poses),
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(ranks), "--comm", comm, "--poses", str(poses),
                         "--landmarks", str(10 * poses), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--check-oracle"], env=env,
                        cwd=root, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]

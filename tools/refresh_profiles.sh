@@ -5,14 +5,14 @@ set -u
 P=${1:-r3}
 OUT=$PWD/gpurun_out/refresh
 mkdir -p $OUT
-python bench.py --steps 20 --warmup 3 > $OUT/${P}_bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/${P}_bench.json 2> $OUT/bench.err
 python lm_bench.py > $OUT/${P}_lm_config5.json 2> $OUT/lm.err
-for n in 2 4 8; do python bench.py --emulate 0/$n --no-cpu-baseline --steps 20 --warmup 3 > $OUT/emu_$n.json 2>> $OUT/bench.err; done
+for n in 2 4 8; do python bench.py --full --emulate 0/$n --no-cpu-baseline --steps 20 --warmup 3 > $OUT/emu_$n.json 2>> $OUT/bench.err; done
 export TMPDIR=/tmp
 R=$PWD
 cd /tmp
 rm -rf /tmp/pk /tmp/pf /tmp/pw
-rocprofv3 --kernel-trace --stats -d /tmp/pk -o k -- python $R/bench.py --no-cpu-baseline --graph off --steps 5 --warmup 2 > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/pk -o k -- python $R/bench.py --full --no-cpu-baseline --graph off --steps 5 --warmup 2 > $OUT/trace.log 2>&1
 python $R/tools/rocpd_summary.py $(find /tmp/pk -name "*.db" | head -1) $OUT/${P}_kernel_stats.csv
 python $R/tools/level_times.py $(find /tmp/pk -name "*.db" | head -1) 2 > $OUT/${P}_level_times.txt
 cd $R
