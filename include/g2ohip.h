@@ -229,23 +229,25 @@ int g2ohip_trial_stats(g2ohip_solver* s, double lambda, int* solve_ok, double* c
  * with "pcg_tolerance" (1e-6),
  * "pcg_absolute_tolerance" (1), "pcg_max_iterations" (-1 = dimension), like LinearSolverPCG's setters
  * (linear_solver_pcg.h:74-85); iterations of the last solve in g2ohip_stats.iterationsLinearSolver.
- * Ordering / symbolic knobs (before g2ohip_build_structure): "nd_leaf" (nested-dissection leaf size in blocks, 32),
- * "max_sn_scalars" (48) / "max_sn_scalars_lds" (24: fronts that fit LDS), "relax_zeros", "relax_front_bytes",
- * "lds_front_bytes", "fuse_chains", "wave_front_tasks", "dep_levels" (64: task levels that may share one
- * dependency-driven launch, 0/1 = one launch per level), "dep_backward" (1), "dep_delay", "dep_spin_limit", "dep_acq_rel" (0; 1 =
- * release / acquire on the dependency counters, for A/B validation), "band_kernel" (1: leaf chains of a band in the one-wave
- * sliding-window kernel), "fuse_fwd_any" (1: forward sweep fused into the factor kernel whatever a front's children),
- * "lds_mfma" ((4 << 16) | 96: LDS fronts with at least that many pivot blocks / boundary rows get one MFMA trailing update),
- * "big_front_passes" (1: large fronts as whole-GPU passes with an MFMA update) / "big_front_min_dim" (180);
- * for those passes "inplace_chains", "mfma_diag", "fuse_panel", "overlap_level_halves", "hoist_big_assembly",
- * "fuse_big_forward", "split_sweeps" / "split_sweeps_min_dim" (512), "merge_backward_levels", "merge_diag_panel" (all 1: see INTEGRATION.md, options).
- * Kernel knobs: "schur_tile_bytes", "schur_group", "fuse_landmark_inverse", "fuse_schur_reduce" (1: g2ohip_solve on
+ * Factorisation (also g2ohip_ls_set_option; the ordering / symbolic ones before g2ohip_build_structure): "nd_leaf"
+ * (nested-dissection leaf size in blocks; 0 = auto: 32 and more for band-shaped graphs, 4 for the others), "max_sn_scalars"
+ * (48: supernode width cap in scalars, at most 64 takes effect), "max_sn_scalars_lds" (0 = auto: 24 for band-shaped graphs,
+ * 48 otherwise; the fronts that fit LDS), "dep_levels" (64: task levels that may share one dependency-driven launch, 0/1 =
+ * one launch per level), "dep_backward" (1: the backward sweep in the same dependency-driven groups), "dep_spin_limit"
+ * (1 << 21: polls before a waiting workgroup gives up), "band_kernel" (1: leaf chains of a band in the one-wave
+ * sliding-window kernel), "tree_backward" (1: backward sweep of small fronts by groups in one workgroup), "big_front_passes"
+ * (1: large fronts as whole-GPU passes with an MFMA update), "big_group" (8: panels of a long in-place chain updated as a
+ * group; 1 = off) / "big_group_min_rows" (1024: for chains of at least that many rows).
+ * Block solver: "schur_tile_bytes" (39936: LDS budget of one Schur tile), "fuse_schur_reduce" (1: g2ohip_solve on
  * one GPU folds the Schur reduction into the factorisation; Hschur is then written only when it is asked for),
- * "ba_fused", "ba_store_ll" (0: Hll and the errors of the fused BA path reach HBM only when a reader asks), "use_graph",
- * "mask_solution", "sharded_virtual" (1: on a rank the factorisation reads Hpp and the partial blocks itself, only the boundary
- * blocks of the reduced system are reduced and exchanged as blocks), "sharded_graph" (1: g2ohip_solve_sharded as one hipGraph where nothing crosses the host; 2: with RCCL too),
+ * "ba_fused" (1: the BA edge set's errors and Jacobians evaluated inside the assembly kernels), "ba_fuse_landmarks" (1: the
+ * landmark side of the fused BA path assembled by the Schur tiles of the solve), "use_graph" (0), "mask_solution" (1),
+ * "marginals_reduced" (0) / "marginals_recursion" (1) (see g2ohip_compute_marginals), "setup_overlap" (1: the symbolic
+ * analysis next to the Schur tiles' set-up), "pcg_check_every" (16: PCG iterations between looks at the convergence flag),
+ * "sharded_graph" (1: g2ohip_solve_sharded as one hipGraph where nothing crosses the host; 2: with RCCL too),
  * "sharded_merge" (1: the boundary blocks / b_p of a sharded solve travel in the all-reduce of the subtree roots -- two collectives per
- * solve instead of three -- whenever only the shared top of the tree consumes them; 0: always three),
+ * solve instead of three -- whenever only the shared top of the tree consumes them; 0: always three), "sharded_selftest" (1: the
+ * first sharded solve of a structure is checked against the reference schedule), "sharded_selftest_break" (tests only),
  * "comm_emulate" (timing only).  G2OHIP_OPTIONS="name=value,..." in the environment sets options for every solver of a process: g2ohip_create and
  * g2ohip_ls_create apply it (so the g2o plugin sees it too); a malformed or, for g2ohip_create, unknown entry fails the
  * creation with G2OHIP_ERR_ARG; an explicit g2ohip_set_option afterwards wins. */

@@ -2269,9 +2269,6 @@ BlockSolver::~BlockSolver() {
     (void)hipEventSynchronize(trial_ev_);
     (void)hipEventDestroy(trial_ev_);
   }
-  if (side_) (void)hipStreamDestroy(side_);
-  if (side_fork_) (void)hipEventDestroy(side_fork_);
-  if (side_join_) (void)hipEventDestroy(side_join_);
   if (own_stream_ && st_) (void)hipStreamDestroy(st_);
   if (h_trial_) (void)hipHostFree(h_trial_);
 }
@@ -2763,7 +2760,6 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
         std::vector<unsigned short> lml;
       };
       std::vector<TileOut> outs(descs.size());
-      const bool sort_dests = schur_sort_dests;
       host_parallel_for(descs.size(), [&](size_t tb_, size_t te_) {
         std::vector<Ent> ents;
         std::vector<int> order;
@@ -2808,10 +2804,9 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
             runs.emplace_back((int)k, (int)k2);
             k = k2;
           }
-          if (sort_dests)
-            std::stable_sort(runs.begin(), runs.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) {
-              return (x.second - x.first) > (y.second - y.first);
-            });
+          std::stable_sort(runs.begin(), runs.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) {
+            return (x.second - x.first) > (y.second - y.first);
+          });
           TileOut& o = outs[ti];
           o.dest.reserve(runs.size());
           o.cnt.reserve(runs.size());
@@ -2933,7 +2928,7 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
   d_pp_colptr.upload(pp_colptr, st_);
   d_pp_row.upload(pp_row, st_);
   // multi-rank + Schur: room behind Hpp for the reduced-system blocks that are summed over the ranks (block d of Hschur at
-  // pp_nnzb + d): the virtual source of the factorisation reads them there (exchange_setup, sharded_virtual)
+  // pp_nnzb + d): the virtual source of the factorisation reads them there (exchange_setup)
   hpp_blocks_ = (size_t)pp_nnzb;
   d_Hpp.alloc(((size_t)pp_nnzb + ((schur_ && chol_opt.world > 1) ? hs_row.size() : 0)) * p * p);
   d_bkP.alloc((size_t)nP * p);
@@ -3224,8 +3219,7 @@ void BlockSolver::launch_ba_landmarks(bool write_hpl) {
 // May the fused BA assembly leave Hpl unwritten?  Only while its two readers on the solve path (Schur tiles,
 // back-substitution) re-evaluate the Jacobians: direct solver, tiled Schur pass that covers every landmark.
 bool BlockSolver::ba_skip_hpl_ok() const {
-  return ba_skip_hpl && schur_ && p_ == 6 && l_ == 3 && linear_solver == 0 && n_tiles_ > 0 && tiles_cover_all_ && fuse_landmark_inverse &&
-         ba_recompute_backsub && ba_.set >= 0 && ba_fused && ba_.fused_ok && ba_.cam_q.p != nullptr && [&] {
+  return schur_ && p_ == 6 && l_ == 3 && linear_solver == 0 && n_tiles_ > 0 && tiles_cover_all_ && ba_.set >= 0 && ba_fused && ba_.fused_ok && ba_.cam_q.p != nullptr && [&] {
            for (size_t i = 0; i < sets_.size(); ++i)
              if ((int)i != ba_.set && sets_[i]->n > 0 && sets_[i]->touches_lm) return false;
            return true;
@@ -3261,7 +3255,7 @@ void BlockSolver::ensure_hpl() {
   if (hpl_valid_) return;
   if (!ba_recompute_ok())
     throw StateFailure("Hpl was not materialised by the last build_system and the estimates (or the robust kernel) have changed since: "
-                       "call build_system again, or set option ba_skip_hpl = 0");
+                       "call build_system again, or set option ba_fused = 0");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   launch_ba_landmarks(true);   // the same kernel with the Hpl stores on (Hll, b_l and the errors come out identical)
   hpl_valid_ = ll_valid_ = true;
@@ -3282,8 +3276,8 @@ __global__ void zero_inactive_poses_kernel(int n, int p, const int* __restrict__
   else b[(size_t)v * p + (e - p * p)] = 0.0;
 }
 
-// pose side of the fused BA assembly (Hpp diagonal blocks, b_p) on stream sp
-void BlockSolver::launch_ba_poses(hipStream_t sp) {
+// pose side of the fused BA assembly (Hpp diagonal blocks, b_p)
+void BlockSolver::launch_ba_poses() {
   EdgeSet& es = *sets_[ba_.set];
   const int G = pick_group((double)es.n_vp_ent / std::max(1, nP_));
   // (a rank of a sharded job: only the poses it has observations of -- the only pose-side set, so nothing else ever
@@ -3292,13 +3286,13 @@ void BlockSolver::launch_ba_poses(hipStream_t sp) {
   const int nPk = compact ? es.n_vp_act : nP_;
   const int* pact = compact ? es.vp_act.p : (const int*)nullptr;
 #define G2OHIP_BA_POSE_(GG, CC)                                                                                                  \
-  hipLaunchKernelGGL((ba_assemble_poses_kernel<GG, CC>), dim3(grid_for((size_t)nPk * GG)), dim3(kThreads), 0, sp, nPk, es.vp_ptr.p,  \
+  hipLaunchKernelGGL((ba_assemble_poses_kernel<GG, CC>), dim3(grid_for((size_t)nPk * GG)), dim3(kThreads), 0, st_, nPk, es.vp_ptr.p,  \
                      ba_.cams.p, ba_.pts.p, ba_.cam_pm.p, ba_.pt_pm.p, ba_.meas_pm.p, ba_.omega_pm.p, ba_.f, ba_.cx, ba_.cy,       \
                      es.kernel_kind, es.delta, d_Hpp.p, d_pp_diag.p, d_b.p, es.first_pose ? 0 : 1, ba_.omega_identity ? 1 : 0,     \
                      pact, ba_.ctab.p)
 #define G2OHIP_BA_POSE(GG) G2OHIP_BA_POSE_(GG, false)
   if (compact && es.first_pose)
-    hipLaunchKernelGGL(zero_inactive_poses_kernel, dim3(grid_for((size_t)(nP_ - nPk) * (p_ * p_ + p_))), dim3(kThreads), 0, sp, nP_ - nPk, p_,
+    hipLaunchKernelGGL(zero_inactive_poses_kernel, dim3(grid_for((size_t)(nP_ - nPk) * (p_ * p_ + p_))), dim3(kThreads), 0, st_, nP_ - nPk, p_,
                        es.vp_act.p + nPk, d_pp_diag.p, d_Hpp.p, d_b.p);
   if (es.touches_pose) {
     static const int g_env = getenv("G2OHIP_POSE_GROUP") ? atoi(getenv("G2OHIP_POSE_GROUP")) : 0;   // (experiments)
@@ -3311,13 +3305,6 @@ void BlockSolver::launch_ba_poses(hipStream_t sp) {
   }
 #undef G2OHIP_BA_POSE
 #undef G2OHIP_BA_POSE_
-}
-
-void BlockSolver::ensure_side() {
-  if (side_) return;
-  G2OHIP_HIP_CHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-  G2OHIP_HIP_CHECK(hipEventCreateWithFlags(&side_fork_, hipEventDisableTiming));
-  G2OHIP_HIP_CHECK(hipEventCreateWithFlags(&side_join_, hipEventDisableTiming));
 }
 
 void BlockSolver::build_system_impl() {
@@ -3339,14 +3326,6 @@ void BlockSolver::build_system_impl() {
       ba_.sys_version = ba_.est_version;
       ba_.sys_kind = es.kernel_kind;
       ba_.sys_delta = es.delta;
-      // The two sides write disjoint arrays (Hll / b_l / Hpl and Hpp / b_p): the pose side runs on a side stream
-      // next to the landmark side unless one of them is being timed on its own.
-      const bool overlap = overlap_assembly && es.touches_pose && !prof.timing(KernelProf::kAsmLandmark) && !prof.timing(KernelProf::kAsmPose);
-      if (overlap) {
-        ensure_side();
-        G2OHIP_HIP_CHECK(hipEventRecord(side_fork_, st_));             // fork before either kernel is queued
-        G2OHIP_HIP_CHECK(hipStreamWaitEvent(side_, side_fork_, 0));
-      }
       hpl_valid_ = !ba_skip_hpl_ok();
       ll_valid_ = !ba_fuse_ll_ok();   // false: the Schur tiles of the solve assemble the landmark side
       if (ll_valid_) {
@@ -3355,11 +3334,7 @@ void BlockSolver::build_system_impl() {
         prof.end(KernelProf::kAsmLandmark, st_);
       }
       prof.begin(KernelProf::kAsmPose, st_);
-      launch_ba_poses(overlap ? side_ : st_);
-      if (overlap) {
-        G2OHIP_HIP_CHECK(hipEventRecord(side_join_, side_));
-        G2OHIP_HIP_CHECK(hipStreamWaitEvent(st_, side_join_, 0));
-      }
+      launch_ba_poses();
       prof.end(KernelProf::kAsmPose, st_);
       continue;
     }
@@ -3563,17 +3538,17 @@ void BlockSolver::solve_schur() {
   require_structure();
   if (!schur_) return;
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const bool sv = sv_ready_ && sharded_virtual && chol_opt.world > 1 && linear_solver == 0 && fuse_schur_reduce;
+  const bool sv = sv_ready_ && chol_opt.world > 1 && linear_solver == 0 && fuse_schur_reduce;
   if (sv != sv_now_) drop_graph_segments();   // (the factor segments are specific to the source of the matrix)
   sv_now_ = sv;
   solve_schur_impl(!sv);
   if (sv && ex_.nbb > 0) launch_boundary_reduce();
 }
 
-// sharded_virtual: the boundary blocks of the reduced system (and the right-hand side of their diagonal ones) from this rank's
+// sharded solve: the boundary blocks of the reduced system (and the right-hand side of their diagonal ones) from this rank's
 // Hpp and partial blocks, into the region behind Hpp -- schur_reduce_kernel over the boundary list
 void BlockSolver::launch_boundary_reduce() {
-  const int G = schur_group > 0 ? schur_group : pick_group((double)n_sc_ / std::max<long>(1, n_td_));
+  const int G = pick_group((double)n_sc_ / std::max<long>(1, n_td_));
   const bool split = (p_ % 2 == 0) && G >= 2;
   double* Hs = d_Hpp.p + hpp_blocks_ * (size_t)p_ * p_;
   const int n_red = ex_.nbb;
@@ -3594,13 +3569,13 @@ void BlockSolver::launch_boundary_reduce() {
 void BlockSolver::solve_schur_impl(bool want_matrix) {
   if (profiling) ts_.start(st_);
   const size_t sizeP = (size_t)nP_ * p_;
-  const int G = schur_group > 0 ? schur_group : pick_group((double)n_sc_ / std::max<long>(1, n_td_));
+  const int G = pick_group((double)n_sc_ / std::max<long>(1, n_td_));
   // every landmark lies in exactly one tile, so the tiles can invert the landmark blocks themselves
-  const bool fuse_inv = fuse_landmark_inverse && n_tiles_ > 0 && tiles_cover_all_;
+  const bool fuse_inv = n_tiles_ > 0 && tiles_cover_all_;
   // fused EdgeProjectXYZ2UV system built from the current estimates: the tiles evaluate their Hpl blocks themselves
   const bool ba_tiles = fuse_inv && p_ == 6 && l_ == 3 && ba_.cam_q.p != nullptr && ba_recompute_ok();
-  if (!ba_tiles) {   // the generic tiles read Hpl, Hll and b_l from memory: both must be there (a fused solve with
-    ensure_hpl();    // ba_store_ll = 0 leaves Hll partial, and with ba_skip_hpl = 0 ensure_hpl alone returns at once)
+  if (!ba_tiles) {   // the generic tiles read Hpl, Hll and b_l from memory: both must be there (a fused solve leaves
+    ensure_hpl();    // Hll partial; ensure_hpl returns at once when build_system wrote Hpl)
     ensure_ll();
   }
   if (ba_tiles) {
@@ -3608,10 +3583,9 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
     prepare_ba_tile_kernels();
     prof.begin(KernelProf::kSchurBlocks, st_);
     const bool fll = !ll_valid_ || ll_hbm_partial_;   // the tiles assemble Hll / b_l / errors themselves (again, if the last ones kept Hll on chip)
-    // ... and write to HBM only what the solve path reads (Dinv, b_l) unless option ba_store_ll asks for Hll and the errors
-    // too: 150 MB less to write at the metric configuration; a later reader (maxDiagonal, multiplyHessian, chi2 without a
-    // linearisation, inspection) has them recomputed by ensure_ll()
-    const bool store_ll = ba_store_ll != 0;
+    // ... and write to HBM only what the solve path reads (Dinv, b_l), not Hll and the errors: 150 MB less to write at the
+    // metric configuration; a later reader (maxDiagonal, multiplyHessian, chi2 without a linearisation, inspection) has them
+    // recomputed by ensure_ll()
     static const int schur_abl = getenv("G2OHIP_SCHUR_ABL") ? atoi(getenv("G2OHIP_SCHUR_ABL")) & ~1 : 0;   // (timing experiments only)
 #define G2OHIP_BA_TILE(GG) G2OHIP_BA_TILE_(GG, false)
 #define G2OHIP_BA_TILE_(GG, CC)                                                                                                    \
@@ -3622,8 +3596,7 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
                          ba_.cy,                                                                                                     \
                          es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,     \
                          d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, ba_.ll_rec.p, ba_.tile_ll.p, ba_.ll_edge.p,       \
-                         (ba_.err_valid || !store_ll) ? (double*)nullptr : es.own_err.p, /* (errors of these estimates already there) */ \
-                         d_tile_q2.p, (store_ll ? 1 : 0) | schur_abl, d_slot_lm.p, ba_.ctab.p);                                            \
+                         (double*)nullptr, d_tile_q2.p, schur_abl, d_slot_lm.p, ba_.ctab.p);                                                  \
     else                                                                                                                           \
       hipLaunchKernelGGL((ba_schur_tile_kernel<GG, false, CC>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,       \
                          ba_.cams.p, ba_.pts.p, ba_.cam_q.p, ba_.pt_q.p, ba_.meas_q.p, ba_.omega_q.p, ba_.f, ba_.cx, ba_.cy,           \
@@ -3640,7 +3613,7 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
     else if (G <= 8) G2OHIP_BA_TILE(8);
     else G2OHIP_BA_TILE(16);
     ll_valid_ = true;
-    ll_hbm_partial_ = fll && !store_ll;
+    ll_hbm_partial_ = fll;
 #undef G2OHIP_BA_TILE
 #undef G2OHIP_BA_TILE_
     prof.end(KernelProf::kSchurBlocks, st_);
@@ -3701,14 +3674,14 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
 // ensure_hschur().
 void BlockSolver::launch_schur_reduce(bool matrix) {
   const int hs_nnzb = (int)hs_row.size();
-  const int G = schur_group > 0 ? schur_group : pick_group((double)n_sc_ / std::max<long>(1, n_td_));
+  const int G = pick_group((double)n_sc_ / std::max<long>(1, n_td_));
   const bool split = (p_ % 2 == 0) && G >= 2;   // rows per lane part of the tile kernel's partial layout
   chol_->set_virtual_split(split);
   if (!matrix) {
     hschur_valid_ = false;
     // one GPU, direct solver: the kernel writes the permuted right-hand side and clears the status word for the factorisation
     // that follows (solve_reduced_device then starts with the band chains: no permute_in launch, no memset)
-    const bool pre = rhs_prefill && chol_opt.world <= 1 && linear_solver == 0;
+    const bool pre = chol_opt.world <= 1 && linear_solver == 0;
     size_t xpn = 0;
     rhs_prefilled_ = pre;
 #define G2OHIP_RHS(P_)                                                                                                        \
@@ -3750,13 +3723,17 @@ void BlockSolver::ensure_hschur() {
   G2OHIP_HIP_CHECK(hipGetLastError());
 }
 
+// solve() folds the Schur reduction into the factorisation only while a block of the reduced system has at most this many
+// partial blocks on average
+constexpr double kFuseReduceMaxPartials = 6.0;
+
 // may solve() leave the reduction to the factorisation?  (one GPU, direct solver, tiled Schur pass)
 bool BlockSolver::virtual_reduced_ok() {
   // (a block of the reduced system that collects partial blocks from many tiles -- loop closures: pose pairs share
   // landmarks all over the landmark order -- is summed faster by the one fully parallel reduction pass than inside the
   // front assembly of its tree level: 6.4 against 7.5 ms per iteration on the 10 000-pose loop-closure graph)
   return schur_ && fuse_schur_reduce && chol_opt.world == 1 && linear_solver == 0 && n_tiles_ > 0 && n_active_ < 0 && !rd_ptr_h_.empty() &&
-         (double)n_td_ <= fuse_reduce_max_partials * (double)std::max<size_t>(hs_row.size(), 1);
+         (double)n_td_ <= kFuseReduceMaxPartials * (double)std::max<size_t>(hs_row.size(), 1);
 }
 
 int BlockSolver::solve_reduced() {
@@ -3997,14 +3974,14 @@ void BlockSolver::exchange_setup(int nbb, const int* bblock, const double* hkeep
   }
   ex_.buf3.alloc((size_t)nh * p_ + 1);
   ex_.buf3.zero(st_);
-  // Virtual source on a rank (sharded_virtual): as on one GPU the fronts are assembled from Hpp and the tiles' partial blocks
+  // Virtual source on a rank: as on one GPU the fronts are assembled from Hpp and the tiles' partial blocks
   // and Hschur is not written -- except the boundary blocks, whose value is a sum over ranks: those are reduced locally
   // into the region behind Hpp, summed there by the exchange and read from there by the factorisation (no partials, no
   // damping of their own: the sum holds both).
   sv_ready_ = false;
-  if (sharded_virtual && schur_ && chol_opt.world > 1 && n_tiles_ > 0 && !rd_ptr_h_.empty() && fuse_schur_reduce && linear_solver == 0 &&
+  if (schur_ && chol_opt.world > 1 && n_tiles_ > 0 && !rd_ptr_h_.empty() && fuse_schur_reduce && linear_solver == 0 &&
       d_Hpp.n >= (hpp_blocks_ + hs_row.size()) * (size_t)p_ * p_ &&
-      (double)n_td_ <= fuse_reduce_max_partials * (double)std::max<size_t>(hs_row.size(), 1)) {
+      (double)n_td_ <= kFuseReduceMaxPartials * (double)std::max<size_t>(hs_row.size(), 1)) {
     const int nb = (int)hs_row.size();
     std::vector<char> isb(nb, 0);
     for (int k = 0; k < nbb; ++k) {
@@ -5140,7 +5117,7 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
 // assembly of the CURRENT estimates (an LM trial solves before it updates; a rejected trial pops back to them), with the
 // same robust kernel, and no other edge set may contribute pose-landmark blocks.
 bool BlockSolver::ba_recompute_ok() const {
-  if (!ba_recompute_backsub || !schur_ || p_ != 6 || l_ != 3 || ba_.set < 0 || !ba_fused || !ba_.fused_ok || ba_.n_cams <= 0) return false;
+  if (!schur_ || p_ != 6 || l_ != 3 || ba_.set < 0 || !ba_fused || !ba_.fused_ok || ba_.n_cams <= 0) return false;
   if (ba_.sys_version < 0 || ba_.sys_version != ba_.est_version) return false;
   const EdgeSet& bs = *sets_[ba_.set];
   if (bs.kernel_kind != ba_.sys_kind || bs.delta != ba_.sys_delta) return false;

@@ -62,6 +62,28 @@ int guarded(F&& f) {
     set_error("null solver handle");      \
     return G2OHIP_ERR_ARG;                \
   }
+
+// the options of the factorisation (CholOptions) that both handles accept; false: not one of them
+bool set_chol_option(CholOptions& o, const char* name, double value) {
+  static const struct { const char* name; int CholOptions::*field; } kFields[] = {
+      {"nd_leaf", &CholOptions::nd_leaf},
+      {"max_sn_scalars", &CholOptions::max_sn_scalars},
+      {"max_sn_scalars_lds", &CholOptions::max_sn_scalars_lds},
+      {"dep_levels", &CholOptions::dep_levels},
+      {"band_kernel", &CholOptions::band_kernel},
+      {"tree_backward", &CholOptions::tree_backward},
+      {"big_group", &CholOptions::big_group},
+      {"big_group_min_rows", &CholOptions::big_group_min_rows},
+      {"dep_backward", &CholOptions::dep_backward},
+      {"big_front_passes", &CholOptions::big_front_passes},
+      {"dep_spin_limit", &CholOptions::dep_spin_limit}};
+  for (const auto& f : kFields)
+    if (!std::strcmp(name, f.name)) {
+      o.*f.field = (int)value;
+      return true;
+    }
+  return false;
+}
 }  // namespace
 
 // G2OHIP_OPTIONS="name=value,..." in the environment: options for every solver handle of the process, applied at creation
@@ -534,18 +556,8 @@ int g2ohip_get_stats(g2ohip_solver* s, g2ohip_stats* out) {
 int g2ohip_set_option(g2ohip_solver* s, const char* name, double value) {
   REQUIRE_HANDLE(s);
   if (!name) return G2OHIP_ERR_ARG;
-  if (!std::strcmp(name, "nd_leaf")) s->impl->chol_opt.nd_leaf = (int)value;
-  else if (!std::strcmp(name, "max_sn_scalars")) s->impl->chol_opt.max_sn_scalars = (int)value;
-  else if (!std::strcmp(name, "max_sn_scalars_lds")) s->impl->chol_opt.max_sn_scalars_lds = (int)value;
-  else if (!std::strcmp(name, "dep_levels")) s->impl->chol_opt.dep_levels = (int)value;
-  else if (!std::strcmp(name, "band_kernel")) s->impl->chol_opt.band_kernel = (int)value;
-  else if (!std::strcmp(name, "tree_backward")) s->impl->chol_opt.tree_backward = (int)value;
-  else if (!std::strcmp(name, "big_group")) s->impl->chol_opt.big_group = (int)value;
-  else if (!std::strcmp(name, "big_group_min_rows")) s->impl->chol_opt.big_group_min_rows = (int)value;
-  else if (!std::strcmp(name, "dep_backward")) s->impl->chol_opt.dep_backward = (int)value;
-  else if (!std::strcmp(name, "big_front_passes")) s->impl->chol_opt.big_front_passes = (int)value;
-  else if (!std::strcmp(name, "dep_spin_limit")) s->impl->chol_opt.dep_spin_limit = (int)value;
-  else if (!std::strcmp(name, "schur_tile_bytes")) s->impl->schur_tile_bytes = (size_t)value;
+  if (set_chol_option(s->impl->chol_opt, name, value)) {
+  } else if (!std::strcmp(name, "schur_tile_bytes")) s->impl->schur_tile_bytes = (size_t)value;
   else if (!std::strcmp(name, "comm_emulate")) s->impl->comm_emulate = (int)value;
   else if (!std::strcmp(name, "mask_solution")) s->impl->mask_solution = value != 0;
   else if (!std::strcmp(name, "linear_solver")) s->impl->linear_solver = (int)value;       // 0 Cholesky, 1 PCG
@@ -1019,18 +1031,7 @@ int g2ohip_ls_get_stats(g2ohip_linear_solver* ls, g2ohip_stats* out) {
 }
 int g2ohip_ls_set_option(g2ohip_linear_solver* ls, const char* name, double value) {
   if (!ls || !name) return G2OHIP_ERR_ARG;
-  if (!std::strcmp(name, "nd_leaf")) ls->opt.nd_leaf = (int)value;
-  else if (!std::strcmp(name, "max_sn_scalars")) ls->opt.max_sn_scalars = (int)value;
-  else if (!std::strcmp(name, "max_sn_scalars_lds")) ls->opt.max_sn_scalars_lds = (int)value;
-  else if (!std::strcmp(name, "dep_levels")) ls->opt.dep_levels = (int)value;
-  else if (!std::strcmp(name, "band_kernel")) ls->opt.band_kernel = (int)value;
-  else if (!std::strcmp(name, "tree_backward")) ls->opt.tree_backward = (int)value;
-  else if (!std::strcmp(name, "big_group")) ls->opt.big_group = (int)value;
-  else if (!std::strcmp(name, "big_group_min_rows")) ls->opt.big_group_min_rows = (int)value;
-  else if (!std::strcmp(name, "dep_backward")) ls->opt.dep_backward = (int)value;
-  else if (!std::strcmp(name, "big_front_passes")) ls->opt.big_front_passes = (int)value;
-  else if (!std::strcmp(name, "dep_spin_limit")) ls->opt.dep_spin_limit = (int)value;
-  else return G2OHIP_ERR_ARG;
+  if (!set_chol_option(ls->opt, name, value)) return G2OHIP_ERR_ARG;
   return G2OHIP_OK;
 }
 

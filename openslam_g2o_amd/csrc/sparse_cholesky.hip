@@ -20,6 +20,20 @@ constexpr int kGatherHeader = 16;                      // ... its header: childr
 constexpr int kGatherLdsOff = 3 * 64 * 65 + 64 + 128;   // ... behind the level launch's own regions (doubles)
 constexpr int kFactorThreadsGlobal = 512;
 constexpr int kChainU = 6;  // doubles per thread that carry an update matrix from one chain front to the next
+// symbolic analysis: supernode amalgamation, LDS fronts, launch shapes
+constexpr double kRelaxZeros = 0.25;              // relaxed amalgamation: tolerated share of explicit zero blocks in a panel
+constexpr size_t kRelaxFrontBytes = 42 * 1024;    // ... relaxed merges only while the front stays this small (3 workgroups per CU)
+constexpr size_t kLdsFrontBytes = 256 * 1024;     // fronts up to this DENSE size (m*m*8) are candidates for LDS (stored packed: half) ...
+constexpr size_t kLdsBudgetBytes = 150 * 1024;    // ... if blocks + vectors + index tables fit this per-workgroup LDS budget
+constexpr int kLdsMfma = (4 << 16) | 96;          // LDS fronts with at least (low 16 bits) boundary rows and (high bits) pivot blocks: pivot steps update
+                                                  // the panel only, ONE MFMA rank-npiv update of the trailing matrix afterwards (CholPlanDev::lds_mfma)
+constexpr int kWideFrontDoubles = 5000;           // launches whose largest LDS front has this many packed doubles (100 rows) use 512 threads per front
+constexpr int kWaveFrontTasks = 1024;             // launches at least this wide use two waves (128 threads) per front
+constexpr int kBigFrontMinDim = 180;              // scratch-slab fronts as whole-GPU passes (big_front_passes) on launches whose largest front has this many rows
+constexpr int kBigMergeTiles = 256;               // scratch-slab levels of at most this many 64 x 64 tiles run the fused panel kernel (panel solve + update
+                                                  // [+ pivot blocks] in one launch); wider levels the separate whole-GPU passes
+constexpr int kSplitSweepsMinDim = 512;           // forward / backward step of scratch-slab fronts by several workgroups per front (256 boundary rows each)
+                                                  // on levels whose largest such front has at least this many rows
 // register-resident wave kernel (wave_front.inc): limits of a front
 constexpr int kPanelSolveWgs = 512;      // big_panel_solve_kernel (pivot blocks + panel rows of a level in one launch) on launches of at most this many workgroups
 constexpr int kEgThreads = 256;           // big_extend_gather_kernel: threads per workgroup = scalar rows per chunk (128 / 64: no different)
@@ -438,7 +452,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
   S.sn_start.clear();
   {
     // Exact merges (identical structure) always; relaxed merges along a parent chain while the
-    // explicit zero blocks stay below opt.relax_zeros of the dense panel and the front still fits LDS.
+    // explicit zero blocks stay below kRelaxZeros of the dense panel and the front still fits LDS.
     long true_blocks = 0;  // structural blocks of the current supernode's columns
     for (int j = 0; j < nb; ++j) {
       bool merge = false;
@@ -449,12 +463,12 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
         const long tb = true_blocks + 1 + nbn;
         const bool exact = st_[j - 1].size() == st_[j].size() + 1 && total == tb;
         const size_t m = (size_t)(w + nbn) * bs;
-        const bool fits = m * m * 8 <= std::min(opt.lds_front_bytes, opt.relax_front_bytes);
+        const bool fits = m * m * 8 <= std::min(kLdsFrontBytes, kRelaxFrontBytes);
         // narrower panels for the fronts that live in LDS (shorter pivot loops per front, smaller solve panels), wide
         // ones for the scratch-slab fronts (each panel is a whole-GPU pass there)
-        const bool lds_class = m * m * 8 <= opt.lds_front_bytes;
+        const bool lds_class = m * m * 8 <= kLdsFrontBytes;
         const long cap = lds_class ? std::max(1, std::min(opt.max_sn_scalars, sn_lds) / bs) : (m >= (size_t)wide_rows ? wide_blocks : max_sn_blocks);
-        if (w <= cap && (exact || (fits && (double)(total - tb) <= opt.relax_zeros * (double)total))) merge = true;
+        if (w <= cap && (exact || (fits && (double)(total - tb) <= kRelaxZeros * (double)total))) merge = true;
       }
       if (!merge) {
         S.sn_start.push_back(j);
@@ -594,41 +608,19 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
   // maxima then fits whatever fronts share a launch.  (A front with few rows but a child with hundreds of boundary
   // blocks -- a landmark seen by hundreds of poses -- used to push a launch beyond 160 KB.)
   auto is_lds = [&](int f) {
-    if (front_dim(f) * front_dim(f) * 8 > opt.lds_front_bytes) return false;
+    if (front_dim(f) * front_dim(f) * 8 > kLdsFrontBytes) return false;
     const long long total = lds_need(f);
-    const long long cap = (long long)opt.lds_budget_bytes;
+    const long long cap = (long long)kLdsBudgetBytes;
     return total <= cap && lds_ints <= 24 * 1024 && total - lds_ints <= 134 * 1024;   // (158 KB of the CU's 160 KB)
   };
   std::vector<int> chain_next(nf, -1), has_prev(nf, 0);
-  if (opt.fuse_chains)
-    for (int f = 0; f < nf; ++f) {
-      const int p = S.f_parent[f];
-      if (p < 0 || S.child_off[p + 1] - S.child_off[p] != 1 || !is_lds(f) || !is_lds(p)) continue;
-      if ((size_t)S.f_nb[f] * (S.f_nb[f] + 1) / 2 * bs * bs > (size_t)kChainU * kFactorThreads) continue;
-      if (S.f_nb[f] * bs > 256) continue;   // solve kernels carry the boundary vector in one round
-      chain_next[f] = p;
-      has_prev[p] = 1;
-    }
-  if (opt.max_chain_fronts > 0) {
-    // Long chains are cut into segments of about equal length (a finer work granularity than whole leaf subtrees for
-    // the dependency-driven launch; the update matrix then crosses the cut through HBM instead of registers).
-    for (int f = 0; f < nf; ++f) {
-      if (has_prev[f] || chain_next[f] < 0) continue;   // chain heads only
-      int len = 0;
-      for (int g = f; g >= 0; g = chain_next[g]) ++len;
-      const int nseg = (len + opt.max_chain_fronts - 1) / opt.max_chain_fronts;
-      if (nseg <= 1) continue;
-      const int seg = (len + nseg - 1) / nseg;
-      int k = 0;
-      for (int g = f; g >= 0;) {
-        const int nx = chain_next[g];
-        if (++k % seg == 0 && nx >= 0) {
-          chain_next[g] = -1;
-          has_prev[nx] = 0;
-        }
-        g = nx;
-      }
-    }
+  for (int f = 0; f < nf; ++f) {
+    const int p = S.f_parent[f];
+    if (p < 0 || S.child_off[p + 1] - S.child_off[p] != 1 || !is_lds(f) || !is_lds(p)) continue;
+    if ((size_t)S.f_nb[f] * (S.f_nb[f] + 1) / 2 * bs * bs > (size_t)kChainU * kFactorThreads) continue;
+    if (S.f_nb[f] * bs > 256) continue;   // solve kernels carry the boundary vector in one round
+    chain_next[f] = p;
+    has_prev[p] = 1;
   }
   S.task_ptr.assign(1, 0);
   S.task_fronts.clear();
@@ -751,7 +743,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
       LL.lds_count = (int)lds[l].size();
       // levels whose fronts all fit the register-resident wave kernel (wave_front.inc): <= kWvNPV pivot columns,
       // <= 16 kWvNTL boundary rows, <= kFwdChildren children
-      LL.wv = opt.wave_kernel != 0 && glb[l].empty() && !lds[l].empty();
+      LL.wv = glb[l].empty() && !lds[l].empty();
       for (int t : lds[l]) {
         if (!LL.wv) break;
         for (int k = S.task_ptr[t]; k < S.task_ptr[t + 1] && LL.wv; ++k) {
@@ -766,7 +758,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
         }
       }
       // wide launches run two waves per front (see front_factor_kernel); *_max_m = packed doubles of the largest front
-      if (!LL.wv && opt.wave_front_tasks > 0 && LL.lds_count >= opt.wave_front_tasks) LL.sm_count = LL.lds_count;
+      if (!LL.wv && LL.lds_count >= kWaveFrontTasks) LL.sm_count = LL.lds_count;
       for (int i = 0; i < (int)lds[l].size(); ++i) {
         const int t = lds[l][i];
         S.level_fronts.push_back(t);
@@ -835,7 +827,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
   {
     std::vector<int> slot_of(nf, -1), lvl_of(nf, -1), ph_of(nf, -1);
     auto level_big = [&](const LevelLaunch& LL) {
-      if (LL.glb_count <= 0 || !opt.big_front_passes || LL.glb_max_m < opt.big_front_min_dim) return false;
+      if (LL.glb_count <= 0 || !opt.big_front_passes || LL.glb_max_m < kBigFrontMinDim) return false;
       for (int q = LL.glb_begin; q < LL.glb_begin + LL.glb_count; ++q) {
         const int f = S.task_fronts[S.task_ptr[S.level_fronts[q]]];
         if (S.f_ns[f] * bs > 64 || S.child_off[f + 1] - S.child_off[f] > 16) return false;
@@ -854,7 +846,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
           ph_of[f] = ph;
         }
       }
-    if (opt.inplace_chains && opt.world == 1)
+    if (opt.world == 1)
       for (int f = 0; f < nf; ++f) {
         if (slot_of[f] < 0 || S.child_off[f + 1] - S.child_off[f] != 1) continue;
         const int c = S.children[S.child_off[f]];
@@ -989,12 +981,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
           const int nthr = LL.sm_count > 0 ? 128 : kFactorThreads;
           // (any number of children, any boundary size: the fifth and later children and those with more boundary rows
           // than threads are added by a loop; one right-hand side value per thread in the pivot part)
-          const bool ok = R.ns * bs <= nthr && (opt.fuse_fwd_any || [&] {
-            bool o = R.child_cnt <= kFwdChildren;
-            for (int c = 0; c < R.child_cnt && o; ++c) o = cdesc[R.child_off + c].nbc * bs <= nthr;
-            return o;
-          }());
-          if (!ok) LL.fuse_fwd = false;
+          if (R.ns * bs > nthr) LL.fuse_fwd = false;
         }
         if (q < LL.glb_begin) LL.wv_idx_ints = std::max(LL.wv_idx_ints, (2 + kVirtInts) * R.asm_cnt + R.cmap_cnt + R.crel_cnt);
         if (q < LL.lds_begin + LL.sm_count) LL.sm_idx_ints = std::max(LL.sm_idx_ints, (2 + kVirtInts) * R.asm_cnt + R.cmap_cnt + R.tri_cnt + R.crel_cnt);
@@ -1080,7 +1067,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
     for (int ph = 0; ph < 2; ++ph)
       for (LevelLaunch& LL : launches_[ph]) {
         int max_children = 0;
-        bool ok = LL.glb_count > 0 && opt.big_front_passes && LL.glb_max_m >= opt.big_front_min_dim && opt.world == 1;
+        bool ok = LL.glb_count > 0 && opt.big_front_passes && LL.glb_max_m >= kBigFrontMinDim && opt.world == 1;
         for (int q = LL.glb_begin; q < LL.glb_begin + LL.glb_count; ++q) {
           const int f = S.task_fronts[S.task_ptr[S.level_fronts[q]]];
           slot_of_f[f] = q;
@@ -1274,7 +1261,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
     // blocks do not depend on any child, so both passes can run once per phase instead of once per level
     for (int ph = 0; ph < 2; ++ph) {
       auto hoistable = [&](const LevelLaunch& LL) {
-        return LL.big_ok && opt.big_front_passes && LL.glb_count > 0 && LL.glb_max_m >= opt.big_front_min_dim;
+        return LL.big_ok && opt.big_front_passes && LL.glb_count > 0 && LL.glb_max_m >= kBigFrontMinDim;
       };
       hz_begin_[ph] = (int)bt.size();
       for (LevelLaunch& LL : launches_[ph])
@@ -1305,7 +1292,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
     int fork_cover = -1, join_cover = 0, nsplit = 0, nfork = 0, njoin = 0;
     for (int l = 0; l < nlev; ++l) {
       LevelLaunch& LL = launches_[ph][l];
-      LL.split_ok = LL.glb_count > 0 && LL.lds_count > 0 && LL.big_ok && opt.big_front_passes && LL.glb_max_m >= opt.big_front_min_dim;
+      LL.split_ok = LL.glb_count > 0 && LL.lds_count > 0 && LL.big_ok && opt.big_front_passes && LL.glb_max_m >= kBigFrontMinDim;
       auto child_on = [&](int q0, int q1, bool side, int since) {
         for (int q = q0; q < q1; ++q) {
           const int t = S.level_fronts[q];
@@ -1404,31 +1391,6 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
           for (int c : signals) recs[c].pad[0] |= 2;
           G.last_level = l1 - 1;
           G.dep = true;
-          // Launch order inside a wide group: level order would dispatch a parent only after EVERY task of the
-          // level below (the last parents then wait a whole round for their children); a parent is placed
-          // dep_delay slots (about the number of resident workgroups) behind its last child instead -- still
-          // behind all its children, which is what the no-deadlock argument needs.
-          if (sm && opt.dep_delay > 0) {
-            const int b0 = G.LL.lds_begin, cnt = G.LL.lds_count;
-            std::vector<long long> key(cnt);
-            std::vector<int> pos_of_task(ntask, -1);
-            for (int i = 0; i < cnt; ++i) pos_of_task[factor_order[b0 + i]] = i;
-            for (int i = 0; i < cnt; ++i) {   // (level order: children before parents)
-              const int t = factor_order[b0 + i], f = S.task_fronts[S.task_ptr[t]];
-              long long k = -1;
-              for (int ch = S.child_off[f]; ch < S.child_off[f + 1]; ++ch) {
-                const int ct = task_of[S.children[ch]];
-                if (ct != t && pos_of_task[ct] >= 0) k = std::max(k, key[pos_of_task[ct]]);
-              }
-              key[i] = k < 0 ? (long long)i : k + opt.dep_delay;
-            }
-            std::vector<int> ord(cnt);
-            for (int i = 0; i < cnt; ++i) ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key[a] < key[b]; });
-            std::vector<int> tmp(cnt);
-            for (int i = 0; i < cnt; ++i) tmp[i] = factor_order[b0 + ord[i]];
-            std::copy(tmp.begin(), tmp.end(), factor_order.begin() + b0);
-          }
         } else {
           l1 = l + 1;
         }
@@ -1980,7 +1942,7 @@ void SparseCholesky::analyze(int nb, const int* colptr, const int* rowidx, hipSt
   plan_.status = d_status.p;
   plan_.ready = d_ready.p;
   plan_.dep_spin_limit = opt.dep_spin_limit;
-  plan_.lds_mfma = opt.lds_mfma;
+  plan_.lds_mfma = kLdsMfma;
   plan_.dbg = nullptr;
   plan_.tl = nullptr;
   plan_.slots = d_slots.p;
@@ -3042,75 +3004,11 @@ __global__ void __launch_bounds__(256) big_extend_gather_kernel(CholPlanDev P, c
   }
 }
 
-// pivot block (npiv <= 64): right-looking Cholesky, one wave per front, lane i owns row i IN REGISTERS; column j of L
-// reaches the other lanes through v_readlane (the loops are fully unrolled: lane and register indices are
-// compile-time constants) -- no LDS, no barriers, ~n^2/2 FMAs with scalar operands
+// v_readlane of a double (lane index wave-uniform)
 __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
   return __hiloint2double(hi, lo);
-}
-template <int BS, bool COH>
-__device__ __forceinline__ void big_diag_body(const CholPlanDev& P, int slot, int lane, double* __restrict__ scratch,
-                                              const long long* __restrict__ scratch_off, const int* __restrict__ scratch_ld) {
-  // COH: the panel block and the reciprocal diagonal go to L with agent-scope stores (read by other workgroups of the
-  // SAME launch: big_panel_kernel)
-  constexpr int MAXB = 64 / BS, N = MAXB * BS;
-  const int f = P.slots[slot].x;
-  const FrontRec rec = load_front_rec(P.rec + f);
-  const int ns = rec.ns, m = (rec.ns + rec.nb) * BS, n = ns * BS;
-  const int ld = scratch_ld[slot];   // leading dimension in the slab (>= m: a front continued in place sits inside its chain's first front)
-  double* F = scratch + scratch_off[slot];
-  double* Lg = P.L + rec.L_off;
-  double r[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) r[c] = (c < n && lane < n && lane >= c) ? F[(size_t)lane + (size_t)ld * c] : 0.0;
-  bool bad = false;
-#pragma unroll
-  for (int jb = 0; jb < MAXB; ++jb) {
-    if (jb < ns) {   // (wave-uniform)
-#pragma unroll
-      for (int jj = 0; jj < BS; ++jj) {
-        const int j = jb * BS + jj;
-        double d = readlane_f64(r[j], j);
-        if (!(d > 0.0)) {
-          bad = true;
-          d = 1.0;
-        }
-        double sq, rs;
-        sqrt_and_rsqrt(d, sq, rs);
-        const double l = lane > j ? r[j] * rs : (lane == j ? sq : 0.0);   // column j of L (zero above the diagonal)
-        r[j] = l;
-        if (lane == j) {
-          if (COH) st_coh(Lg + (size_t)m * n + j, rs);
-          else Lg[(size_t)m * n + j] = rs;
-        }
-#pragma unroll
-        for (int c = j + 1; c < (jb + 1) * BS; ++c) r[c] -= l * readlane_f64(l, c);
-#pragma unroll
-        for (int cb = jb + 1; cb < MAXB; ++cb)
-          if (cb < ns) {
-#pragma unroll
-            for (int cc = 0; cc < BS; ++cc) r[cb * BS + cc] -= l * readlane_f64(l, cb * BS + cc);
-          }
-      }
-    }
-  }
-  if (bad && lane == 0) atomicMax(P.status, 1);
-  if (lane < n) {
-#pragma unroll
-    for (int c = 0; c < N; ++c)
-      if (c < n) {
-        F[(size_t)lane + (size_t)ld * c] = r[c];
-        if (COH) st_coh(Lg + (size_t)lane + (size_t)m * c, r[c]);
-        else Lg[(size_t)lane + (size_t)m * c] = r[c];
-      }
-  }
-}
-template <int BS>
-__global__ void __launch_bounds__(64) big_diag_kernel(CholPlanDev P, int slot0, double* __restrict__ scratch,
-                                                     const long long* __restrict__ scratch_off, const int* __restrict__ scratch_ld) {
-  big_diag_body<BS, false>(P, slot0 + blockIdx.x, threadIdx.x, scratch, scratch_off, scratch_ld);
 }
 
 // panel rows below the pivot block: x L11' = row, one thread per row, the row in registers
@@ -4431,7 +4329,7 @@ __global__ void mask_kernel(size_t n, const double* __restrict__ mask, double* _
 // Pivot block of a scratch-slab front (n <= 64 columns) on the matrix cores: the blocked right-looking Cholesky of
 // wave_front_kernel restricted to the pivot block -- the symmetric n x n block as ten upper 16 x 16 tiles in accumulator
 // layout dealt to four waves, four columns per step (row panel by symmetry, 4 x 4 pivot block factorised by every lane,
-// scaled panel and rank-4 update one MFMA each).  The one-wave kernel (big_diag_kernel: a row per lane, columns broadcast
+// scaled panel and rank-4 update one MFMA each).  A one-wave kernel (a row per lane, columns broadcast
 // by v_readlane) needs n^2 / 2 readlane + FMA pairs in ONE instruction stream: 23 us for 48 columns, on the critical path
 // of every level of a pose graph; this one takes about half of that.
 // FWD: the forward step of fronts WITHOUT boundary rows (roots: no panel tiles) rides along; the others: big_panel_kernel.
@@ -4791,9 +4689,7 @@ struct BigLaunch {   // whole-GPU passes over the scratch-slab fronts of one lev
   bool fwd = false;       // the forward step rides along in the pivot-block and panel kernels (big_forward_carried)
   int* flag = nullptr;    // non-null: pivot blocks and panel tiles of the level in one launch (big_level_kernel), per-front flags
   const int* ld;   // leading dimension per launch slot
-  bool fuse_panel;   // big_panel_kernel instead of big_trsm_kernel + big_front_update_kernel
-  bool mfma_diag;    // big_diag_mfma_kernel instead of big_diag_kernel
-  int merge_tiles = 256;   // the fused panel kernel on levels of at most this many tiles (CholOptions::big_merge_tiles)
+  int merge_tiles = 256;   // the fused panel kernel on levels of at most this many tiles (kBigMergeTiles)
   bool gather = false;     // the merged level launch gathers the children's update matrices itself: no extend-add passes (LevelLaunch::gather)
   int eg_begin = 0, eg_count = 0;   // the level's extend-add in one launch (big_extend_gather_kernel); 0: the passes per child ordinal
   bool eg_write = false;            // ... into regions that were not zero-filled (LevelLaunch::eg_write), the original blocks la_* behind it
@@ -4867,7 +4763,7 @@ void launch_factor_level(const CholPlanDev& P, const int* d_tasks, const long lo
       hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(big.ba_count), dim3(256), 0, st, P, big.chunks + big.ba_begin, dA, d_scratch,
                          d_scratch_off, big.ld);
     G2OHIP_LAUNCH_CHECK("big_assemble_kernel");
-    const bool level_launch = big.flag && big.mfma_diag && big.fuse_panel && bt_count > 0 && bt_count <= big.merge_tiles;
+    const bool level_launch = big.flag && bt_count > 0 && bt_count <= big.merge_tiles;
     bool any_pass = false;
     for (const auto& pass : *big.be_pass) any_pass = any_pass || pass.second > 0;
     const bool gather = level_launch && big.gather && any_pass;   // (the level's launch adds the children's update matrices where it loads the fronts)
@@ -4909,21 +4805,19 @@ void launch_factor_level(const CholPlanDev& P, const int* d_tasks, const long lo
     // (at most kPanelSolveWgs workgroups: each repeats the pivot block on one wave and holds a CU's registers meanwhile -- a level of many
     // fronts is faster with the two separate launches; profiles/r6_grid_sweep.txt)
     constexpr int ps_max = kPanelSolveWgs;
-    if (big.mfma_diag && !big.fwd && big.panel_solve && big.tr_count > 0 && 4 * big.tr_count <= ps_max && !(big.fuse_panel && bt_count <= big.merge_tiles)) {
+    if (!big.fwd && big.panel_solve && big.tr_count > 0 && 4 * big.tr_count <= ps_max && bt_count > big.merge_tiles) {
       // pivot blocks + panel rows in one launch (every front of the level has boundary rows: BigLaunch::panel_solve)
       hipLaunchKernelGGL((big_panel_solve_kernel<BS>), dim3(4 * big.tr_count), dim3(256), 0, st, P, big.chunks + big.tr_begin, d_scratch,
                          d_scratch_off, big.ld);
       G2OHIP_LAUNCH_CHECK("big_panel_solve_kernel");
     } else {
-      if (big.mfma_diag && big.fwd)
+      if (big.fwd)
         hipLaunchKernelGGL((big_diag_mfma_kernel<BS, true>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, big.ld, bperm, yout);
-      else if (big.mfma_diag)
+      else
         hipLaunchKernelGGL((big_diag_mfma_kernel<BS, false>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, big.ld,
                            (const double*)nullptr, (double*)nullptr);
-      else
-        hipLaunchKernelGGL((big_diag_kernel<BS>), dim3(glb_count), dim3(64), 0, st, P, glb_begin, d_scratch, d_scratch_off, big.ld);
-      G2OHIP_LAUNCH_CHECK("big_diag_kernel");
-      if (big.fuse_panel && bt_count <= big.merge_tiles) {   // panel solve + update in one launch -- while the level is a latency chain (at most one
+      G2OHIP_LAUNCH_CHECK("big_diag_mfma_kernel");
+      if (bt_count <= big.merge_tiles) {   // panel solve + update in one launch -- while the level is a latency chain (at most one
                                                  // workgroup per CU); a level that fills the GPU pays for the rows solved more than once
         if (bt_count > 0) {
           const size_t shp = (size_t)(3 * 64 * 65 + 64 + 128) * sizeof(double);
@@ -5027,11 +4921,15 @@ void SparseCholesky::set_virtual_blocks(const VirtualBlocks& vb, hipStream_t st)
   plan_.vsplit = vb.split ? 1 : 0;
 }
 
+int SparseCholesky::merge_tiles_of(const LevelLaunch& LL) const {
+  return (LL.grouped || LL.group_in) ? -1 : kBigMergeTiles;   // (grouped chains: the separate kernels)
+}
+
 bool SparseCholesky::big_forward_carried(const LevelLaunch& LL) const {
   // (the conditions of the pivot-block kernel on the matrix cores, of the fused panel kernel and of single-front tasks with
   // at most 64 pivot columns)
-  return opt.fuse_big_forward && opt.mfma_diag && opt.fuse_panel && opt.big_front_passes && LL.big_ok && LL.glb_count > 0 &&
-         LL.glb_max_m >= opt.big_front_min_dim && LL.bt_count <= merge_tiles_of(LL) && LL.sw_count > 0;
+  return opt.big_front_passes && LL.big_ok && LL.glb_count > 0 &&
+         LL.glb_max_m >= kBigFrontMinDim && LL.bt_count <= merge_tiles_of(LL) && LL.sw_count > 0;
 }
 
 void SparseCholesky::launch_factor(const LevelLaunch& LL, const double* dA, bool fwd, hipStream_t st, bool dep, int parts) {
@@ -5042,9 +4940,9 @@ void SparseCholesky::launch_factor(const LevelLaunch& LL, const double* dA, bool
 #endif
   CholPlanDev fplan = plan_;
   fplan.slots = d_fslots.p;
-  const BigLaunch big{LL.big_ok && opt.big_front_passes && LL.glb_max_m >= opt.big_front_min_dim, d_big_tiles.p, LL.ba_begin, LL.ba_count, LL.tr_begin, LL.tr_count, &LL.be_pass,
-                      LL.fz_begin, LL.fz_count, LL.hoisted && opt.hoist_big_assembly != 0, fwd && big_forward_carried(LL),
-                      (opt.merge_diag_panel && !dep_off_) ? d_sw_flag.p : (int*)nullptr, d_scratch_ld.p, opt.fuse_panel != 0, opt.mfma_diag != 0, merge_tiles_of(LL), LL.gather && opt.big_gather != 0,
+  const BigLaunch big{LL.big_ok && opt.big_front_passes && LL.glb_max_m >= kBigFrontMinDim, d_big_tiles.p, LL.ba_begin, LL.ba_count, LL.tr_begin, LL.tr_count, &LL.be_pass,
+                      LL.fz_begin, LL.fz_count, LL.hoisted, fwd && big_forward_carried(LL),
+                      !dep_off_ ? d_sw_flag.p : (int*)nullptr, d_scratch_ld.p, merge_tiles_of(LL), LL.gather,
                       LL.eg_begin, LL.eg_count, LL.eg_write, LL.eg_maxc, LL.la_begin, LL.la_count, LL.tr_all};
   const bool virt = dA == nullptr;   // assemble from the virtual source (set_virtual_blocks)
   if (virt && !has_virtual_blocks()) throw StateFailure("SparseCholesky::factor: no matrix and no virtual source");
@@ -5052,7 +4950,7 @@ void SparseCholesky::launch_factor(const LevelLaunch& LL, const double* dA, bool
   launch_factor_level<BS_, V_>(fplan, d_level_fronts.p, d_scratch_off.p, d_scratch.p, dA, LL.lds_begin, LL.lds_count, LL.lds_max_m, \
                                LL.glb_begin, LL.glb_count, LL.lds_idx_ints, LL.glb_idx_ints, LL.sm_count, LL.sm_max_m,            \
                                LL.sm_idx_ints, LL.lds_vec_m, fwd ? d_xp.p : (const double*)nullptr, fwd ? d_y.p : (double*)nullptr,   \
-                               dep ? 1 : 0, d_big_tiles.p + LL.bt_begin, LL.bt_count, big, opt.wide_front_doubles, LL.wv, LL.wv_pn,   \
+                               dep ? 1 : 0, d_big_tiles.p + LL.bt_begin, LL.bt_count, big, kWideFrontDoubles, LL.wv, LL.wv_pn,   \
                                LL.wv_idx_ints, st, parts)
   switch (bs_) {
     case 3:
@@ -5161,8 +5059,8 @@ void SparseCholesky::factor_phase(const double* dA, int phase, hipStream_t st, b
     dbg_launch_ = 0;
   }
 #endif
-  if ((parts & 2) && opt.merge_diag_panel && !dep_off_ && d_sw_flag.p && ha_count_[phase] > 0) d_sw_flag.zero(st);   // per-front flags of big_level_kernel (phases with scratch-slab levels only)
-  if ((parts & 2) && opt.hoist_big_assembly && (hz_count_[phase] > 0 || ha_count_[phase] > 0)) {
+  if ((parts & 2) && !dep_off_ && d_sw_flag.p && ha_count_[phase] > 0) d_sw_flag.zero(st);   // per-front flags of big_level_kernel (phases with scratch-slab levels only)
+  if ((parts & 2) && (hz_count_[phase] > 0 || ha_count_[phase] > 0)) {
     const bool virt = dA == nullptr;
     if (virt && !has_virtual_blocks()) throw StateFailure("SparseCholesky::factor: no matrix and no virtual source");
     if (hz_count_[phase] > 0)
@@ -5208,8 +5106,8 @@ void SparseCholesky::factor_phase(const double* dA, int phase, hipStream_t st, b
     const LevelLaunch& LL = G.LL;
     const bool fused = fwd && LL.fuse_fwd;
     if (!(parts & 2) && !band_usable(G, dA)) continue;   // (a band-only call: nothing else of this group)
-    const bool big_passes = LL.big_ok && opt.big_front_passes && LL.glb_max_m >= opt.big_front_min_dim;
-    if (opt.overlap_level_halves && st != nullptr && big_passes && LL.glb_count > 0 && LL.lds_count > 0 && !G.dep && (fused || !fwd)) {
+    const bool big_passes = LL.big_ok && opt.big_front_passes && LL.glb_max_m >= kBigFrontMinDim;
+    if (st != nullptr && big_passes && LL.glb_count > 0 && LL.lds_count > 0 && !G.dep && (fused || !fwd)) {
       // (levels with large fronts only stay on one stream: a forward step moved to a side stream was measured to cost more
       // in cross-stream dependencies than the 14 us it hides)
       // The LDS fronts and the scratch-slab fronts of a level do not depend on each other: the one launch of the former
@@ -5222,7 +5120,7 @@ void SparseCholesky::factor_phase(const double* dA, int phase, hipStream_t st, b
       }
       // (lazy: the streams wait for each other only where the tree asks for it -- LevelLaunch::fork / join; the first use of the side
       // stream in a call always forks: inside a stream capture that is what makes it part of the graph)
-      const bool lazy = opt.lazy_level_joins && LL.split_ok && !side_unsure;
+      const bool lazy = LL.split_ok && !side_unsure;
       if (side_dirty && (!lazy || LL.join)) {
         G2OHIP_HIP_CHECK(hipStreamWaitEvent(st, ev_[1], 0));
         side_dirty = false;
@@ -5250,12 +5148,12 @@ void SparseCholesky::factor_phase(const double* dA, int phase, hipStream_t st, b
       }
       continue;
     }
-    if (side_dirty && (!opt.lazy_level_joins || LL.join || LL.split_ok || side_unsure)) {   // (a front of this level has a child on the side stream)
+    if (side_dirty && (LL.join || LL.split_ok || side_unsure)) {   // (a front of this level has a child on the side stream)
       G2OHIP_HIP_CHECK(hipStreamWaitEvent(st, ev_[1], 0));
       side_dirty = false;
     }
     if (LL.split_ok) side_unsure = true;   // (a level the plan put on the side stream ran here: its fork / join flags no longer describe the streams)
-    if (opt.group_forward_side && st != nullptr && big_passes && (LL.grouped || LL.group_in) && LL.lds_count == 0 && LL.glb_count > 0 && !G.dep && fwd &&
+    if (st != nullptr && big_passes && (LL.grouped || LL.group_in) && LL.lds_count == 0 && LL.glb_count > 0 && !G.dep && fwd &&
         !big_forward_carried(LL)) {
       // Panels of a grouped in-place chain: the forward step of a panel (20 us of a 65 us level) needs the panel's solved rows and the
       // previous panel's update vector, nothing of the next panel's factorisation -- it runs on the side stream next to it (inside a
@@ -5534,7 +5432,7 @@ void SparseCholesky::launch_solve(const LevelLaunch& LL, bool fwd, hipStream_t s
     max_m = LL.lds_vec_m;
     max_panel = LL.lds_max_panel;
   }
-  if (!dep && !skip_glb && opt.split_sweeps && LL.sw_count > 0 && LL.glb_max_m >= opt.split_sweeps_min_dim) {
+  if (!dep && !skip_glb && LL.sw_count > 0 && LL.glb_max_m >= kSplitSweepsMinDim) {
     // the scratch-slab fronts of the level: several workgroups per front; the LDS / register fronts (independent of
     // them: same level) follow in their own launch, sized for themselves
     const int4* ch = d_big_tiles.p + LL.sw_begin;
@@ -5620,7 +5518,7 @@ void SparseCholesky::solve_forward_phase(int phase, hipStream_t st) {
 }
 void SparseCholesky::solve_backward_phase(int phase, hipStream_t st) {
   // overwrite d_xp with the solution, highest level first
-  const bool merge = opt.merge_backward_levels && opt.split_sweeps && !dep_off_ && !bw_groups_[phase].empty();
+  const bool merge = !dep_off_ && !bw_groups_[phase].empty();
   bool flags_zeroed = false;
   for (size_t g = groups_[phase].size(); g-- > 0;) {
     const FactorGroup& G = groups_[phase][g];

@@ -363,7 +363,7 @@ __global__ void __launch_bounds__(64 * kWvWaves, 4) wave_front_kernel(WvPlan P, 
     __syncthreads();
     // ---- factorisation in three phases (round 6; replaces six 4-column right-looking steps with two barriers each)
     //   1. the pivot block F11 = L11 L11' (<= 24 columns) by COLUMN BLOCKS dealt to the waves (six columns each; seven for 7 x 7
-    //      blocks): lane i = row i, a wave's columns in registers, the pivot column through v_readlane (big_diag_body's scheme);
+    //      blocks): lane i = row i, a wave's columns in registers, the pivot column through v_readlane;
     //      lanes 32 + c carry column c of the rows of W = L11^-1 through the SAME instructions (row j of W is scaled like column j
     //      of L, row c of W receives -L(c, j) x row j like column c of F11).  A wave factorises its block, publishes it in LDS,
     //      a barrier, the waves behind apply it to their columns (the multipliers L(c, j) as LDS broadcast reads): the critical
