@@ -2657,12 +2657,11 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
     // The symbolic analysis of the reduced system (nested dissection, supernodes, frontal matrices, launch plans: 0.08 s at the
     // metric configuration) needs nothing but this pattern: it runs on a thread of its own next to the Schur tiles' set-up below.
     new_chol = std::make_unique<SparseCholesky>(p);
-    new_chol->opt = chol_opt;
     if (setup_overlap) {
       analysis_thread = std::thread([&] {
         try {
           G2OHIP_HIP_CHECK(hipSetDevice(device_));
-          new_chol->analyze(nP, hs_colptr.data(), hs_row.data(), st_);
+          new_chol->analyze(nP, hs_colptr.data(), hs_row.data(), chol_opt, st_);
         } catch (...) {
           analysis_error = std::current_exception();
         }
@@ -2960,9 +2959,8 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
     chol_ = std::move(new_chol);
   } else {
     chol_ = new_chol ? std::move(new_chol) : std::make_unique<SparseCholesky>(p);
-    chol_->opt = chol_opt;
-    if (schur_) chol_->analyze(nP, hs_colptr.data(), hs_row.data(), st_);
-    else chol_->analyze(nP, pp_colptr.data(), pp_row.data(), st_);
+    if (schur_) chol_->analyze(nP, hs_colptr.data(), hs_row.data(), chol_opt, st_);
+    else chol_->analyze(nP, pp_colptr.data(), pp_row.data(), chol_opt, st_);
   }
   // (the exchange of a sharded job was set up for the previous structure: its index lists address the old pattern and a merged
   // payload (sharded_merge) lives behind the previous Cholesky's exchange buffer -- gone with it)
@@ -3746,9 +3744,9 @@ int BlockSolver::solve_reduced() {
 }
 
 int BlockSolver::solve_reduced_impl() {
-  if (!chol_->analyzed()) {
-    if (schur_) chol_->analyze(nP_, hs_colptr.data(), hs_row.data(), st_);
-    else chol_->analyze(nP_, pp_colptr.data(), pp_row.data(), st_);
+  if (!chol_->analyzed()) {   // (again, with the options of the last analysis)
+    if (schur_) chol_->analyze(nP_, hs_colptr.data(), hs_row.data(), chol_->options(), st_);
+    else chol_->analyze(nP_, pp_colptr.data(), pp_row.data(), chol_->options(), st_);
   }
   if (linear_solver == 1) {   // LinearSolverPCG on the reduced system
     if (!pcg_) pcg_ = std::make_unique<BlockPCG>(p_);

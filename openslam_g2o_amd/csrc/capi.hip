@@ -432,12 +432,11 @@ int g2ohip_partition_poses(const g2ohip_solver* options_from, int block_dim, int
                            int world, int32_t* pose_owner, int32_t* block_consumer) {
   if (!colptr || !rowidx || !pose_owner || n_blocks <= 0 || world < 1) return G2OHIP_ERR_ARG;
   return guarded([&] {
-    SparseCholesky chol(block_dim);
-    if (options_from) chol.opt = options_from->impl->chol_opt;
-    chol.opt.rank = 0;
-    chol.opt.world = world;
-    chol.analyze(n_blocks, colptr, rowidx, nullptr, /*host_only=*/true);
-    const CholSymbolic& S = chol.symbolic();
+    CholOptions opt = options_from ? options_from->impl->chol_opt : CholOptions();
+    opt.rank = 0;
+    opt.world = world;
+    const CholPlan plan = plan_cholesky(block_dim, n_blocks, colptr, rowidx, opt);
+    const CholSymbolic& S = plan.sym;
     std::copy(S.pose_owner.begin(), S.pose_owner.end(), pose_owner);
     if (block_consumer) std::copy(S.block_consumer.begin(), S.block_consumer.end(), block_consumer);
     return G2OHIP_OK;
@@ -884,10 +883,9 @@ bool same_pattern(const std::vector<int>& cp, const std::vector<int>& ri, int n_
 void analyze_into(g2ohip_linear_solver* ls, std::unique_ptr<SparseCholesky>& chol, std::vector<int>& cp, std::vector<int>& ri, int n_blocks,
                   const int32_t* colptr, const int32_t* rowidx) {
   chol = std::make_unique<SparseCholesky>(ls->bs);
-  chol->opt = ls->opt;
   cp.assign(colptr, colptr + n_blocks + 1);
   ri.assign(rowidx, rowidx + colptr[n_blocks]);
-  chol->analyze(n_blocks, colptr, rowidx, ls->st);
+  chol->analyze(n_blocks, colptr, rowidx, ls->opt, ls->st);
 }
 // factorise; a dependency-driven launch that gave up waiting is not "not positive definite": once more, level by level
 bool factor_checked(SparseCholesky& chol, const double* dA, hipStream_t st) {

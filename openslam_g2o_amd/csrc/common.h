@@ -77,13 +77,6 @@ inline void host_parallel_for(size_t n, Fn fn, size_t grain = (size_t)1 << 15) {
   host_parallel_chunks(n, want < nt ? want : nt, [&](size_t, size_t b, size_t e) { fn(b, e); });
 }
 
-// When set, DevBuf operations are skipped: lets the host-only symbolic analysis (partition queries, CPU
-// tests) share the code path of the device build without touching HIP.
-inline bool& host_only_flag() {
-  static thread_local bool f = false;
-  return f;
-}
-
 template <class T>
 struct DevBuf {
   T* p = nullptr;
@@ -109,7 +102,6 @@ struct DevBuf {
     n = 0;
   }
   void alloc(size_t count) {
-    if (host_only_flag()) return;
     if (count <= n && p) return;
     release();
     if (count == 0) count = 1;
@@ -117,7 +109,6 @@ struct DevBuf {
     n = count;
   }
   void upload(const T* h, size_t count, hipStream_t st) {
-    if (host_only_flag()) return;
     alloc(count);
     if (count) G2OHIP_HIP_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st));
   }
@@ -130,7 +121,6 @@ struct DevBuf {
     G2OHIP_HIP_CHECK(hipStreamSynchronize(st));
   }
   void zero(hipStream_t st) {
-    if (host_only_flag()) return;
     if (p && n) G2OHIP_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(T), st));
   }
 };

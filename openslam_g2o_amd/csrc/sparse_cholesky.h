@@ -155,14 +155,115 @@ struct CholPlanDev {
   const int4* band_entv;   // the same with the virtual source's fields (set_virtual_blocks)
 };
 
+// used by both the symbolic analysis (sparse_cholesky_plan.hip) and the kernels / launches (sparse_cholesky.hip)
+constexpr int kFactorThreads = 256;
+constexpr int kFwdChildren = 4;   // fused forward sweep: children per front handled by the factor kernel
+constexpr int kGatherInts = 1024;                      // scratch-slab fronts gathered at load time: gather table of a front (header + children x blocks) staged in LDS
+constexpr int kGatherHeader = 16;                      // ... its header: children, offsets of their update matrices
+constexpr int kChainU = 6;  // doubles per thread that carry an update matrix from one chain front to the next
+constexpr int kBigMergeTiles = 256;               // scratch-slab levels of at most this many 64 x 64 tiles run the fused panel kernel (panel solve + update
+                                                  // [+ pivot blocks] in one launch); wider levels the separate whole-GPU passes
+constexpr int kEgThreads = 256;           // big_extend_gather_kernel: threads per workgroup = scalar rows per chunk (128 / 64: no different)
+// register-resident wave kernel (wave_front.inc): limits of a front
+constexpr int kWvNPV = 24;             // pivot columns (scalars)
+constexpr int kWvNTL = 3;              // 16-row tiles of boundary rows (48 rows)
+
+// per level launch info
+struct LevelLaunch {
+  int lds_begin = 0, lds_count = 0, lds_max_m = 0;     // index range in d_level_fronts
+  int glb_begin = 0, glb_count = 0, glb_max_m = 0;
+  int max_panel = 0;                                   // max m*npiv (doubles) for solve kernels
+  int max_m = 0;
+  int fz_begin = 0, fz_count = 0;                      // zero-fill chunks of the scratch-slab fronts that start a region at this level
+  bool hoisted = false;                                // its fill / assembly chunks are also in the phase-wide lists (CholPlan::hz_* / ha_*)
+  int lds_max_panel = 0;                               // max_panel over the LDS / register fronts only
+  int sw_begin = 0, sw_count = 0;                      // row chunks of the scratch-slab fronts for the multi-workgroup sweeps (d_big_tiles); 0: not eligible
+  int lds_vec_m = 0;                                   // largest front dimension among the LDS / register fronts only (their vectors in LDS)
+  int lds_idx_ints = 0, glb_idx_ints = 0;              // staged index lists (ints) per front, max over the launch
+  bool fuse_fwd = true;                                // every LDS front of the launch is within the fused forward sweep's limits
+  int sm_count = 0, sm_max_m = 0, sm_idx_ints = 0;     // leading part of the lds range: small fronts, one wave each
+  bool wv = false;                                     // every front fits the register-resident wave kernel (wave_front.inc)
+  int wv_pn = 0, wv_idx_ints = 0;                      // ... its panel region (doubles) and index tables (ints), max over the launch
+  bool grouped = false;                                // a front of the launch is the LAST panel of a group of an in-place chain (its tiles carry the group's columns: separate kernels)
+  bool group_in = false;                               // ... a panel INSIDE a group (its tiles stop at the group's end: the fused kernels clip)
+  int bt_begin = 0, bt_count = 0;                      // 64 x 64 trailing-update tiles of the scratch-slab fronts (d_big_tiles)
+  // scratch-slab fronts as whole-GPU passes (all ranges index d_big_tiles): assembly chunks, one extend-add pass
+  // per child ordinal, row chunks of the panel solve; big_ok: every such front has at most 64 pivot columns
+  int ba_begin = 0, ba_count = 0, tr_begin = 0, tr_count = 0;
+  std::vector<std::pair<int, int>> be_pass;
+  long long glb_scratch = 0;                           // doubles of the scratch slab this launch uses
+  bool big_ok = false;
+  bool big_passes = false;                             // the level's scratch-slab fronts run as whole-GPU passes: big_ok, the option
+                                                       // big_front_passes and a front of at least kBigFrontMinDim rows
+  bool eg_ok = false;                                  // the level's extend-add as one launch (big_extend_gather_kernel: every front has a map table, 2..7 children)
+  int eg_begin = 0, eg_count = 0;                      // ... its chunks (d_big_tiles)
+  int eg_maxc = 7;                                     // ... children per front at most
+  bool eg_write = false;                               // ... and it WRITES the regions of its fronts (no zero fill for them; their original blocks, and those of the
+                                                       // fronts continued in place behind them, are added behind it: la_*)
+  int la_begin = 0, la_count = 0;
+  bool tr_all = false;                                 // every scratch-slab front of the level has boundary rows (big_panel_solve_kernel)
+  // levels whose LDS fronts run on a side stream next to the scratch-slab passes: split_ok = the level
+  // qualifies by its structure; fork = an LDS front of it has a child that ran on the main stream since the side stream last
+  // waited for it; join = a front of the main part has a child that ran on the side stream since the main stream last did
+  bool split_ok = false, fork = false, join = false;
+  bool gather = false;                                 // every scratch-slab front of the level can gather its children's update matrices at load time (cinv tables): no extend-add passes
+};
+struct FactorGroup {
+  LevelLaunch LL; int first_level, last_level; bool dep; int band_count = 0, band_rec0 = 0, band_ent_cap = 0, band_tab_cap = 0;
+  int tb_grp0 = 0, tb_ngrp = 0, tb_low = 0;   // tree_backward: its groups (d_tb_grec), the launch slots (lowest levels) left to the per-task kernel
+};
+// merged backward launches: per phase, runs of consecutive levels (top level first) of scratch-slab fronts only
+struct BwGroup { int top_level, bottom_level, begin, count; };
+struct SegCopy { long long a, b; int n, flags; };  // exchange segment: a = offset in U (or w: flag 2), b = offset in xbuf; flag 1 = mine
+
+// the fused panel kernel on levels of at most this many tiles (-1: none)
+inline int merge_tiles_of(const LevelLaunch& LL) {
+  return (LL.grouped || LL.group_in) ? -1 : kBigMergeTiles;   // (grouped chains: the separate kernels)
+}
+
+// Host result of the symbolic analysis: everything SparseCholesky uploads or keeps.  No device state.
+struct CholPlan {
+  CholOptions opt;   // the options the plan was built from
+  CholSymbolic sym;
+  CholStats stats;
+  std::vector<LevelLaunch> launches[2];   // [0] own tasks, [1] shared top-of-tree tasks
+  std::vector<FactorGroup> groups[2];     // factorisation launches: runs of levels (dep: one launch, in-kernel dependencies)
+  std::vector<BwGroup> bw_groups[2];
+  std::vector<int> bw_of_level[2];        // level -> index into bw_groups or -1
+  int hz_begin[2] = {0, 0}, hz_count[2] = {0, 0}, ha_begin[2] = {0, 0}, ha_count[2] = {0, 0};   // phase-wide fill / assembly chunks (big_tiles)
+  // the tables of CholPlanDev (see there)
+  std::vector<FrontRec> recs;
+  std::vector<ChildDesc> cdesc;
+  std::vector<int> crel, cmap, tri, cinv, gtab, gtab_off;
+  std::vector<int2> cinv_slot;
+  std::vector<int4> big_tiles;            // chunks of the whole-GPU passes (LevelLaunch ranges)
+  std::vector<BandChainRec> band_rec;
+  std::vector<int> band_tab;
+  std::vector<int4> band_ent;             // (set_virtual_blocks derives the virtual source's copy from it)
+  std::vector<int> band_ent_asm;          // assembly entry (index into asm_q) of every band entry
+  std::vector<int4> tb_grec;              // tree_backward: see SparseCholesky::d_tb_grec
+  std::vector<int2> tb_front;
+  std::vector<int> tb_rows;
+  std::vector<SegCopy> xseg;              // multi-GPU exchange segments
+  std::vector<double> xmask;              // 1 on the solution entries this rank owns
+  std::vector<int2> slots, fslots, bslots;   // launch slot -> (first front, chain length): level order, factor order, reversed level order
+  std::vector<long long> scratch_off;     // per launch slot: offset of a scratch-slab front in the slab
+  std::vector<int> scratch_ld;            // ... its leading dimension (that of the chain's first front)
+  long long scratch_max = 0;              // doubles of the slab
+  // element counts of the work buffers
+  size_t n_sw_flag = 0, n_sw_part = 0, n_sw_cnt = 0, n_ready = 0, n_xbuf = 0;
+};
+
+// Host symbolic analysis of an upper-triangular block-CCS pattern (rows <= col, sorted) with bs x bs blocks.
+CholPlan plan_cholesky(int bs, int nb, const int* colptr, const int* rowidx, const CholOptions& opt);
+
 class SparseCholesky {
  public:
   explicit SparseCholesky(int block_size) : bs_(block_size) {}
-  CholOptions opt;
 
-  // Host symbolic analysis of an upper-triangular block-CCS pattern (rows <= col, sorted).
-  // host_only: no device work at all (partition queries, CPU tests).
-  void analyze(int nb, const int* colptr, const int* rowidx, hipStream_t st, bool host_only = false);
+  // Symbolic analysis of an upper-triangular block-CCS pattern (rows <= col, sorted): plan_cholesky, then the upload of
+  // the plan.  Every later call works by the options given here.
+  void analyze(int nb, const int* colptr, const int* rowidx, const CholOptions& opt, hipStream_t st);
   bool analyzed() const { return analyzed_; }
   void reset() { analyzed_ = false; }
 
@@ -197,7 +298,7 @@ class SparseCholesky {
   // room for `n` more doubles BEHIND the subtree-root segments of the exchange buffer (the caller's own payload travels in
   // the same all-reduce: BlockSolver's boundary blocks); pack_exchange clears and fills the head only
   double* reserve_exchange_tail(size_t n);
-  double* permuted_solution(size_t* count) { *count = (size_t)sym_.nb * bs_; return d_xp.p; }
+  double* permuted_solution(size_t* count) { *count = (size_t)hplan_.sym.nb * bs_; return d_xp.p; }
   // A caller that produces the right-hand side itself may write it permuted (xp[iperm[old] * bs + r]) and clear the status word
   // in the same kernel: solve_begin and the memset of factor_phase(phase 0) are then two launches less (skip_status_clear)
   const int* inverse_permutation_device() const { return d_iperm.p; }
@@ -230,15 +331,15 @@ class SparseCholesky {
   // (the caller drops its captured graphs and repeats the solve)
   bool dependency_stall() { const bool v = dep_stalled_; dep_stalled_ = false; return v; }
 
-  const CholStats& stats() const { return stats_; }
-  const CholSymbolic& symbolic() const { return sym_; }
+  const CholOptions& options() const { return hplan_.opt; }   // those of the last analyze()
+  const CholStats& stats() const { return hplan_.stats; }
+  const CholSymbolic& symbolic() const { return hplan_.sym; }
   int block_size() const { return bs_; }
 
  private:
   int bs_;
   bool analyzed_ = false;
-  CholSymbolic sym_;
-  CholStats stats_;
+  CholPlan hplan_;   // host plan (plan_cholesky)
   // device plan
   DevBuf<int> d_f_ns, d_f_nb, d_f_c0, d_rows_off, d_rows, d_rel_off, d_rel, d_asm_off, d_asm_q, d_asm_pos,
       d_child_off, d_children, d_level_fronts, d_perm, d_iperm, d_status;
@@ -259,64 +360,14 @@ class SparseCholesky {
   DevBuf<int> d_crel, d_cmap, d_tri, d_task_ptr, d_task_fronts, d_cinv, d_gtab, d_gtab_off;
   DevBuf<int2> d_cinv_slot;
   DevBuf<double> d_L, d_U, d_w, d_y, d_xp, d_scratch;
-  int hz_begin_[2] = {0, 0}, hz_count_[2] = {0, 0}, ha_begin_[2] = {0, 0}, ha_count_[2] = {0, 0};   // phase-wide fill / assembly chunks (d_big_tiles)
-  // merged backward launches: per phase, runs of consecutive levels (top level first) of scratch-slab fronts only
-  struct BwGroup { int top_level, bottom_level, begin, count; };
-  std::vector<BwGroup> bw_groups_[2];
-  std::vector<int> bw_of_level_[2];   // level -> index into bw_groups_ or -1
   DevBuf<int> d_sw_flag;              // per front: its pivot part of the solution is in memory (merged launches)
   DevBuf<double> d_sw_part;     // multi-workgroup backward step: per row chunk the partial L21' x (64 doubles)
   DevBuf<int> d_sw_cnt;         // ... and per launch slot the chunks that have delivered (the last one finishes the front and resets it)
   DevBuf<double> d_sweep_vec;   // vectors of the triangular sweeps of fronts too large for LDS
-  // per level launch info
-  struct LevelLaunch {
-    int lds_begin = 0, lds_count = 0, lds_max_m = 0;     // index range in d_level_fronts
-    int glb_begin = 0, glb_count = 0, glb_max_m = 0;
-    int max_panel = 0;                                   // max m*npiv (doubles) for solve kernels
-    int max_m = 0;
-    int fz_begin = 0, fz_count = 0;                      // zero-fill chunks of the scratch-slab fronts that start a region at this level
-    bool hoisted = false;                                // its fill / assembly chunks are also in the phase-wide lists (hz_ / ha_)
-    int lds_max_panel = 0;                               // max_panel over the LDS / register fronts only
-    int sw_begin = 0, sw_count = 0;                      // row chunks of the scratch-slab fronts for the multi-workgroup sweeps (d_big_tiles); 0: not eligible
-    int lds_vec_m = 0;                                   // largest front dimension among the LDS / register fronts only (their vectors in LDS)
-    int lds_idx_ints = 0, glb_idx_ints = 0;              // staged index lists (ints) per front, max over the launch
-    bool fuse_fwd = true;                                // every LDS front of the launch is within the fused forward sweep's limits
-    int sm_count = 0, sm_max_m = 0, sm_idx_ints = 0;     // leading part of the lds range: small fronts, one wave each
-    bool wv = false;                                     // every front fits the register-resident wave kernel (wave_front.inc)
-    int wv_pn = 0, wv_idx_ints = 0;                      // ... its panel region (doubles) and index tables (ints), max over the launch
-    bool grouped = false;                                // a front of the launch is the LAST panel of a group of an in-place chain (its tiles carry the group's columns: separate kernels)
-    bool group_in = false;                               // ... a panel INSIDE a group (its tiles stop at the group's end: the fused kernels clip)
-    int bt_begin = 0, bt_count = 0;                      // 64 x 64 trailing-update tiles of the scratch-slab fronts (d_big_tiles)
-    // scratch-slab fronts as whole-GPU passes (all ranges index d_big_tiles): assembly chunks, one extend-add pass
-    // per child ordinal, row chunks of the panel solve; big_ok: every such front has at most 64 pivot columns
-    int ba_begin = 0, ba_count = 0, tr_begin = 0, tr_count = 0;
-    std::vector<std::pair<int, int>> be_pass;
-    long long glb_scratch = 0;                           // doubles of the scratch slab this launch uses
-    bool big_ok = false;
-    bool eg_ok = false;                                  // the level's extend-add as one launch (big_extend_gather_kernel: every front has a map table, 2..7 children)
-    int eg_begin = 0, eg_count = 0;                      // ... its chunks (d_big_tiles)
-    int eg_maxc = 7;                                     // ... children per front at most
-    bool eg_write = false;                               // ... and it WRITES the regions of its fronts (no zero fill for them; their original blocks, and those of the
-                                                         // fronts continued in place behind them, are added behind it: la_*)
-    int la_begin = 0, la_count = 0;
-    bool tr_all = false;                                 // every scratch-slab front of the level has boundary rows (big_panel_solve_kernel)
-    // levels whose LDS fronts run on a side stream next to the scratch-slab passes: split_ok = the level
-    // qualifies by its structure; fork = an LDS front of it has a child that ran on the main stream since the side stream last
-    // waited for it; join = a front of the main part has a child that ran on the side stream since the main stream last did
-    bool split_ok = false, fork = false, join = false;
-    bool gather = false;                                 // every scratch-slab front of the level can gather its children's update matrices at load time (cinv tables): no extend-add passes
-  };
-  std::vector<LevelLaunch> launches_[2];   // [0] own tasks, [1] shared top-of-tree tasks
-  struct FactorGroup {
-    LevelLaunch LL; int first_level, last_level; bool dep; int band_count = 0, band_rec0 = 0, band_ent_cap = 0, band_tab_cap = 0;
-    int tb_grp0 = 0, tb_ngrp = 0, tb_low = 0;   // tree_backward: its groups (d_tb_grec), the launch slots (lowest levels) left to the per-task kernel
-  };
-  std::vector<FactorGroup> groups_[2];     // factorisation launches: runs of levels (dep: one launch, in-kernel dependencies)
   DevBuf<int> d_ready;
   DevBuf<int4> d_tb_grec;    // tree_backward: per group (first entry of d_tb_front, fronts, levels, front to wait for)
   DevBuf<int2> d_tb_front;   // ... per group front (front, level inside the group | tasks to release << 8), level by level
   DevBuf<int> d_tb_rows;     // ... the boundary row lists (indexed like d_rows) with the rows a front of the same group owns replaced by -1 - (offset in LDS)
-  struct SegCopy { long long a, b; int n, flags; };  // exchange segment: a = offset in U (or w: flag 2), b = offset in xbuf; flag 1 = mine
   DevBuf<SegCopy> d_xseg;
   DevBuf<double> d_xbuf, d_xmask;
   DevBuf<long long> d_dbg;
@@ -325,8 +376,6 @@ class SparseCholesky {
   DevBuf<BandChainRec> d_band_rec;
   DevBuf<int> d_band_tab;
   DevBuf<int4> d_band_ent, d_band_entv;
-  std::vector<int4> band_ent_h_;        // host copy of d_band_ent (set_virtual_blocks derives d_band_entv from it)
-  std::vector<int> band_ent_asm_;       // assembly entry (index into asm_q) of every band entry
   DevBuf<int4> d_big_tiles;
   int n_slots_ = 0;
   bool dep_off_ = false, dep_stalled_ = false;
@@ -340,8 +389,8 @@ class SparseCholesky {
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
   void launch_solve(const LevelLaunch& LL, bool fwd, hipStream_t st, bool glb_only = false, bool dep = false, bool skip_glb = false, int dep_tail = 0);
   bool big_forward_carried(const LevelLaunch& LL) const;   // the forward step of the level's scratch-slab fronts rides along in their factorisation
+  void upload_plan(hipStream_t st);   // device copies of hplan_'s tables, the work buffers and storage; fills plan_
   static void prepare_kernels();
-  int merge_tiles_of(const LevelLaunch& LL) const;   // the fused panel kernel on levels of at most this many tiles (-1: none)
   CholPlanDev plan_{};
 };
 
