@@ -461,6 +461,34 @@ int g2ohip_pg_push(g2ohip_solver* s);
 int g2ohip_pg_pop(g2ohip_solver* s);
 int g2ohip_pg_discard_top(g2ohip_solver* s);
 
+/* ---- ... its landmark half: odometry between poses PLUS point landmarks observed from them ---------------------
+ * One pose-landmark observation set of the same handle beside the pose-pose set of g2ohip_pg_set_edges, the landmark
+ * estimates resident on the device:
+ *   type 3 = EdgeSE2PointXY over VertexSE2 / VertexPointXY (g2o/types/slam2d/edge_se2_pointxy.h:44-49 computeError,
+ *            edge_se2_pointxy.cpp:66-90 linearizeOplus, vertex_point_xy.h:77-81 oplusImpl): e = R(theta)' (l - t) - z,
+ *            measurements [n][2], information [n][2x2], landmarks (x, y); beside a type-1 pose set only;
+ *   type 4 = EdgeSE3PointXYZ over VertexSE3 / VertexPointXYZ (g2o/types/slam3d/edge_se3_pointxyz.cpp:95-131 computeError /
+ *            linearizeOplus, parameter_se3_offset.cpp:44-50 CacheSE3Offset::updateImpl, vertex_pointxyz.h:48-51 oplusImpl)
+ *            with ONE ParameterSE3Offset for the whole set: e = (X offset)^-1 l - z, measurements [n][3], information
+ *            [n][3x3], landmarks (x, y, z), offset an isometry [12] = R (column-major) | t or NULL for the identity (type 4
+ *            only); beside a type-2 pose set only.
+ * Edge set `set` was added with error_dim 2 / 3, vertex 0 = the pose's hessian index, vertex 1 = the landmark's
+ * (num_poses + landmark number), -1 for a fixed vertex on either side.  pose_vertex[k] indexes the pose table of
+ * g2ohip_pg_set_estimates, point_vertex[k] the landmark table of g2ohip_pg_set_landmark_estimates, whose hidx[v] is the
+ * landmark's hessian index in the whole system (>= num_poses) or -1; its update is the plain addition of
+ * x[num_poses * pose_dim + (hidx - num_poses) * landmark_dim ..].
+ * Call after g2ohip_build_structure and after g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise); a wrong pairing of types,
+ * wrong dimensions of the set, indices out of range or hessian indices that differ from the edge set's give G2OHIP_ERR_ARG.
+ * g2ohip_pg_linearize / update / push / pop / discard_top then act on both halves; g2ohip_pg_linearize with landmark edges
+ * bound but no landmark estimates returns G2OHIP_ERR_STATE.  The binding goes wherever the pose binding goes
+ * (g2ohip_clear_edge_sets, growth of a bound set).  Robust kernels of the set: g2ohip_set_robust_kernel(_per_edge) as for
+ * any set.  do_schur = 1 (landmarks marginalised) is the intended configuration; with do_schur = 0 g2ohip_solve solves the
+ * pose block alone (x_p = Hpp^-1 b_p, the landmark part of x stays zero), as for every system with landmarks. */
+int g2ohip_pg_set_landmark_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                 const double* meas, const double* info, const double* offset);
+int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
+int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
+
 /* ---- narrow seam: g2o::LinearSolver<MatrixType> ------------------------------------------- */
 
 /* LinearSolver ctor for MatrixType = block_dim x block_dim. */

@@ -91,6 +91,10 @@ class BlockSolver {
   void pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_estimates(int nv, const double* poses, const int* hidx);
   void pg_get_estimates(double* poses);
+  void pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
+                             const double* offset);
+  void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
+  void pg_get_landmark_estimates(double* points);
   void pg_linearize(bool jacobians);
   void pg_update();
   void pg_push();
@@ -268,6 +272,7 @@ class BlockSolver {
   bool ba_fuse_landmarks = true;      // fused BA path (Hpl not written while nobody reads it, ensure_hpl): the landmark side (Hll, b_l, errors) is
                                       // assembled by the Schur tiles of the solve, which write only b_l and Dinv, what the solve reads
   bool marginals_recursion = true;  // compute_marginals: all entries on the pattern of L in one top-down pass (sparse inverse) instead of one pair of sweeps per column
+  bool pg_landmark_staged = true;   // landmark linearize kernels: results leave through LDS, contiguous per wave (pg_landmark.inc)
   bool marginals_reduced = false;   // compute_marginals: invert the reduced pose system instead of Hpp alone (the reference inverts Hpp)
  private:
   hipStream_t fetch_st_ = nullptr;                         // ba_fetch_begin: the copy stream of the asynchronous estimate read-back
@@ -331,6 +336,7 @@ class BlockSolver {
   bool ll_valid_ = true;   // Hll, b_l and the errors of the fused BA path match the last build_system
   bool ll_hbm_partial_ = false;   // ... but the Schur tiles that assembled them wrote b_l only (Hll and the errors stayed on chip)
   void pg_validate();
+  void pg_validate_landmarks();
   struct BaFrontEnd {
     int set = -1, n_edges = 0, n_cams = 0, n_points = 0;
     double f = 0, cx = 0, cy = 0;
@@ -368,13 +374,29 @@ class BlockSolver {
     bool ll_slots_ok = false;
     bool has_backup = false;
   } ba_;
-  struct PgFrontEnd {   // pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12])
+  // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
+  // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
+  // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)).  Vertex 0 of an observation
+  // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); pt_hidx[v] is the landmark's index in
+  // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
+  // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
+  // Schur on (landmarks marginalised) is the configuration the front end is meant for.  With do_schur = 0 and landmarks in the
+  // structure the solver does what it does for any such system: H and b are assembled in full (Hpp, Hpl, Hll, b_p, b_l), solve()
+  // factorises Hpp ALONE and writes x_p = Hpp^-1 b_p (what BlockSolver hands its linear solver without Schur, and what
+  // OracleSolver(schur=False) computes); the landmark part of x keeps the zeros of build_structure, so pg_update leaves the
+  // landmarks where they are.  The front end adds nothing of its own to that path.
+  struct PgFrontEnd {
     int set = -1, type = 0, nv = 0;
     DevBuf<int> vi, vj, hidx;
     std::vector<int> h_vi, h_vj, h_hidx;
     DevBuf<double> meas, poses, poses_bak;
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
+    int lm_set = -1, lm_type = 0, n_points = 0;
+    DevBuf<int> vp, vl, pt_hidx;
+    std::vector<int> h_vp, h_vl, h_pt_hidx;   // host copies: index validation (pg_validate_landmarks)
+    DevBuf<double> lm_meas, points, points_bak;
+    double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4)
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

@@ -2079,6 +2079,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
   pg_iso_mul(Tl, inc, out);
   for (int i = 0; i < 12; ++i) T[i] = out[i];
 }
+#include "pg_landmark.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -2355,7 +2356,7 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     es.external = false;
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then
-    if (set == pg_.set) pg_ = PgFrontEnd();
+    if (set == pg_.set || set == pg_.lm_set) pg_ = PgFrontEnd();
     if (set == ba_.set) ba_.set = -1;
     // per-edge robust kernels cover the old edge count: the new edges get "none" (kind 0) until set_robust_kernel_per_edge is
     // called again -- the array is extended on the device so that no kernel reads past its end
@@ -3050,7 +3051,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == pg_.set;
+  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5160,6 +5161,35 @@ void BlockSolver::pg_validate() {
   }
 }
 
+// the landmark half: hidx_pose[vp[k]] == v0[k] and hidx_point[vl[k]] == v1[k] of the observation set (whatever of the tables
+// has been handed over so far)
+void BlockSolver::pg_validate_landmarks() {
+  if (pg_.lm_set < 0 || pg_.h_vp.empty()) return;
+  const EdgeSet& es = *sets_[pg_.lm_set];
+  const int nv = (int)pg_.h_hidx.size(), np = (int)pg_.h_pt_hidx.size();
+  for (int v = 0; v < np; ++v) {
+    const int h = pg_.h_pt_hidx[v];
+    if (h != -1 && (h < nP_ || h >= nP_ + nL_)) throw ArgFailure("pg: hessian index of landmark " + std::to_string(v) + " outside the landmark range of the structure");
+  }
+  for (size_t k = 0; k < pg_.h_vp.size(); ++k) {
+    const int a = pg_.h_vp[k], b = pg_.h_vl[k];
+    if (a < 0 || b < 0) throw ArgFailure("pg: negative vertex index in landmark edge " + std::to_string(k));
+    if (nv > 0) {
+      if (a >= nv) throw ArgFailure("pg: pose index of landmark edge " + std::to_string(k) + " outside the estimate table");
+      const int ha = pg_.h_hidx[a];
+      if (ha >= nP_) throw ArgFailure("pg: hessian index of an estimate outside the structure");
+      if (es.v0[k] != (ha < 0 ? -1 : ha))
+        throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the pose's hessian index differs from the edge set's");
+    }
+    if (np > 0) {
+      if (b >= np) throw ArgFailure("pg: landmark index of landmark edge " + std::to_string(k) + " outside the landmark table");
+      const int hb = pg_.h_pt_hidx[b];
+      if (es.v1[k] != (hb < 0 ? -1 : hb))
+        throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the landmark's hessian index differs from the edge set's");
+    }
+  }
+}
+
 void BlockSolver::ba_set_estimates(int n_cams, const double* cams, const int* cam_hidx, int n_points, const double* points,
                                    const int* point_hidx) {
   if (n_cams <= 0 || n_points <= 0 || !cams || !points || !cam_hidx || !point_hidx) throw ArgFailure("ba_set_estimates: bad arguments");
@@ -5412,7 +5442,14 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
   }
   pg_.nv = nv;
   pg_.h_hidx.assign(hidx, hidx + nv);
-  pg_validate();
+  try {
+    pg_validate();
+    pg_validate_landmarks();
+  } catch (...) {   // (no estimate table rather than one the edges do not fit: pg_linearize refuses until a valid one arrives)
+    pg_.nv = 0;
+    pg_.h_hidx.clear();
+    throw;
+  }
   pg_.poses.upload(poses, (size_t)nv * ps, st_);
   pg_.hidx.upload(hidx, (size_t)nv, st_);
   pg_.poses_bak.alloc((size_t)nv * ps);
@@ -5425,13 +5462,105 @@ void BlockSolver::pg_get_estimates(double* poses) {
   pg_.poses.download(poses, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12), st_);
 }
 
+// ---- ... its landmark half (EdgeSE2PointXY / EdgeSE3PointXYZ over VertexPointXY / VertexPointXYZ) -----------------------
+void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                        const double* info, const double* offset) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 3 && type != 4) throw ArgFailure("pg_set_landmark_edges: type must be 3 (EdgeSE2PointXY) or 4 (EdgeSE3PointXYZ)");
+  if (type != pg_.type + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
+  if (set == pg_.set) throw ArgFailure("pg_set_landmark_edges: the set is bound as the pose-pose set");
+  EdgeSet& es = *sets_[set];
+  const int d = type == 3 ? 2 : 3, dp = type == 3 ? 3 : 6;
+  if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != d || p_ != dp || l_ != d)
+    throw ArgFailure("pg_set_landmark_edges: the set must be a binary pose-landmark set with (error, pose, landmark) dimensions (2, 3, 2) or (3, 6, 3)");
+  if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure("pg_set_landmark_edges: null array");
+  if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const size_t n = (size_t)es.n;
+  // (a failed validation must not leave half a binding)
+  const int old_set = pg_.lm_set, old_type = pg_.lm_type;
+  std::vector<int> old_vp = std::move(pg_.h_vp), old_vl = std::move(pg_.h_vl);
+  pg_.lm_set = set;
+  pg_.lm_type = type;
+  pg_.h_vp.assign(pose_vertex, pose_vertex + n);
+  pg_.h_vl.assign(point_vertex, point_vertex + n);
+  try {
+    pg_validate_landmarks();
+  } catch (...) {
+    pg_.lm_set = old_set;
+    pg_.lm_type = old_type;
+    pg_.h_vp = std::move(old_vp);
+    pg_.h_vl = std::move(old_vl);
+    throw;
+  }
+  for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
+  pg_.vp.upload(pose_vertex, n, st_);
+  pg_.vl.upload(point_vertex, n, st_);
+  pg_.lm_meas.upload(meas, n * d, st_);
+  es.own_omega.upload(info, n * d * d, st_);
+  es.own_J0.alloc(n * d * dp);
+  es.own_J1.alloc(n * d * d);
+  es.own_err.alloc(n * d);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void BlockSolver::pg_set_landmark_estimates(int n_points, const double* points, const int* hidx) {
+  require_structure();
+  if (pg_.type == 0) throw StateFailure("pg_set_landmark_estimates: call pg_set_edges first");
+  if (n_points <= 0 || !points || !hidx) throw ArgFailure("pg_set_landmark_estimates: bad arguments");
+  const size_t l = pg_.type == 1 ? 2 : 3;
+  if ((int)l != l_) throw ArgFailure("pg_set_landmark_estimates: the solver's landmark dimension does not fit the pose set's type");
+  pg_.err_valid = pg_.jac_valid = false;
+  chi2_valid_ = false;
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  if (n_points == pg_.n_points && pg_.points.p && (int)pg_.h_pt_hidx.size() == n_points &&
+      std::memcmp(pg_.h_pt_hidx.data(), hidx, sizeof(int) * (size_t)n_points) == 0) {
+    pg_.has_backup = false;   // (same tables, new values: see pg_set_estimates)
+    pg_.points.upload(points, (size_t)n_points * l, st_);
+    G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+    return;
+  }
+  std::vector<int> old = std::move(pg_.h_pt_hidx);
+  pg_.h_pt_hidx.assign(hidx, hidx + n_points);
+  try {
+    pg_validate_landmarks();
+  } catch (...) {
+    pg_.h_pt_hidx = std::move(old);
+    throw;
+  }
+  invalidate_graphs();
+  pg_.n_points = n_points;
+  pg_.points.upload(points, (size_t)n_points * l, st_);
+  pg_.pt_hidx.upload(hidx, (size_t)n_points, st_);
+  pg_.points_bak.alloc((size_t)n_points * l);
+  pg_.has_backup = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void BlockSolver::pg_get_landmark_estimates(double* points) {
+  if (pg_.n_points <= 0) throw StateFailure("pg_get_landmark_estimates before pg_set_landmark_estimates");
+  pg_.points.download(points, (size_t)pg_.n_points * (pg_.type == 1 ? 2 : 3), st_);
+}
+
 void BlockSolver::pg_linearize(bool jacobians) {
   if (pg_.set < 0 || pg_.nv <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   EdgeSet& es = *sets_[pg_.set];
   if ((int)pg_.h_vi.size() != es.n) throw StateFailure("pg_linearize: the edge set has grown since pg_set_edges (g2ohip_update_structure): call pg_set_edges again");
+  EdgeSet* el = pg_.lm_set >= 0 ? sets_[pg_.lm_set].get() : nullptr;
+  if (el) {
+    if (pg_.n_points <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
+    if ((int)pg_.h_vp.size() != el->n) throw StateFailure("pg_linearize: the landmark edge set has changed since pg_set_landmark_edges: call it again");
+  }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     if (jacobians) es.has_data = true;
+    if (jacobians && el) el->has_data = true;
     return;
   }
   pg_.err_valid = true;
@@ -5443,9 +5572,36 @@ void BlockSolver::pg_linearize(bool jacobians) {
   else
     hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
+  if (el && el->n > 0) {
+    prof.begin(KernelProf::kPgLandmark, st_);
+    const dim3 grid(grid_for(el->n)), block(kThreads);
+    const int jac = jacobians ? 1 : 0;
+    if (pg_.lm_type == 3) {
+      if (pg_landmark_staged)
+        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<true>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
+                           pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+      else
+        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<false>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
+                           pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+    } else {
+      PgIso off;
+      for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
+      if (pg_landmark_staged)
+        hipLaunchKernelGGL(pg_se3_pointxyz_linearize_kernel<true>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
+                           pg_.lm_meas.p, off, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+      else
+        hipLaunchKernelGGL(pg_se3_pointxyz_linearize_kernel<false>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
+                           pg_.lm_meas.p, off, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+    }
+    prof.end(KernelProf::kPgLandmark, st_);
+  }
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
+  if (el) {
+    el->has_err = true;
+    if (jacobians) el->has_data = true;
+  }
 }
 
 void BlockSolver::pg_update() {
@@ -5457,6 +5613,11 @@ void BlockSolver::pg_update() {
     hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.nv)), dim3(kThreads), 0, st_, pg_.nv, pg_.poses.p, pg_.hidx.p, d_x.p);
   else
     hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.nv)), dim3(kThreads), 0, st_, pg_.nv, pg_.poses.p, pg_.hidx.p, d_x.p);
+  if (pg_.n_points > 0) {
+    const size_t ns = (size_t)pg_.n_points * l_;
+    hipLaunchKernelGGL(pg_points_update_kernel, dim3(grid_for(ns)), dim3(kThreads), 0, st_, ns, l_, pg_.points.p, pg_.pt_hidx.p, d_x.p,
+                       (size_t)nP_ * p_, nP_);
+  }
   G2OHIP_HIP_CHECK(hipGetLastError());
 }
 
@@ -5465,6 +5626,8 @@ void BlockSolver::pg_push() {
   if (pg_.has_backup) throw StateFailure("pg_push: the estimate stack holds one level");
   G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.poses_bak.p, pg_.poses.p, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12) * sizeof(double),
                                   hipMemcpyDeviceToDevice, st_));
+  if (pg_.n_points > 0)
+    G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.points_bak.p, pg_.points.p, (size_t)pg_.n_points * l_ * sizeof(double), hipMemcpyDeviceToDevice, st_));
   pg_.has_backup = true;
 }
 void BlockSolver::pg_pop() {
@@ -5472,6 +5635,8 @@ void BlockSolver::pg_pop() {
   pg_.err_valid = pg_.jac_valid = false;
   G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.poses.p, pg_.poses_bak.p, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12) * sizeof(double),
                                   hipMemcpyDeviceToDevice, st_));
+  if (pg_.n_points > 0)
+    G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.points.p, pg_.points_bak.p, (size_t)pg_.n_points * l_ * sizeof(double), hipMemcpyDeviceToDevice, st_));
   pg_.has_backup = false;
 }
 void BlockSolver::pg_discard_top() {

@@ -566,6 +566,10 @@ int g2ohip_set_option(g2ohip_solver* s, const char* name, double value) {
   else if (!std::strcmp(name, "pcg_check_every")) s->impl->pcg_opt.check_every = std::max(1, (int)value);
   else if (!std::strcmp(name, "fuse_schur_reduce")) s->impl->fuse_schur_reduce = value != 0;
   else if (!std::strcmp(name, "marginals_reduced")) s->impl->marginals_reduced = value != 0;
+  else if (!std::strcmp(name, "pg_landmark_staged")) {
+    s->impl->pg_landmark_staged = value != 0;
+    s->impl->invalidate_graphs();   // (the next pg_linearize evaluates again, in the chosen form)
+  }
   else if (!std::strcmp(name, "marginals_recursion")) s->impl->marginals_recursion = value != 0;
   else if (!std::strcmp(name, "use_graph")) s->impl->use_graph = value != 0;
   else if (!std::strcmp(name, "sharded_graph")) s->impl->sharded_graph = (int)value;
@@ -835,6 +839,29 @@ G2OHIP_PG_SIMPLE(g2ohip_pg_push, pg_push)
 G2OHIP_PG_SIMPLE(g2ohip_pg_pop, pg_pop)
 G2OHIP_PG_SIMPLE(g2ohip_pg_discard_top, pg_discard_top)
 #undef G2OHIP_PG_SIMPLE
+int g2ohip_pg_set_landmark_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                 const double* meas, const double* info, const double* offset) {
+  REQUIRE_HANDLE(s);
+  return guarded([&] {
+    s->impl->pg_set_landmark_edges(set, type, pose_vertex, point_vertex, meas, info, offset);
+    return G2OHIP_OK;
+  });
+}
+int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx) {
+  REQUIRE_HANDLE(s);
+  return guarded([&] {
+    s->impl->pg_set_landmark_estimates(n_points, points, hidx);
+    return G2OHIP_OK;
+  });
+}
+int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points) {
+  REQUIRE_HANDLE(s);
+  if (!points) return G2OHIP_ERR_ARG;
+  return guarded([&] {
+    s->impl->pg_get_landmark_estimates(points);
+    return G2OHIP_OK;
+  });
+}
 
 // ---- narrow seam ---------------------------------------------------------------------
 int g2ohip_ls_create(g2ohip_linear_solver** out, int block_dim, int device) {

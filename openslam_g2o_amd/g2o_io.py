@@ -4,6 +4,9 @@ Mirrors what OptimizableGraph::load (g2o/core/optimizable_graph.cpp:356-480) doe
 `VERTEX_SE2` / `EDGE_SE2` (g2o/types/slam2d/{vertex_se2,edge_se2}.cpp read()) and
 `VERTEX_SE3:QUAT` / `EDGE_SE3:QUAT` (g2o/types/slam3d/{vertex_se3,edge_se3}.cpp read()):
 the information matrix is given as its upper triangle, row-major (edge_se2.cpp:46-51).
+Landmark SLAM files add `VERTEX_XY` / `EDGE_SE2_XY` (g2o/types/slam2d/{vertex_point_xy,edge_se2_pointxy}.cpp read()) and
+`VERTEX_TRACKXYZ` / `EDGE_SE3_TRACKXYZ` / `PARAMS_SE3OFFSET` (g2o/types/slam3d/{vertex_pointxyz,edge_se3_pointxyz,
+parameter_se3_offset}.cpp read()).
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -20,8 +23,13 @@ def _upper_to_full(vals, d):
 
 
 def read_g2o(path):
-    """Returns dict(kind='se2'|'se3', ids, estimates, edges=(vi, vj), meas, info, fixed)."""
+    """Returns dict(kind='se2'|'se3', ids, estimates, edges=(vi, vj), meas, info, fixed).
+    A file with point landmarks (VERTEX_XY / EDGE_SE2_XY, VERTEX_TRACKXYZ / EDGE_SE3_TRACKXYZ, PARAMS_SE3OFFSET) gives the same
+    keys for its poses and pose-pose edges plus: point_ids, points [L][2|3] (sorted by id), lm_vp / lm_vl (pose-table and
+    point-table index of every observation), lm_meas, lm_info [M][d][d], lm_param (offset parameter id per observation, 3-D),
+    offsets {id: (x y z qx qy qz qw), quaternion normalised as ParameterSE3Offset::read does}, fixed_points."""
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
+    pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     kind = None
     with open(path) as f:
         for line in f:
@@ -47,6 +55,27 @@ def read_g2o(path):
                 ej.append(int(t[2]))
                 meas.append([float(x) for x in t[3:10]])
                 info.append(_upper_to_full([float(x) for x in t[10:31]], 6))
+            elif tag == "VERTEX_XY":
+                pid.append(int(t[1]))
+                pest.append([float(x) for x in t[2:4]])
+            elif tag == "EDGE_SE2_XY":
+                lp.append(int(t[1]))
+                ll.append(int(t[2]))
+                lmeas.append([float(x) for x in t[3:5]])
+                linfo.append(_upper_to_full([float(x) for x in t[5:8]], 2))
+            elif tag == "VERTEX_TRACKXYZ":
+                pid.append(int(t[1]))
+                pest.append([float(x) for x in t[2:5]])
+            elif tag == "EDGE_SE3_TRACKXYZ":
+                lp.append(int(t[1]))
+                ll.append(int(t[2]))
+                lparam.append(int(t[3]))
+                lmeas.append([float(x) for x in t[4:7]])
+                linfo.append(_upper_to_full([float(x) for x in t[7:13]], 3))
+            elif tag == "PARAMS_SE3OFFSET":
+                o = np.asarray([float(x) for x in t[2:9]])
+                o[3:] /= np.linalg.norm(o[3:])
+                offsets[int(t[1])] = o
             elif tag == "FIX":
                 fixed.extend(int(x) for x in t[1:])
     vid = np.asarray(vid, np.int64)
@@ -56,8 +85,18 @@ def read_g2o(path):
     lut = {int(v): k for k, v in enumerate(vid)}
     vi = np.asarray([lut[a] for a in ei], np.int32)
     vj = np.asarray([lut[a] for a in ej], np.int32)
-    return dict(kind=kind, ids=vid, estimates=vest, vi=vi, vj=vj, meas=np.asarray(meas, np.float64),
-                info=np.asarray(info, np.float64), fixed=[lut[f] for f in fixed if f in lut])
+    out = dict(kind=kind, ids=vid, estimates=vest, vi=vi, vj=vj, meas=np.asarray(meas, np.float64),
+               info=np.asarray(info, np.float64), fixed=[lut[f] for f in fixed if f in lut])
+    if pid or lp or offsets:
+        pid = np.asarray(pid, np.int64)
+        po = np.argsort(pid, kind="stable")
+        pid = pid[po]
+        plut = {int(v): k for k, v in enumerate(pid)}
+        out.update(point_ids=pid, points=np.asarray(pest, np.float64)[po],
+                   lm_vp=np.asarray([lut[a] for a in lp], np.int32), lm_vl=np.asarray([plut[a] for a in ll], np.int32),
+                   lm_meas=np.asarray(lmeas, np.float64), lm_info=np.asarray(linfo, np.float64),
+                   lm_param=np.asarray(lparam, np.int32), offsets=offsets, fixed_points=[plut[f] for f in fixed if f in plut])
+    return out
 
 
 def hessian_index(n_vertices, fixed):
@@ -70,6 +109,94 @@ def hessian_index(n_vertices, fixed):
             h[v] = k
             k += 1
     return h, k
+
+
+def landmark_hessian_index(n_poses, n_points, fixed_poses=(), fixed_points=()):
+    """buildIndexMapping (sparse_optimizer.cpp:174-187) for poses + marginalised point landmarks: free poses by id, then the
+    free landmarks by id.  Returns (pose hidx, point hidx, number of free poses, number of free landmarks); fixed -> -1."""
+    h, nP = hessian_index(n_poses, fixed_poses)
+    hl, nL = hessian_index(n_points, fixed_points)
+    hl = np.where(hl >= 0, hl + nP, -1).astype(np.int32)
+    return h, hl, nP, nL
+
+
+def _iso_from_qt(qt):
+    """[n][7] (x y z qx qy qz qw, unit quaternion) -> [n][12] isometries (R column-major | t)."""
+    qt = np.asarray(qt, np.float64).reshape(-1, 7)
+    return np.concatenate([_quat_to_R(qt[:, 3:7]).transpose(0, 2, 1).reshape(-1, 9), qt[:, 0:3]], axis=1)
+
+
+def landmark_problem(rd, fixed_poses=None, fixed_points=None):
+    """read_g2o() result of a landmark SLAM file -> the problem dict of openslam_g2o_amd.synthetic.make_landmark_slam (what
+    lm.setup_device_landmark_slam takes).  fixed_*: indices into the pose / point tables (default: the file's FIX lines; a file
+    without any gets pose 0 fixed as the gauge).  All 3-D observations must name the same PARAMS_SE3OFFSET."""
+    if "points" not in rd:
+        raise ValueError("the file has no point landmarks")
+    se2 = rd["kind"] == "se2"
+    fp = list(rd["fixed"]) if fixed_poses is None else list(fixed_poses)
+    fl = list(rd["fixed_points"]) if fixed_points is None else list(fixed_points)
+    if fixed_poses is None and not fp:
+        fp = [0]
+    n, L = len(rd["estimates"]), len(rd["points"])
+    hidx, pt_hidx, nP, nL = landmark_hessian_index(n, L, fp, fl)
+    dp, dl = (3, 2) if se2 else (6, 3)
+    offset = None
+    if se2:
+        poses, Z = rd["estimates"].copy(), rd["meas"].copy()
+    else:
+        def unit(qt):
+            qt = np.asarray(qt, np.float64).reshape(-1, 7).copy()
+            qt[:, 3:] /= np.linalg.norm(qt[:, 3:], axis=1)[:, None]
+            return qt
+        poses, Z = _iso_from_qt(unit(rd["estimates"])), _iso_from_qt(unit(rd["meas"]))
+        ids = set(int(v) for v in rd["lm_param"])
+        if len(ids) > 1:
+            raise ValueError("observations with different PARAMS_SE3OFFSET are not one set")
+        if ids:
+            offset = _iso_from_qt(rd["offsets"][ids.pop()])[0]
+    E, M = len(rd["vi"]), len(rd["lm_vp"])
+    return dict(kind=rd["kind"], n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=rd["vi"], vj=rd["vj"], Z=Z,
+                omega=np.asarray(rd["info"]).transpose(0, 2, 1).reshape(E, dp * dp).copy(), vp=rd["lm_vp"], vl=rd["lm_vl"],
+                zl=rd["lm_meas"], omega_l=np.asarray(rd["lm_info"]).transpose(0, 2, 1).reshape(M, dl * dl).copy(), offset=offset,
+                poses=poses, points=rd["points"].copy(), hidx=hidx, pt_hidx=pt_hidx)
+
+
+def write_g2o_landmarks(path, prob):
+    """make_landmark_slam-style problem -> `.g2o` text with the reference's tags (poses get the ids 0..n-1, landmarks
+    n..n+L-1, the sensor offset parameter id 0); fixed vertices (hessian index -1) go into a FIX line."""
+    se2 = prob["kind"] == "se2"
+    n = len(prob["poses"])
+    fmt = lambda v: " ".join("%.17g" % x for x in v)
+    upper = lambda Mx, d: fmt(Mx.reshape(d, d)[i, j] for i in range(d) for j in range(i, d))
+
+    def qt(T):
+        T = np.asarray(T, np.float64).reshape(-1, 12)
+        return np.concatenate([T[:, 9:12], _R_to_quat(T[:, 0:9].reshape(-1, 3, 3).transpose(0, 2, 1))], axis=1)
+    with open(path, "w") as f:
+        if se2:
+            for i in range(n):
+                f.write("VERTEX_SE2 %d %s\n" % (i, fmt(prob["poses"][i])))
+            for j, pt in enumerate(prob["points"]):
+                f.write("VERTEX_XY %d %s\n" % (n + j, fmt(pt)))
+        else:
+            off = prob.get("offset")
+            off = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]) if off is None else off
+            f.write("PARAMS_SE3OFFSET 0 %s\n" % fmt(qt(off)[0]))
+            for i, v in enumerate(qt(prob["poses"])):
+                f.write("VERTEX_SE3:QUAT %d %s\n" % (i, fmt(v)))
+            for j, pt in enumerate(prob["points"]):
+                f.write("VERTEX_TRACKXYZ %d %s\n" % (n + j, fmt(pt)))
+        fixed = [i for i in range(n) if prob["hidx"][i] < 0] + [n + j for j in range(len(prob["points"])) if prob["pt_hidx"][j] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(i) for i in fixed))
+        dp, dl = (3, 2) if se2 else (6, 3)
+        Zq = prob["Z"] if se2 else qt(prob["Z"])
+        for e in range(len(prob["vi"])):
+            f.write("%s %d %d %s %s\n" % ("EDGE_SE2" if se2 else "EDGE_SE3:QUAT", prob["vi"][e], prob["vj"][e], fmt(Zq[e]),
+                                          upper(np.asarray(prob["omega"][e]), dp)))
+        for e in range(len(prob["vp"])):
+            f.write("%s %d %d %s%s %s\n" % ("EDGE_SE2_XY" if se2 else "EDGE_SE3_TRACKXYZ", prob["vp"][e], n + prob["vl"][e],
+                                            "" if se2 else "0 ", fmt(prob["zl"][e]), upper(np.asarray(prob["omega_l"][e]), dl)))
 
 
 # ---- bundle-adjustment tags (SURVEY.md 8f.2) --------------------------------------------------------------

@@ -305,7 +305,8 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
 
 
 class DevicePoseGraph:
-    """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3)."""
+    """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3, and the
+    landmark observations bound beside them: setup_device_landmark_slam)."""
 
     device_resident = True
 
@@ -348,4 +349,31 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
     s.pgSetEstimates(estimates, hidx)
+    return s, DevicePoseGraph(s)
+
+
+def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, options=None):
+    """HipBlockSolver for an openslam_g2o_amd.synthetic.make_landmark_slam (or g2o_io.landmark_problem) graph: odometry edges
+    between poses (EdgeSE2 / EdgeSE3) plus observations of point landmarks (EdgeSE2PointXY / EdgeSE3PointXYZ), pose and
+    landmark estimates, errors and Jacobians on the device; BlockSolver_3_2 / BlockSolver_6_3 semantics, landmarks
+    marginalised (schur=True).  huber_delta > 0: Huber kernel on the observation set.  Returns (solver, DevicePoseGraph);
+    solver.landmark_sets = (odometry set id, observation set id)."""
+    import numpy as np
+    from . import capi
+    se2 = prob["kind"] == "se2"
+    p, l = (3, 2) if se2 else (6, 3)
+    s = capi.HipBlockSolver(p, l, device)
+    for name, value in (options or {}).items():
+        s.setOption(name, value)
+    hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
+    k0 = s.addEdgeSet(p, hidx[prob["vi"]], hidx[prob["vj"]])
+    k1 = s.addEdgeSet(l, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    s.buildStructure(prob["nP"], prob["nL"], schur)
+    s.pgSetEdges(k0, 1 if se2 else 2, prob["vi"], prob["vj"], prob["Z"], prob["omega"])
+    s.pgSetEstimates(prob["poses"], hidx)
+    s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
+    s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
+    if huber_delta > 0:
+        s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    s.landmark_sets = (k0, k1)
     return s, DevicePoseGraph(s)

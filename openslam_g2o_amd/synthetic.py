@@ -367,3 +367,123 @@ def make_sphere(nodes_per_level=50, laps=50, radius=100.0, noise_translation=0.0
     hidx = np.arange(n, dtype=np.int32) - 1                      # vertex 0 fixed
     return dict(n=n, nP=n - 1, E=E, vi=vi, vj=vj, poses=_iso_pack(Re, te), poses_true=_iso_pack(R, t), Z=_iso_pack(Rm, tm),
                 omega=np.tile(info.T.reshape(1, 36), (E, 1)), hidx=hidx)
+
+
+def _wrap(theta):
+    """normalize_theta (g2o/stuff/misc.h): into [-pi, pi)."""
+    return (np.asarray(theta) + np.pi) % (2.0 * np.pi) - np.pi
+
+
+def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, window=2, max_obs=None, seed=42,
+                       noise_odometry=(0.02, 0.01), noise_landmark=0.05, outlier_frac=0.0, perturb=(0.1, 0.02, 0.2),
+                       closure_stride=5, fixed_landmarks=0):
+    """Landmark SLAM graph: odometry between poses plus point landmarks observed from them.
+    kind "se2": VertexSE2 / VertexPointXY with EdgeSE2 + EdgeSE2PointXY; "se3": VertexSE3 / VertexPointXYZ with EdgeSE3 +
+    EdgeSE3PointXYZ and one non-identity sensor offset (ParameterSE3Offset).
+    The robot drives `laps` times round the same loop (radius chosen for a step of ~1 between poses; in 3-D the loop also
+    rises and falls), so every place is revisited.  Edges: odometry between successive poses and a loop closure to the pose
+    one lap earlier every `closure_stride` poses.  Landmark j sits within half the sensor range of the pose c_j = floor(j *
+    per_lap / n_landmarks) and is observed from the poses c_j - window .. c_j + window of EVERY lap that are within
+    `sensor_range` of it (at least from the nearest of them), at most `max_obs` of them.  Measurements carry Gaussian noise
+    (noise_odometry = (translation, rotation) sigma, noise_landmark sigma; the information matrices match), a fraction
+    `outlier_frac` of the observations gets a gross error on top; the initial estimates are the ground truth perturbed
+    by N(0, perturb = (pose translation, pose rotation, landmark)).  Pose 0 is fixed (gauge) and the first `fixed_landmarks`
+    landmarks.  Counter-based RNG: the same seed gives the same graph anywhere.  Ground truth: poses_true, points_true.
+    Layout: SE2 poses (x, y, theta), SE3 poses / measurements isometries [12]; hidx / pt_hidx hessian indices (landmarks
+    behind the poses: nP + number among the free landmarks; -1 fixed)."""
+    if kind not in ("se2", "se3"):
+        raise ValueError("kind must be 'se2' or 'se3'")
+    se2 = kind == "se2"
+    rng = CounterRng(seed)
+    n, L = int(n_poses), int(n_landmarks)
+    per_lap = max(4, n // laps)
+    radius = per_lap / (2.0 * np.pi)
+    k = np.arange(n)
+    ang = 2.0 * np.pi * (k % per_lap) / per_lap
+    lap = k // per_lap
+    wob = 0.15 * np.sin(3.0 * ang + 0.7 * lap)                      # laps differ a little: revisits are near, not identical
+    px, py = (radius + wob) * np.cos(ang), (radius + wob) * np.sin(ang)
+    yaw = ang + 0.5 * np.pi
+    dl = 2 if se2 else 3
+    if se2:
+        pos = np.stack([px, py], axis=1)
+        poses_true = np.stack([px, py, _wrap(yaw)], axis=1)
+    else:
+        pz = 0.1 * radius * np.sin(2.0 * ang) + 0.05 * lap
+        pos = np.stack([px, py, pz], axis=1)
+        R = _exp_so3(np.stack([0.05 * np.sin(ang), 0.05 * np.cos(2 * ang), yaw], axis=1))[0]
+        poses_true = _iso_pack(R, pos)
+    # landmarks around their anchor pose (first lap)
+    anchor = np.minimum((np.arange(L) * per_lap) // max(L, 1), per_lap - 1)
+    off = np.stack([rng.uniform(200 + c, L) for c in range(dl)], axis=1) * 2.0 - 1.0
+    points_true = pos[anchor] + off * (0.5 * sensor_range / np.sqrt(dl))
+    # candidate observers: the window round the anchor in every lap
+    n_laps = (n + per_lap - 1) // per_lap
+    dw = np.arange(-window, window + 1)
+    cand = (anchor[:, None, None] + dw[None, None, :]) % per_lap + per_lap * np.arange(n_laps)[None, :, None]
+    cand = cand.reshape(L, -1)
+    dist = np.linalg.norm(pos[np.minimum(cand, n - 1)] - points_true[:, None, :], axis=2)
+    dist = np.where(cand < n, dist, np.inf)
+    seen = dist <= sensor_range
+    seen[np.arange(L), np.argmin(dist, axis=1)] = True              # every landmark is observed at least once
+    if max_obs is not None:
+        seen &= np.cumsum(seen, axis=1) <= max_obs
+    lm_i, slot = np.nonzero(seen)
+    vp = cand[lm_i, slot].astype(np.int32)
+    vl = lm_i.astype(np.int32)
+    order = np.lexsort((vl, vp))                                    # observations in the order the robot makes them
+    vp, vl = vp[order], vl[order]
+    M = len(vp)
+    # odometry + loop closures
+    a = [np.arange(n - 1)]
+    b = [np.arange(1, n)]
+    if n > per_lap:
+        c = np.arange(per_lap, n, max(1, closure_stride))
+        a.append(c - per_lap)
+        b.append(c)
+    vi, vj = np.concatenate(a).astype(np.int32), np.concatenate(b).astype(np.int32)
+    E = len(vi)
+    st, sr = noise_odometry
+    if se2:
+        c, s = np.cos(poses_true[vi, 2]), np.sin(poses_true[vi, 2])
+        d = poses_true[vj, :2] - poses_true[vi, :2]
+        Z = np.stack([c * d[:, 0] + s * d[:, 1] + st * rng.normal(210, E), -s * d[:, 0] + c * d[:, 1] + st * rng.normal(211, E),
+                      _wrap(poses_true[vj, 2] - poses_true[vi, 2] + sr * rng.normal(212, E))], axis=1)
+        info = np.diag([1 / st ** 2, 1 / st ** 2, 1 / sr ** 2])
+        c, s = np.cos(poses_true[vp, 2]), np.sin(poses_true[vp, 2])
+        d = points_true[vl] - poses_true[vp, :2]
+        zl = np.stack([c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1]], axis=1)
+        offset = None
+        poses = poses_true + np.stack([perturb[0] * rng.normal(220, n), perturb[0] * rng.normal(221, n), perturb[1] * rng.normal(222, n)], axis=1)
+        poses[:, 2] = _wrap(poses[:, 2])
+    else:
+        Rt = R.transpose(0, 2, 1)
+        Rm = Rt[vi] @ R[vj] @ _exp_so3(np.stack([rng.normal(213 + q, E) for q in range(3)], axis=1) * sr)[0]
+        tm = np.einsum("nij,nj->ni", Rt[vi], pos[vj] - pos[vi]) + st * np.stack([rng.normal(210 + q, E) for q in range(3)], axis=1)
+        Z = _iso_pack(Rm, tm)
+        info = np.zeros((6, 6))
+        info[:3, :3] = np.eye(3) / st ** 2
+        info[3:, 3:] = np.eye(3) / (0.5 * sr) ** 2                  # (the error's rotation part is the quaternion vector: half the angle)
+        Ro = _exp_so3(np.array([[0.1, -0.2, 0.3]]))[0][0]           # the sensor is mounted off-centre and rotated
+        to = np.array([0.2, -0.1, 0.3])
+        offset = _iso_pack(Ro[None], to[None])[0]
+        Rn = R[vp] @ Ro                                             # n2w = X * offset
+        tn = np.einsum("nij,j->ni", R[vp], to) + pos[vp]
+        zl = np.einsum("nji,nj->ni", Rn, points_true[vl] - tn)
+        Rp = R @ _exp_so3(np.stack([rng.normal(223 + q, n) for q in range(3)], axis=1) * perturb[1])[0]
+        poses = _iso_pack(Rp, pos + perturb[0] * np.stack([rng.normal(220 + q, n) for q in range(3)], axis=1))
+    poses[0] = poses_true[0]
+    zl = zl + noise_landmark * np.stack([rng.normal(230 + q, M) for q in range(dl)], axis=1)
+    if outlier_frac > 0:
+        bad = rng.uniform(240, M) < outlier_frac
+        zl = zl + bad[:, None] * sensor_range * (np.stack([rng.uniform(241 + q, M) for q in range(dl)], axis=1) * 2.0 - 1.0)
+    points = points_true + perturb[2] * np.stack([rng.normal(250 + q, L) for q in range(dl)], axis=1)
+    points[:fixed_landmarks] = points_true[:fixed_landmarks]
+    hidx = np.arange(n, dtype=np.int32) - 1                         # pose 0 fixed
+    nP, nL = n - 1, L - int(fixed_landmarks)
+    pt_hidx = np.where(np.arange(L) < fixed_landmarks, -1, nP + np.arange(L) - int(fixed_landmarks)).astype(np.int32)
+    dp = 3 if se2 else 6
+    return dict(kind=kind, n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=vi, vj=vj, Z=Z, omega=np.tile(info.T.reshape(1, dp * dp), (E, 1)),
+                vp=vp, vl=vl, zl=zl, omega_l=np.tile((np.eye(dl) / noise_landmark ** 2).reshape(1, dl * dl), (M, 1)),
+                offset=offset, poses=poses, poses_true=poses_true, points=points, points_true=points_true, hidx=hidx,
+                pt_hidx=pt_hidx)

@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""Landmark SLAM (odometry + point landmarks, openslam_g2o_amd.synthetic.make_landmark_slam), 2-D and 3-D:
+
+  default   ms per Levenberg-Marquardt iteration on a large generated graph (a) with the device front end
+            (g2ohip_pg_set_landmark_edges: estimates, errors and Jacobians stay on the device) and (b) with the same library
+            fed host arrays from the vectorised NumPy producers through setEdgeData every iteration (estimates, oplus,
+            push / pop on the host) -- warm-up, then --reps repetitions of --iterations iterations each, median and
+            min / max; then the two landmark linearize kernels alone (HIP events of the library's kernel slot
+            "pg_landmark_linearize"), both store forms, with their algorithmic bytes / time.
+  --drift   CPU only: how far two equally valid oracle runs of the test graphs drift apart per LM iteration (the oracle's
+            Schur path against the full system solved without elimination) -- the bound of
+            tests/test_gpu_landmark_slam.py::test_lm_run_matches_oracle is ten times this.
+
+One JSON line per result on stdout, appended to --out if given.
+  python tools/landmark_slam_time.py [--drift] [--poses 20000 --landmarks 100000 --max-obs 10] [--iterations 5 --reps 5] [--out f]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from openslam_g2o_amd import lm, synthetic as S
+from tests import landmark_helpers as LH
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--drift", action="store_true")
+ap.add_argument("--poses", type=int, default=20000)
+ap.add_argument("--landmarks", type=int, default=100000)
+ap.add_argument("--max-obs", type=int, default=10)
+ap.add_argument("--iterations", type=int, default=5)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--kernel-reps", type=int, default=20)
+ap.add_argument("--kinds", default="se2,se3")
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+HBM_PEAK = 8.0e12      # bytes / s, MI355X data sheet
+
+
+def emit(d):
+    line = json.dumps(d)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+if args.drift:
+    for kind, (n, L) in LH.LM_CASES.items():
+        g = LH.lm_test_graph(kind)
+        a = LH.oracle_lm_run(g, 10, dense=False)
+        b = LH.oracle_lm_run(g, 10, dense=True)
+        emit({"what": "oracle_drift", "kind": kind, "poses": n, "landmarks": L, "observations": int(g["M"]),
+              "relative_chi2_gap": [abs(x - y) / y for x, y in zip(a[1], b[1])], "chi2_schur": a[1], "trials_schur": a[3],
+              "trials_full_system": b[3]})
+    sys.exit(0)
+
+from openslam_g2o_amd import capi
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "n": len(v)}
+
+
+for kind in args.kinds.split(","):
+    g = S.make_landmark_slam(kind, args.poses, args.landmarks, max_obs=args.max_obs)
+    dp, dl = LH.dims(g)
+    size = {"kind": kind, "poses": g["n"], "landmarks": g["L"], "odometry_edges": int(g["E"]), "observations": int(g["M"])}
+    # (a) device front end
+    s, graph = lm.setup_device_landmark_slam(g, options={"use_graph": 1})
+
+    def reset_device():
+        s.pgSetEstimates(g["poses"], g["hidx"])
+        s.pgSetLandmarkEstimates(g["points"], g["pt_hidx"])
+    lm.optimize(graph, s, 3, "lm")                      # warm-up: lazy analysis, graph capture
+    ms_a, traj_a = [], None
+    for r in range(args.reps):
+        reset_device()
+        s.sync()
+        t0 = time.perf_counter()
+        done, chis, lams, trials = lm.optimize(graph, s, args.iterations, "lm")
+        s.sync()
+        ms_a.append(1e3 * (time.perf_counter() - t0) / max(1, done))
+        traj_a = (chis, trials)
+    emit(dict(size, what="lm_iteration", path="device_front_end", ms_per_lm_iteration=spread(ms_a), lm_trials=traj_a[1],
+              chi2=traj_a[0]))
+    # the two landmark kernels alone
+    s.setProfiling(1)
+    pose_doubles = 3 if kind == "se2" else 12
+    table_bytes = 8 * (g["n"] * pose_doubles + g["L"] * dl)
+    for staged in (1, 0):
+        s.setOption("pg_landmark_staged", staged)
+        for jac in (True, False):
+            s.pgLinearize(jac)
+            s.sync()
+            s.kernelTimes(reset=True)
+            for r in range(args.kernel_reps):
+                s.pgSetLandmarkEstimates(g["points"], g["pt_hidx"])      # (same tables: only invalidates the evaluation)
+                s.pgLinearize(jac)
+            s.sync()
+            t, n = s.kernelTimes(reset=True).get("pg_landmark_linearize", (0.0, 0))
+            out_doubles = dl + (dl * dp + dl * dl if jac else 0)
+            nbytes = g["M"] * (8 + 8 * dl + 8 * out_doubles) + table_bytes
+            us = 1e6 * t / max(1, n)
+            emit(dict(size, what="landmark_linearize_kernel", staged=staged, jacobians=bool(jac), launches=int(n), us_per_launch=us,
+                      algorithmic_bytes=int(nbytes), bytes_per_second=nbytes / (1e-6 * us) if us > 0 else 0.0,
+                      fraction_of_hbm_peak=(nbytes / (1e-6 * us) / HBM_PEAK) if us > 0 else 0.0))
+    s.setProfiling(0)
+    s.setOption("pg_landmark_staged", 1)
+    del s, graph
+    # (b) the same library fed from the host
+    p, l = dp, dl
+    h = capi.HipBlockSolver(p, l, 0)
+    h.setOption("use_graph", 1)
+    (a0, a1), (b0, b1) = LH.edge_set_indices(g)
+    k0 = h.addEdgeSet(p, a0, a1)
+    k1 = h.addEdgeSet(l, b0, b1)
+    h.buildStructure(g["nP"], g["nL"], True)
+
+    def feed_err(k, err):
+        err = np.ascontiguousarray(err)
+        capi._check(h.L.g2ohip_set_edge_errors(h.h, k, capi._dp(err)), "setEdgeErrors")
+    host = LH.HostLandmarkGraph(g, lambda k, J0, J1, om, err: h.setEdgeData(k, J0, J1, om, err), h.x, h.chi2, feed_err)
+    lm.optimize(host, h, 2, "lm")
+    ms_b, traj_b = [], None
+    for r in range(max(2, args.reps // 2)):
+        host.pr["poses"], host.pr["points"] = g["poses"].copy(), g["points"].copy()
+        h.sync()
+        t0 = time.perf_counter()
+        done, chis, lams, trials = lm.optimize(host, h, args.iterations, "lm")
+        h.sync()
+        ms_b.append(1e3 * (time.perf_counter() - t0) / max(1, done))
+        traj_b = (chis, trials)
+    emit(dict(size, what="lm_iteration", path="host_numpy_producers", ms_per_lm_iteration=spread(ms_b), lm_trials=traj_b[1],
+              chi2=traj_b[0]))
+    del h, host
