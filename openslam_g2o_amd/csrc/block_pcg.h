@@ -47,6 +47,8 @@ class BlockPCG {
   void reset_residual() { residual_ = -1.0; }
 
  private:
+  template <int BS, class Apply>
+  bool iterate(const double* d_diag_blocks, const Apply& apply, const double* d_b, double* d_x, hipStream_t st);
   int bs_, nb_ = 0, iters_ = 0;
   double residual_ = -1.0;
   DevBuf<int> d_diag, d_ent_ptr, d_ent;   // per block row: diagonal block id; entries (block id << 1 | transposed, other block row)

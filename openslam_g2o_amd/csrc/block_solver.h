@@ -205,7 +205,11 @@ class BlockSolver {
   void run_seg(int id, F&& body);
   void build_system_impl();
   void solve_schur_impl(bool want_matrix = true);
+  template <int P, int L>
+  void launch_schur_tiles(int G, bool fuse_inv);
   void launch_schur_reduce(bool matrix);
+  void launch_reduce_kernel(int n_red, bool split, double* Hs, const unsigned char* lam_mask, const int* list);
+  void launch_chi2(const EdgeSet& es, int nblocks, double* red);
   void ensure_hschur();
   bool virtual_reduced_ok();
   void solve_reduced_device();

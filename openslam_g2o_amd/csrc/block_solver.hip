@@ -17,6 +17,7 @@ namespace g2ohip {
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 1024;   // partial sums per slot of d_red_multi (slot 0: computeScale, slot k + 1: chi2 of edge set k)
 
 // Sum over groups of G consecutive lanes (G = 1, 2, 4, 8, 16) with DPP lane permutations: no LDS
 // round trip (ds_bpermute) per step.  Every lane of the group ends up with the total.
@@ -2085,66 +2086,49 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
 
 // ---- dispatch tables ----------------------------------------------------------------
+template <int V>
+constexpr std::integral_constant<int, V> ic{};   // a table row's entry as a type (the rows of dispatch_vertex / dispatch_offdiag)
+
 template <int D, int DV>
 void launch_vertex(int G, int nV, const int* vptr, const int* vent, const EdgeSet& es, double* H, const int* diag_blk, double* b,
                    int accumulate, hipStream_t st) {
   if (nV == 0) return;
-#define G2OHIP_LV(GG)                                                                                                    \
-  hipLaunchKernelGGL((assemble_vertex_kernel<D, DV, GG>), dim3(grid_for((size_t)nV * GG)), dim3(kThreads), 0, st, nV, vptr, \
-                     vent, es.J0, es.J1, es.omega, es.err, es.kernel_kind, es.delta, H, diag_blk, b, accumulate, es.rk.p)
-  if (G <= 1)
-    G2OHIP_LV(1);
-  else if (G <= 4)
-    G2OHIP_LV(4);
-  else
-    G2OHIP_LV(8);
-#undef G2OHIP_LV
+  with_lane_group<1, 4, 8>(G, [&](auto g) {
+    constexpr int GG = g;
+    hipLaunchKernelGGL((assemble_vertex_kernel<D, DV, GG>), dim3(grid_for((size_t)nV * GG)), dim3(kThreads), 0, st, nV, vptr,
+                       vent, es.J0, es.J1, es.omega, es.err, es.kernel_kind, es.delta, H, diag_blk, b, accumulate, es.rk.p);
+  });
 }
 
 void dispatch_vertex(int D, int DV, int G, int nV, const int* vptr, const int* vent, const EdgeSet& es, double* H,
                      const int* diag_blk, double* b, int accumulate, hipStream_t st) {
-#define G2OHIP_CASE(d_, v_) \
-  if (D == d_ && DV == v_) return launch_vertex<d_, v_>(G, nV, vptr, vent, es, H, diag_blk, b, accumulate, st)
-  G2OHIP_CASE(2, 2);
-  G2OHIP_CASE(2, 3);
-  G2OHIP_CASE(2, 6);
-  G2OHIP_CASE(3, 2);
-  G2OHIP_CASE(3, 3);
-  G2OHIP_CASE(3, 6);
-  G2OHIP_CASE(6, 6);
-  G2OHIP_CASE(7, 7);
-  G2OHIP_CASE(1, 3);
-  G2OHIP_CASE(1, 6);
-  G2OHIP_CASE(1, 2);   // bearing-only observations of 2D points (EdgeSE2PointBearing)
-  G2OHIP_CASE(2, 7);   // projections seen from similarity poses (EdgeSim3ProjectXYZ, BlockSolver_7_3)
-  G2OHIP_CASE(3, 7);
-#undef G2OHIP_CASE
+  auto row = [&](auto d, auto dv) {   // the row (d, dv) of the table: launches it if it is the one asked for
+    if (D != d || DV != dv) return false;
+    launch_vertex<decltype(d)::value, decltype(dv)::value>(G, nV, vptr, vent, es, H, diag_blk, b, accumulate, st);
+    return true;
+  };
+  if (row(ic<2>, ic<2>) || row(ic<2>, ic<3>) || row(ic<2>, ic<6>) || row(ic<3>, ic<2>) || row(ic<3>, ic<3>) || row(ic<3>, ic<6>) ||
+      row(ic<6>, ic<6>) || row(ic<7>, ic<7>) || row(ic<1>, ic<3>) || row(ic<1>, ic<6>) ||
+      row(ic<1>, ic<2>) ||                        // bearing-only observations of 2D points (EdgeSE2PointBearing)
+      row(ic<2>, ic<7>) || row(ic<3>, ic<7>))     // projections seen from similarity poses (EdgeSim3ProjectXYZ, BlockSolver_7_3)
+    return;
   throw ArgFailure("unsupported (error_dim, vertex_dim) = (" + std::to_string(D) + "," + std::to_string(DV) + ")");
 }
 
 void dispatch_offdiag(int D, int DR, int DC, int nDst, const int* dst, const int* ptr, const int* ent, const EdgeSet& es, double* H,
                       int accumulate, hipStream_t st) {
   if (nDst == 0) return;
-#define G2OHIP_CASE(d_, r_, c_)                                                                                         \
-  if (D == d_ && DR == r_ && DC == c_) {                                                                                \
-    hipLaunchKernelGGL((assemble_offdiag_kernel<d_, r_, c_>), dim3(grid_for(nDst)), dim3(kThreads), 0, st, nDst, dst, ptr, \
-                       ent, es.J0, es.J1, es.omega, es.err, es.kernel_kind, es.delta, H, accumulate, es.rk.p);          \
-    return;                                                                                                             \
-  }
-  G2OHIP_CASE(2, 3, 2);
-  G2OHIP_CASE(2, 6, 3);
-  G2OHIP_CASE(3, 3, 3);
-  G2OHIP_CASE(3, 6, 3);
-  G2OHIP_CASE(6, 6, 6);
-  G2OHIP_CASE(7, 7, 7);
-  G2OHIP_CASE(2, 3, 3);
-  G2OHIP_CASE(2, 6, 6);
-  G2OHIP_CASE(3, 6, 6);
-  G2OHIP_CASE(1, 3, 2);
-  G2OHIP_CASE(1, 6, 3);
-  G2OHIP_CASE(2, 7, 3);
-  G2OHIP_CASE(3, 7, 3);
-#undef G2OHIP_CASE
+  auto row = [&](auto d, auto dr, auto dc) {   // the row (d, rows, cols) of the table: launches it if it is the one asked for
+    if (D != d || DR != dr || DC != dc) return false;
+    hipLaunchKernelGGL((assemble_offdiag_kernel<decltype(d)::value, decltype(dr)::value, decltype(dc)::value>), dim3(grid_for(nDst)), dim3(kThreads),
+                       0, st, nDst, dst, ptr, ent, es.J0, es.J1, es.omega, es.err, es.kernel_kind, es.delta, H, accumulate, es.rk.p);
+    return true;
+  };
+  if (row(ic<2>, ic<3>, ic<2>) || row(ic<2>, ic<6>, ic<3>) || row(ic<3>, ic<3>, ic<3>) || row(ic<3>, ic<6>, ic<3>) ||
+      row(ic<6>, ic<6>, ic<6>) || row(ic<7>, ic<7>, ic<7>) || row(ic<2>, ic<3>, ic<3>) || row(ic<2>, ic<6>, ic<6>) ||
+      row(ic<3>, ic<6>, ic<6>) || row(ic<1>, ic<3>, ic<2>) || row(ic<1>, ic<6>, ic<3>) || row(ic<2>, ic<7>, ic<3>) ||
+      row(ic<3>, ic<7>, ic<3>))
+    return;
   throw ArgFailure("unsupported off-diagonal block shape (d,rows,cols) = (" + std::to_string(D) + "," + std::to_string(DR) + "," +
                    std::to_string(DC) + ")");
 }
@@ -2218,19 +2202,14 @@ void group_by(int ndst, const std::vector<int>& dest, const std::vector<int>& pa
 static void prepare_ba_tile_kernels() {
   static bool attr = false;
   if (!attr) {
-#define G2OHIP_BA_TILE_ATTR(GG)                                                                                                    \
-  (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<GG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<GG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-    (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    G2OHIP_BA_TILE_ATTR(1);
-    G2OHIP_BA_TILE_ATTR(2);
-    G2OHIP_BA_TILE_ATTR(4);
-    G2OHIP_BA_TILE_ATTR(8);
-    G2OHIP_BA_TILE_ATTR(16);
-#undef G2OHIP_BA_TILE_ATTR
+    const auto set_attr = [](auto g, auto cls) {   // both FUSE_LL forms of a (lane-group width, edge classes) pair
+      constexpr int GG = g;
+      constexpr bool CLS = cls;
+      (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<GG, false, CLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)ba_schur_tile_kernel<GG, true, CLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    };
+    for_each_value<1, 8>([&](auto g) { set_attr(g, std::true_type{}); });   // (edge classes: these two widths only)
+    for_each_value<1, 2, 4, 8, 16>([&](auto g) { set_attr(g, std::false_type{}); });
     attr = true;
   }
 }
@@ -3199,20 +3178,17 @@ void BlockSolver::launch_ba_landmarks(bool write_hpl) {
   EdgeSet& es = *sets_[ba_.set];
   const size_t sizeP = (size_t)nP_ * p_;
   const int GL = ba_lm_group();
-#define G2OHIP_BA_LM_(GG, CC)                                                                                                    \
-  hipLaunchKernelGGL((ba_assemble_landmarks_kernel<GG, CC>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p, \
-                     es.vl_ent.p, ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.hpl_lm.p, ba_.f, \
-                     ba_.cx, ba_.cy, es.kernel_kind, es.delta, d_Hll.p, d_b.p + sizeP, d_Hpl.p, es.own_err.p, ba_.omega_identity ? 1 : 0, \
-                     d_pl_colptr.p, write_hpl ? 1 : 0, ba_.ctab.p)
-#define G2OHIP_BA_LM(GG) G2OHIP_BA_LM_(GG, false)
-  if (ba_.n_classes > 1) {   // (edge classes: one lane-group width is instantiated)
-    if (GL == 1) G2OHIP_BA_LM_(1, true);
-    else G2OHIP_BA_LM_(8, true);
-  } else if (GL == 1) G2OHIP_BA_LM(1);
-  else if (GL == 4) G2OHIP_BA_LM(4);
-  else G2OHIP_BA_LM(8);
-#undef G2OHIP_BA_LM
-#undef G2OHIP_BA_LM_
+  const auto launch = [&](auto g, auto cls) {
+    constexpr int GG = g;
+    constexpr bool CLS = cls;
+    hipLaunchKernelGGL((ba_assemble_landmarks_kernel<GG, CLS>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p,
+                       es.vl_ent.p, ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.hpl_lm.p, ba_.f,
+                       ba_.cx, ba_.cy, es.kernel_kind, es.delta, d_Hll.p, d_b.p + sizeP, d_Hpl.p, es.own_err.p, ba_.omega_identity ? 1 : 0,
+                       d_pl_colptr.p, write_hpl ? 1 : 0, ba_.ctab.p);
+  };
+  // (GL is 1, 4 or 8; edge classes: two lane-group widths are instantiated)
+  if (ba_.n_classes > 1) with_lane_group<1, 8>(GL, [&](auto g) { launch(g, std::true_type{}); });
+  else with_lane_group<1, 4, 8>(GL, [&](auto g) { launch(g, std::false_type{}); });
 }
 
 // May the fused BA assembly leave Hpl unwritten?  Only while its two readers on the solve path (Schur tiles,
@@ -3284,26 +3260,21 @@ void BlockSolver::launch_ba_poses() {
   const bool compact = es.n_vp_act > 0 && sets_.size() == 1 && chol_opt.world > 1;
   const int nPk = compact ? es.n_vp_act : nP_;
   const int* pact = compact ? es.vp_act.p : (const int*)nullptr;
-#define G2OHIP_BA_POSE_(GG, CC)                                                                                                  \
-  hipLaunchKernelGGL((ba_assemble_poses_kernel<GG, CC>), dim3(grid_for((size_t)nPk * GG)), dim3(kThreads), 0, st_, nPk, es.vp_ptr.p,  \
-                     ba_.cams.p, ba_.pts.p, ba_.cam_pm.p, ba_.pt_pm.p, ba_.meas_pm.p, ba_.omega_pm.p, ba_.f, ba_.cx, ba_.cy,       \
-                     es.kernel_kind, es.delta, d_Hpp.p, d_pp_diag.p, d_b.p, es.first_pose ? 0 : 1, ba_.omega_identity ? 1 : 0,     \
-                     pact, ba_.ctab.p)
-#define G2OHIP_BA_POSE(GG) G2OHIP_BA_POSE_(GG, false)
   if (compact && es.first_pose)
     hipLaunchKernelGGL(zero_inactive_poses_kernel, dim3(grid_for((size_t)(nP_ - nPk) * (p_ * p_ + p_))), dim3(kThreads), 0, st_, nP_ - nPk, p_,
                        es.vp_act.p + nPk, d_pp_diag.p, d_Hpp.p, d_b.p);
-  if (es.touches_pose) {
-    static const int g_env = getenv("G2OHIP_POSE_GROUP") ? atoi(getenv("G2OHIP_POSE_GROUP")) : 0;   // (experiments)
-    const int Gp = g_env > 0 ? g_env : G;
-    if (ba_.n_classes > 1) G2OHIP_BA_POSE_(8, true);   // (edge classes: one lane-group width is instantiated)
-    else if (Gp <= 1) G2OHIP_BA_POSE(1);
-    else if (Gp <= 4) G2OHIP_BA_POSE(4);
-    else if (Gp <= 8) G2OHIP_BA_POSE(8);
-    else G2OHIP_BA_POSE(16);
-  }
-#undef G2OHIP_BA_POSE
-#undef G2OHIP_BA_POSE_
+  if (!es.touches_pose) return;
+  const auto launch = [&](auto g, auto cls) {
+    constexpr int GG = g;
+    constexpr bool CLS = cls;
+    hipLaunchKernelGGL((ba_assemble_poses_kernel<GG, CLS>), dim3(grid_for((size_t)nPk * GG)), dim3(kThreads), 0, st_, nPk, es.vp_ptr.p,
+                       ba_.cams.p, ba_.pts.p, ba_.cam_pm.p, ba_.pt_pm.p, ba_.meas_pm.p, ba_.omega_pm.p, ba_.f, ba_.cx, ba_.cy,
+                       es.kernel_kind, es.delta, d_Hpp.p, d_pp_diag.p, d_b.p, es.first_pose ? 0 : 1, ba_.omega_identity ? 1 : 0,
+                       pact, ba_.ctab.p);
+  };
+  static const int g_env = getenv("G2OHIP_POSE_GROUP") ? atoi(getenv("G2OHIP_POSE_GROUP")) : 0;   // (experiments)
+  if (ba_.n_classes > 1) launch(ic<8>, std::true_type{});   // (edge classes: one lane-group width is instantiated)
+  else with_lane_group<1, 4, 8, 16>(g_env > 0 ? g_env : G, [&](auto g) { launch(g, std::false_type{}); });
 }
 
 void BlockSolver::build_system_impl() {
@@ -3380,6 +3351,15 @@ double BlockSolver::reduce_sum_finish(int nblocks) {
   return s;
 }
 
+// the partial sums of an edge set's chi2 (one per workgroup) into red
+void BlockSolver::launch_chi2(const EdgeSet& es, int nblocks, double* red) {
+  const bool known = dispatch_value<1, 2, 3, 6, 7>(es.d, [&](auto d) {
+    constexpr int D = d;
+    hipLaunchKernelGGL((chi2_kernel<D>), dim3(nblocks), dim3(kThreads), 0, st_, es.n, es.omega, es.err, es.kernel_kind, es.delta, red, es.rk.p);
+  });
+  if (!known) throw ArgFailure("chi2: unsupported error dimension");
+}
+
 double BlockSolver::chi2() {
   require_structure();
   if (chi2_valid_) return chi2_value_;   // same errors, same kernels as the last evaluation (LM asks twice per accepted step)
@@ -3393,29 +3373,15 @@ double BlockSolver::chi2() {
     if (!es.has_err) throw StateFailure("chi2: edge data missing");
     int nblocks = std::min(1024, grid_for(es.n));
     if (ba_.err_valid && esp.get() == sets_[ba_.set].get()) {   // partial sums left by ba_linearize (same values trial_stats reads)
-      std::vector<double> h(1024);
-      G2OHIP_HIP_CHECK(hipMemcpyAsync(h.data(), d_red_multi.p + (size_t)(ba_.set + 1) * 1024, 1024 * sizeof(double), hipMemcpyDeviceToHost, st_));
+      std::vector<double> h(kMaxBlocks);
+      G2OHIP_HIP_CHECK(hipMemcpyAsync(h.data(), d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks, kMaxBlocks * sizeof(double), hipMemcpyDeviceToHost, st_));
       G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
       double sset = 0.0;
       for (double v : h) sset += v;
       total += sset;
       continue;
     }
-#define G2OHIP_CHI(d_)                                                                                                      \
-  case d_:                                                                                                                  \
-    hipLaunchKernelGGL((chi2_kernel<d_>), dim3(nblocks), dim3(kThreads), 0, st_, es.n, es.omega, es.err, es.kernel_kind, es.delta, \
-                       d_red.p, es.rk.p);                                                                                   \
-    break
-    switch (es.d) {
-      G2OHIP_CHI(1);
-      G2OHIP_CHI(2);
-      G2OHIP_CHI(3);
-      G2OHIP_CHI(6);
-      G2OHIP_CHI(7);
-      default:
-        throw ArgFailure("chi2: unsupported error dimension");
-    }
-#undef G2OHIP_CHI
+    launch_chi2(es, nblocks, d_red.p);
     total += reduce_sum_finish(nblocks);
   }
   chi2_value_ = total;
@@ -3544,25 +3510,60 @@ void BlockSolver::solve_schur() {
   if (sv && ex_.nbb > 0) launch_boundary_reduce();
 }
 
+// schur_reduce_kernel over n_red blocks of the reduced system (list: their indices, null: the first n_red) into Hs.  NRP: the rows
+// per lane part of the tile kernel's partial layout -- an even pose dimension is split in two when the tiles ran with G >= 2.
+void BlockSolver::launch_reduce_kernel(int n_red, bool split, double* Hs, const unsigned char* lam_mask, const int* list) {
+  const auto launch = [&](auto p, auto nrp) {
+    constexpr int P = p, NRP = nrp;
+    hipLaunchKernelGGL((schur_reduce_kernel<P, NRP>), dim3(grid_for((size_t)n_red * P * P)), dim3(kThreads), 0, st_, n_red,
+                       d_rd_ptr.p, d_rd_slot.p, d_hs_src.p, d_Hpp.p, d_Pd.p, Hs, d_hs_diag.p, d_Pr.p, d_b.p, d_bschur.p, d_lam.p,
+                       lam_mask, list, (int)std::max<long>(1, n_td_));
+  };
+  if (p_ == 3) launch(ic<3>, ic<3>);
+  else if (p_ == 6 && split) launch(ic<6>, ic<3>);
+  else if (p_ == 6) launch(ic<6>, ic<6>);
+  else if (p_ == 7) launch(ic<7>, ic<7>);
+  else throw ArgFailure("unsupported pose dimension for Schur");
+}
+
 // sharded solve: the boundary blocks of the reduced system (and the right-hand side of their diagonal ones) from this rank's
 // Hpp and partial blocks, into the region behind Hpp -- schur_reduce_kernel over the boundary list
 void BlockSolver::launch_boundary_reduce() {
   const int G = pick_group((double)n_sc_ / std::max<long>(1, n_td_));
   const bool split = (p_ % 2 == 0) && G >= 2;
-  double* Hs = d_Hpp.p + hpp_blocks_ * (size_t)p_ * p_;
-  const int n_red = ex_.nbb;
-#define G2OHIP_RED(P_, NRP_)                                                                                                  \
-  hipLaunchKernelGGL((schur_reduce_kernel<P_, NRP_>), dim3(grid_for((size_t)n_red * P_ * P_)), dim3(kThreads), 0, st_, n_red,     \
-                     d_rd_ptr.p, d_rd_slot.p, d_hs_src.p, d_Hpp.p, d_Pd.p, Hs, d_hs_diag.p, d_Pr.p, d_b.p, d_bschur.p, d_lam.p,  \
-                     d_lam_mask.p, ex_.bblock.p, (int)std::max<long>(1, n_td_))
-  switch (p_) {
-    case 3: G2OHIP_RED(3, 3); break;
-    case 6: if (split) G2OHIP_RED(6, 3); else G2OHIP_RED(6, 6); break;
-    case 7: G2OHIP_RED(7, 7); break;
-    default: throw ArgFailure("unsupported pose dimension for Schur");
-  }
-#undef G2OHIP_RED
+  launch_reduce_kernel(ex_.nbb, split, d_Hpp.p + hpp_blocks_ * (size_t)p_ * p_, d_lam_mask.p, ex_.bblock.p);
   G2OHIP_HIP_CHECK(hipGetLastError());
+}
+
+// Pass 1 of the generic Schur complement: the landmark inverses (unless the tiles invert their landmarks themselves: fuse_inv),
+// then the tiles' partial blocks with G lanes per pose pair.
+template <int P, int L>
+void BlockSolver::launch_schur_tiles(int G, bool fuse_inv) {
+  const size_t sizeP = (size_t)nP_ * p_;
+  if (!fuse_inv) {
+    prof.begin(KernelProf::kLmInverse, st_);
+    hipLaunchKernelGGL((landmark_inverse_kernel<L>), dim3(grid_for(nL_)), dim3(kThreads), 0, st_, nL_, d_Hll.p, d_b.p + sizeP,
+                       d_Dinv.p, d_db.p, d_lam.p);
+    prof.end(KernelProf::kLmInverse, st_);
+  }
+  prof.begin(KernelProf::kSchurBlocks, st_);
+  if (n_tiles_ > 0) {
+    static bool attr = false;
+    if (!attr) {
+      for_each_value<1, 2, 4, 8, 16>([](auto g) {
+        constexpr int GG = g;
+        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P, L, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      });
+      attr = true;
+    }
+    with_lane_group<1, 2, 4, 8, 16>(G, [&](auto g) {
+      constexpr int GG = g;
+      hipLaunchKernelGGL((schur_tile_kernel<P, L, GG>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p, d_tile_td0.p,
+                         d_pl_colptr.p, d_Hpl.p, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p, d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p,
+                         fuse_inv ? d_Hll.p : (const double*)nullptr, d_lam.p, d_tile_q2.p, d_slot_lm.p);
+    });
+  }
+  prof.end(KernelProf::kSchurBlocks, st_);
 }
 
 void BlockSolver::solve_schur_impl(bool want_matrix) {
@@ -3586,78 +3587,36 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
     // metric configuration; a later reader (maxDiagonal, multiplyHessian, chi2 without a linearisation, inspection) has them
     // recomputed by ensure_ll()
     static const int schur_abl = getenv("G2OHIP_SCHUR_ABL") ? atoi(getenv("G2OHIP_SCHUR_ABL")) & ~1 : 0;   // (timing experiments only)
-#define G2OHIP_BA_TILE(GG) G2OHIP_BA_TILE_(GG, false)
-#define G2OHIP_BA_TILE_(GG, CC)                                                                                                    \
-  do {                                                                                                                             \
-    if (fll)                                                                                                                       \
-      hipLaunchKernelGGL((ba_schur_tile_kernel<GG, true, CC>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,        \
-                         ba_.cams.p, ba_.pts.p, (const int*)nullptr, (const int*)nullptr, ba_.ll_meas.p, ba_.ll_omega.p, ba_.f, ba_.cx,  \
-                         ba_.cy,                                                                                                     \
-                         es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,     \
-                         d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, ba_.ll_rec.p, ba_.tile_ll.p, ba_.ll_edge.p,       \
-                         (double*)nullptr, d_tile_q2.p, schur_abl, d_slot_lm.p, ba_.ctab.p);                                                  \
-    else                                                                                                                           \
-      hipLaunchKernelGGL((ba_schur_tile_kernel<GG, false, CC>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,       \
-                         ba_.cams.p, ba_.pts.p, ba_.cam_q.p, ba_.pt_q.p, ba_.meas_q.p, ba_.omega_q.p, ba_.f, ba_.cx, ba_.cy,           \
-                         es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,     \
-                         d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, (const int4*)nullptr, (const int4*)nullptr,        \
-                         (const int*)nullptr, (double*)nullptr, d_tile_q2.p, 1, d_slot_lm.p, ba_.ctab.p);                                  \
-  } while (0)
-    if (ba_.n_classes > 1) {   // edge classes: two lane-group widths are instantiated -- the ones on either side of the row split of the
-      if (G <= 1) G2OHIP_BA_TILE_(1, true);   // partial blocks (launch_schur_reduce and the factorisation read the layout G implies)
-      else G2OHIP_BA_TILE_(8, true);
-    } else if (G <= 1) G2OHIP_BA_TILE(1);
-    else if (G <= 2) G2OHIP_BA_TILE(2);
-    else if (G <= 4) G2OHIP_BA_TILE(4);
-    else if (G <= 8) G2OHIP_BA_TILE(8);
-    else G2OHIP_BA_TILE(16);
+    const auto launch = [&](auto g, auto cls) {
+      constexpr int GG = g;
+      constexpr bool CLS = cls;
+      if (fll)
+        hipLaunchKernelGGL((ba_schur_tile_kernel<GG, true, CLS>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,
+                           ba_.cams.p, ba_.pts.p, (const int*)nullptr, (const int*)nullptr, ba_.ll_meas.p, ba_.ll_omega.p, ba_.f, ba_.cx,
+                           ba_.cy,
+                           es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,
+                           d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, ba_.ll_rec.p, ba_.tile_ll.p, ba_.ll_edge.p,
+                           (double*)nullptr, d_tile_q2.p, schur_abl, d_slot_lm.p, ba_.ctab.p);
+      else
+        hipLaunchKernelGGL((ba_schur_tile_kernel<GG, false, CLS>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,
+                           ba_.cams.p, ba_.pts.p, ba_.cam_q.p, ba_.pt_q.p, ba_.meas_q.p, ba_.omega_q.p, ba_.f, ba_.cx, ba_.cy,
+                           es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,
+                           d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, (const int4*)nullptr, (const int4*)nullptr,
+                           (const int*)nullptr, (double*)nullptr, d_tile_q2.p, 1, d_slot_lm.p, ba_.ctab.p);
+    };
+    // edge classes: two lane-group widths are instantiated -- the ones on either side of the row split of the partial blocks
+    // (launch_schur_reduce and the factorisation read the layout G implies)
+    if (ba_.n_classes > 1) with_lane_group<1, 8>(G, [&](auto g) { launch(g, std::true_type{}); });
+    else with_lane_group<1, 2, 4, 8, 16>(G, [&](auto g) { launch(g, std::false_type{}); });
     ll_valid_ = true;
     ll_hbm_partial_ = fll;
-#undef G2OHIP_BA_TILE
-#undef G2OHIP_BA_TILE_
     prof.end(KernelProf::kSchurBlocks, st_);
-  } else
-#define G2OHIP_TILE_ARGS d_tile_lm0.p, d_tile_td0.p, d_pl_colptr.p, d_Hpl.p, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p, d_te_pack.p, \
-                         d_te_lm.p, d_Pd.p, d_Pr.p, fuse_inv ? d_Hll.p : (const double*)nullptr, d_lam.p, d_tile_q2.p, d_slot_lm.p
-#define G2OHIP_SCHUR(P_, L_)                                                                                                   \
-  if (p_ == P_ && l_ == L_) {                                                                                                  \
-    if (!fuse_inv) {                                                                                                           \
-      prof.begin(KernelProf::kLmInverse, st_);                                                                                 \
-      hipLaunchKernelGGL((landmark_inverse_kernel<L_>), dim3(grid_for(nL_)), dim3(kThreads), 0, st_, nL_, d_Hll.p, d_b.p + sizeP, \
-                         d_Dinv.p, d_db.p, d_lam.p);                                                                           \
-      prof.end(KernelProf::kLmInverse, st_);                                                                                   \
-    }                                                                                                                          \
-    prof.begin(KernelProf::kSchurBlocks, st_);                                                                                 \
-    if (n_tiles_ > 0) {                                                                                                        \
-      static bool attr = false;                                                                                                \
-      if (!attr) {                                                                                                             \
-        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P_, L_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P_, L_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P_, L_, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P_, L_, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)schur_tile_kernel<P_, L_, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        attr = true;                                                                                                           \
-      }                                                                                                                        \
-      if (G <= 1)                                                                                                              \
-        hipLaunchKernelGGL((schur_tile_kernel<P_, L_, 1>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, G2OHIP_TILE_ARGS); \
-      else if (G <= 2)                                                                                                         \
-        hipLaunchKernelGGL((schur_tile_kernel<P_, L_, 2>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, G2OHIP_TILE_ARGS); \
-      else if (G <= 4)                                                                                                         \
-        hipLaunchKernelGGL((schur_tile_kernel<P_, L_, 4>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, G2OHIP_TILE_ARGS); \
-      else if (G <= 8)                                                                                                         \
-        hipLaunchKernelGGL((schur_tile_kernel<P_, L_, 8>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, G2OHIP_TILE_ARGS); \
-      else                                                                                                                     \
-        hipLaunchKernelGGL((schur_tile_kernel<P_, L_, 16>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, G2OHIP_TILE_ARGS); \
-    }                                                                                                                          \
-    prof.end(KernelProf::kSchurBlocks, st_);                                                                                   \
-  } else
-  G2OHIP_SCHUR(6, 3)
-  G2OHIP_SCHUR(3, 2)
-  G2OHIP_SCHUR(7, 3)
-  G2OHIP_SCHUR(6, 2)
-  G2OHIP_SCHUR(3, 3) { throw ArgFailure("unsupported (pose_dim, landmark_dim) for Schur"); }
-#undef G2OHIP_SCHUR
-#undef G2OHIP_TILE_ARGS
+  } else if (p_ == 6 && l_ == 3) launch_schur_tiles<6, 3>(G, fuse_inv);
+  else if (p_ == 3 && l_ == 2) launch_schur_tiles<3, 2>(G, fuse_inv);
+  else if (p_ == 7 && l_ == 3) launch_schur_tiles<7, 3>(G, fuse_inv);
+  else if (p_ == 6 && l_ == 2) launch_schur_tiles<6, 2>(G, fuse_inv);
+  else if (p_ == 3 && l_ == 3) launch_schur_tiles<3, 3>(G, fuse_inv);
+  else throw ArgFailure("unsupported (pose_dim, landmark_dim) for Schur");
   prof.begin(KernelProf::kSchurRhs, st_);
   launch_schur_reduce(want_matrix);
   prof.end(KernelProf::kSchurRhs, st_);
@@ -3683,36 +3642,20 @@ void BlockSolver::launch_schur_reduce(bool matrix) {
     const bool pre = chol_opt.world <= 1 && linear_solver == 0;
     size_t xpn = 0;
     rhs_prefilled_ = pre;
-#define G2OHIP_RHS(P_)                                                                                                        \
-  case P_:                                                                                                                    \
-    hipLaunchKernelGGL((schur_rhs_kernel<P_>), dim3(grid_for((size_t)nP_ * P_)), dim3(kThreads), 0, st_, nP_, d_pose_diag.p, d_rd_ptr.p, \
-                       d_rd_slot.p, d_Pr.p, d_b.p, d_bschur.p, pre ? chol_->inverse_permutation_device() : (const int*)nullptr,        \
-                       pre ? chol_->permuted_solution(&xpn) : (double*)nullptr, pre ? chol_->status_word_device() : (int*)nullptr);      \
-    break
-    switch (p_) {
-      G2OHIP_RHS(3);
-      G2OHIP_RHS(6);
-      G2OHIP_RHS(7);
-      default: throw ArgFailure("unsupported pose dimension for Schur");
-    }
-#undef G2OHIP_RHS
+    const bool known = dispatch_value<3, 6, 7>(p_, [&](auto p) {
+      constexpr int P = p;
+      hipLaunchKernelGGL((schur_rhs_kernel<P>), dim3(grid_for((size_t)nP_ * P)), dim3(kThreads), 0, st_, nP_, d_pose_diag.p, d_rd_ptr.p,
+                         d_rd_slot.p, d_Pr.p, d_b.p, d_bschur.p, pre ? chol_->inverse_permutation_device() : (const int*)nullptr,
+                         pre ? chol_->permuted_solution(&xpn) : (double*)nullptr, pre ? chol_->status_word_device() : (int*)nullptr);
+    });
+    if (!known) throw ArgFailure("unsupported pose dimension for Schur");
     return;
   }
   hschur_valid_ = true;
   const int n_red = n_active_ >= 0 ? n_active_ : hs_nnzb;
   if (n_red <= 0) return;
-#define G2OHIP_RED(P_, NRP_)                                                                                                  \
-  hipLaunchKernelGGL((schur_reduce_kernel<P_, NRP_>), dim3(grid_for((size_t)n_red * P_ * P_)), dim3(kThreads), 0, st_, n_red,     \
-                     d_rd_ptr.p, d_rd_slot.p, d_hs_src.p, d_Hpp.p, d_Pd.p, d_Hschur.p, d_hs_diag.p, d_Pr.p, d_b.p, d_bschur.p, \
-                     d_lam.p, chol_opt.world > 1 ? d_lam_mask.p : (const unsigned char*)nullptr,                              \
-                     n_active_ >= 0 ? d_active.p : (const int*)nullptr, (int)std::max<long>(1, n_td_))
-  switch (p_) {
-    case 3: G2OHIP_RED(3, 3); break;
-    case 6: if (split) G2OHIP_RED(6, 3); else G2OHIP_RED(6, 6); break;
-    case 7: G2OHIP_RED(7, 7); break;
-    default: throw ArgFailure("unsupported pose dimension for Schur");
-  }
-#undef G2OHIP_RED
+  launch_reduce_kernel(n_red, split, d_Hschur.p, chol_opt.world > 1 ? d_lam_mask.p : (const unsigned char*)nullptr,
+                       n_active_ >= 0 ? d_active.p : (const int*)nullptr);
 }
 
 // somebody reads Hschur (copy_values, PCG, marginals, multi-GPU exchange) after a solve() that skipped it
@@ -4329,39 +4272,36 @@ void BlockSolver::solve_back_substitute_impl() {
     EdgeSet& es = *sets_[ba_.set];
     const int GL = ba_lm_group();
     if (ba_fuse_landmarks && ba_.ll_slots_ok && n_tiles_ > 0) {
-#define G2OHIP_BA_BACK_SLOTS(CC)                                                                                                   \
-  hipLaunchKernelGGL((ba_back_substitute_slots_kernel<CC>), dim3(n_tiles_), dim3(kThreads), 0, st_, d_tile_lm0.p, ba_.tile_ll.p,    \
-                     ba_.ll_rec.p, ba_.ll_row.p, ba_.ll_meas.p, ba_.ll_omega.p, ba_.cams.p, ba_.pts.p, ba_.f, ba_.cx, ba_.cy,       \
-                     es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p, d_x.p + sizeP, ba_.ctab.p)
-      if (ba_.n_classes > 1) G2OHIP_BA_BACK_SLOTS(true);
-      else G2OHIP_BA_BACK_SLOTS(false);
-#undef G2OHIP_BA_BACK_SLOTS
-    } else
-#define G2OHIP_BA_BACK(GG) G2OHIP_BA_BACK_(GG, false)
-#define G2OHIP_BA_BACK_(GG, CC)                                                                                                    \
-  hipLaunchKernelGGL((ba_back_substitute_kernel<GG, CC>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p, \
-                     ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.row_lm.p, ba_.f,          \
-                     ba_.cx, ba_.cy, es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p,           \
-                     d_x.p + sizeP, ba_.ctab.p)
-    if (ba_.n_classes > 1) G2OHIP_BA_BACK_(8, true);
-    else if (GL == 1) G2OHIP_BA_BACK(1);
-    else if (GL == 4) G2OHIP_BA_BACK(4);
-    else G2OHIP_BA_BACK(8);
-#undef G2OHIP_BA_BACK
-#undef G2OHIP_BA_BACK_
-  } else if ((ensure_hpl(), false)) {
-  } else
-#define G2OHIP_BACK(P_, L_)                                                                                                    \
-  if (p_ == P_ && l_ == L_)                                                                                                    \
-    hipLaunchKernelGGL((back_substitute_kernel<P_, L_>), dim3(grid_for(nL_)), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p,        \
-                       d_pl_row.p, d_Hpl.p, d_Dinv.p, d_b.p + sizeP, d_x.p, d_x.p + sizeP);                                    \
-  else
-  G2OHIP_BACK(6, 3)
-  G2OHIP_BACK(3, 2)
-  G2OHIP_BACK(7, 3)
-  G2OHIP_BACK(6, 2)
-  G2OHIP_BACK(3, 3) { throw ArgFailure("unsupported (pose_dim, landmark_dim)"); }
-#undef G2OHIP_BACK
+      with_bool(ba_.n_classes > 1, [&](auto cls) {
+        constexpr bool CLS = cls;
+        hipLaunchKernelGGL((ba_back_substitute_slots_kernel<CLS>), dim3(n_tiles_), dim3(kThreads), 0, st_, d_tile_lm0.p, ba_.tile_ll.p,
+                           ba_.ll_rec.p, ba_.ll_row.p, ba_.ll_meas.p, ba_.ll_omega.p, ba_.cams.p, ba_.pts.p, ba_.f, ba_.cx, ba_.cy,
+                           es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p, d_x.p + sizeP, ba_.ctab.p);
+      });
+    } else {
+      const auto launch = [&](auto g, auto cls) {
+        constexpr int GG = g;
+        constexpr bool CLS = cls;
+        hipLaunchKernelGGL((ba_back_substitute_kernel<GG, CLS>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p,
+                           ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.row_lm.p, ba_.f,
+                           ba_.cx, ba_.cy, es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p,
+                           d_x.p + sizeP, ba_.ctab.p);
+      };
+      if (ba_.n_classes > 1) launch(ic<8>, std::true_type{});   // (edge classes: one lane-group width is instantiated)
+      else with_lane_group<1, 4, 8>(GL, [&](auto g) { launch(g, std::false_type{}); });   // (GL is 1, 4 or 8)
+    }
+  } else {
+    ensure_hpl();
+    const auto row = [&](auto p, auto l) {   // the pair (p, l) of the list below: launches it if it is this solver's
+      constexpr int P = p, L = l;
+      if (p_ != P || l_ != L) return false;
+      hipLaunchKernelGGL((back_substitute_kernel<P, L>), dim3(grid_for(nL_)), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p,
+                         d_pl_row.p, d_Hpl.p, d_Dinv.p, d_b.p + sizeP, d_x.p, d_x.p + sizeP);
+      return true;
+    };
+    if (!(row(ic<6>, ic<3>) || row(ic<3>, ic<2>) || row(ic<7>, ic<3>) || row(ic<6>, ic<2>) || row(ic<3>, ic<3>)))
+      throw ArgFailure("unsupported (pose_dim, landmark_dim)");
+  }
   prof.end(KernelProf::kBackSub, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   if (profiling) {
@@ -4445,11 +4385,14 @@ void BlockSolver::mf_prepare_lists() {
   pcg_hpp_->analyze(nP_, pp_colptr.data(), pp_row.data(), st_);
 }
 
-#define G2OHIP_MF_DISPATCH(BODY)                                                                              \
-  if (p_ == 6 && l_ == 3) { constexpr int P_ = 6, L_ = 3; BODY }                                              \
-  else if (p_ == 3 && l_ == 2) { constexpr int P_ = 3, L_ = 2; BODY }                                         \
-  else if (p_ == 7 && l_ == 3) { constexpr int P_ = 7, L_ = 3; BODY }                                         \
+// f(ic<P>, ic<L>) for the (pose_dim, landmark_dim) pairs the matrix-free kernels are instantiated for
+template <class F>
+static void with_mf_dims(int p, int l, F&& f) {
+  if (p == 6 && l == 3) f(ic<6>, ic<3>);
+  else if (p == 3 && l == 2) f(ic<3>, ic<2>);
+  else if (p == 7 && l == 3) f(ic<7>, ic<3>);
   else throw ArgFailure("unsupported (pose_dim, landmark_dim) for the matrix-free reduced operator");
+}
 
 // Dinv = (Hll + lam_l I)^-1, bschur = b_p - Hpl Dinv b_l, diagonal blocks of the reduced system (device array 107)
 void BlockSolver::schur_operator_prepare() {
@@ -4460,17 +4403,18 @@ void BlockSolver::schur_operator_prepare() {
   ensure_hpl();
   const size_t sizeP = (size_t)nP_ * p_;
   const int gl = grid_for(nL_), gp = grid_for(sizeP);
-  G2OHIP_MF_DISPATCH(
-    const int gd = grid_for(sizeP * P_);
-    hipLaunchKernelGGL((landmark_inverse_kernel<L_>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_Hll.p, d_b.p + sizeP, d_Dinv.p, d_db.p,
+  with_mf_dims(p_, l_, [&](auto p, auto l) {
+    constexpr int P = p, L = l;
+    const int gd = grid_for(sizeP * P);
+    hipLaunchKernelGGL((landmark_inverse_kernel<L>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_Hll.p, d_b.p + sizeP, d_Dinv.p, d_db.p,
                        d_lam.p);
-    hipLaunchKernelGGL((back_substitute_kernel<P_, L_>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p, d_pl_row.p, d_Hpl.p,
+    hipLaunchKernelGGL((back_substitute_kernel<P, L>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p, d_pl_row.p, d_Hpl.p,
                        d_Dinv.p, d_b.p + sizeP, d_mf_zero.p, d_mf_l.p);   // Dinv b_l
-    hipLaunchKernelGGL((mf_pose_kernel<P_, L_>), dim3(gp), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
+    hipLaunchKernelGGL((mf_pose_kernel<P, L>), dim3(gp), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
                        d_mf_l.p, d_b.p, (const double*)nullptr, d_lam.p, -1.0, d_bschur.p);
-    hipLaunchKernelGGL((mf_diag_kernel<P_, L_>), dim3(gd), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
+    hipLaunchKernelGGL((mf_diag_kernel<P, L>), dim3(gd), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
                        d_Dinv.p, d_Hpp.p, d_pp_diag.p, d_lam.p, d_mf_diag.p);
-  )
+  });
   hschur_valid_ = false;
   G2OHIP_HIP_CHECK(hipGetLastError());
 }
@@ -4482,14 +4426,14 @@ void BlockSolver::schur_operator_apply(const double* din, double* dout) {
   const size_t sizeP = (size_t)nP_ * p_;
   const int gl = grid_for(nL_), gp = grid_for(sizeP);
   pcg_hpp_->multiply(d_Hpp.p, din, dout, st_);
-  G2OHIP_MF_DISPATCH(
-    hipLaunchKernelGGL((back_substitute_kernel<P_, L_>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p, d_pl_row.p, d_Hpl.p,
+  with_mf_dims(p_, l_, [&](auto p, auto l) {
+    constexpr int P = p, L = l;
+    hipLaunchKernelGGL((back_substitute_kernel<P, L>), dim3(gl), dim3(kThreads), 0, st_, nL_, d_pl_colptr.p, d_pl_row.p, d_Hpl.p,
                        d_Dinv.p, d_mf_zero.p, din, d_mf_l.p);   // -Dinv Hpl' d
-    hipLaunchKernelGGL((mf_pose_kernel<P_, L_>), dim3(gp), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
+    hipLaunchKernelGGL((mf_pose_kernel<P, L>), dim3(gp), dim3(kThreads), 0, st_, nP_, d_pm_ptr.p, d_pm_q.p, d_pm_lm.p, d_Hpl.p,
                        d_mf_l.p, dout, din, d_lam.p, 1.0, dout);
-  )
+  });
 }
-#undef G2OHIP_MF_DISPATCH
 
 int BlockSolver::solve_matrix_free() {
   if (chol_opt.world > 1) throw StateFailure("linear_solver 2 inside the library: one GPU (the sharded form lives in distributed.py)");
@@ -4559,7 +4503,6 @@ void BlockSolver::trial_stats_begin(double lambda) {
   if (trial_.begun) throw StateFailure("trial_stats_begin: the previous one has not been read (trial_stats)");
   require_structure();
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  constexpr int kMaxBlocks = 1024;
   const size_t nsets = sets_.size();
   if (d_red_multi.n < (nsets + 1) * kMaxBlocks) d_red_multi.alloc((nsets + 1) * kMaxBlocks);
   std::vector<int>& nblk = trial_.nblk;
@@ -4580,20 +4523,7 @@ void BlockSolver::trial_stats_begin(double lambda) {
       continue;
     }
     double* red = d_red_multi.p + (k + 1) * kMaxBlocks;
-#define G2OHIP_CHI(d_)                                                                                                      \
-  case d_:                                                                                                                  \
-    hipLaunchKernelGGL((chi2_kernel<d_>), dim3(nblk[k + 1]), dim3(kThreads), 0, st_, es.n, es.omega, es.err, es.kernel_kind, es.delta, red, es.rk.p); \
-    break
-    switch (es.d) {
-      G2OHIP_CHI(1);
-      G2OHIP_CHI(2);
-      G2OHIP_CHI(3);
-      G2OHIP_CHI(6);
-      G2OHIP_CHI(7);
-      default:
-        throw ArgFailure("chi2: unsupported error dimension");
-    }
-#undef G2OHIP_CHI
+    launch_chi2(es, nblk[k + 1], red);
   }
   G2OHIP_HIP_CHECK(hipGetLastError());
   // read-back into pinned memory: the partial sums and (asynchronous solve) the status word of the factorisation are two
@@ -4630,7 +4560,6 @@ void BlockSolver::trial_stats_begin(double lambda) {
 
 void BlockSolver::trial_stats(double lambda, int* ok, double* chi2_out, double* scale_out) {
   if (!trial_.begun) trial_stats_begin(lambda);
-  constexpr int kMaxBlocks = 1024;
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   trial_.begun = false;
   G2OHIP_HIP_CHECK(hipEventSynchronize(trial_ev_));
@@ -5334,7 +5263,6 @@ void BlockSolver::ba_linearize(bool jacobians) {
   if (profiling) tfe_.start(st_);
   // the chi2 of these errors rides along: 1 024 partial sums in this set's slot of the trial read-back buffer (chi2() and
   // trial_stats() take them from there while err_valid holds)
-  constexpr int kMaxBlocks = 1024;
   const int lgrid = grid_for(es.n);
   if (d_red_multi.n < (sets_.size() + 1) * kMaxBlocks) d_red_multi.alloc((sets_.size() + 1) * kMaxBlocks);
   if (ba_.chi_part.n < (size_t)lgrid) ba_.chi_part.alloc(lgrid);
@@ -5412,7 +5340,6 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   pg_.type = type;
   pg_.h_vi.assign(vi, vi + n);
   pg_.h_vj.assign(vj, vj + n);
-  pg_.set = set;
   pg_validate();
   pg_.vi.upload(vi, n, st_);
   pg_.vj.upload(vj, n, st_);

@@ -234,3 +234,5 @@ struct KernelProf {
 };
 
 }  // namespace g2ohip
+
+#include "dispatch.h"   // with_block_size & co. (needs ArgFailure)

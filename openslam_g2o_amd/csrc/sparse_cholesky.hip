@@ -2881,23 +2881,21 @@ __global__ void __launch_bounds__(256) big_level_kernel(CholPlanDev P, int slot0
   }
 }
 
-struct BigLaunch {   // whole-GPU passes over the scratch-slab fronts of one level (LevelLaunch::ba_* / be_pass / tr_*)
-  bool ok;
-  const int4* chunks;
-  int ba_begin, ba_count, tr_begin, tr_count;
-  const std::vector<std::pair<int, int>>* be_pass;
-  int fz_begin, fz_count;
-  bool hoisted = false;   // fill + assembly already done by the phase-wide passes
-  bool fwd = false;       // the forward step rides along in the pivot-block and panel kernels (big_forward_carried)
-  int* flag = nullptr;    // non-null: pivot blocks and panel tiles of the level in one launch (big_level_kernel), per-front flags
-  const int* ld;   // leading dimension per launch slot
-  int merge_tiles = 256;   // the fused panel kernel on levels of at most this many tiles (kBigMergeTiles)
-  bool gather = false;     // the merged level launch gathers the children's update matrices itself: no extend-add passes (LevelLaunch::gather)
-  int eg_begin = 0, eg_count = 0;   // the level's extend-add in one launch (big_extend_gather_kernel); 0: the passes per child ordinal
-  bool eg_write = false;            // ... into regions that were not zero-filled (LevelLaunch::eg_write), the original blocks la_* behind it
-  int eg_maxc = 7;                  // ... children per front of the level at most
-  int la_begin = 0, la_count = 0;
-  bool panel_solve = false;   // pivot blocks + panel rows of the level in one launch (big_panel_solve_kernel): LevelLaunch::tr_all and not a merged / fused level
+struct FactorArgs {   // what the launches of one level take besides its LevelLaunch (launch_factor fills it)
+  const long long* scratch_off;   // device tables: slab offset per launch slot,
+  double* scratch;                // the scratch slab,
+  const int4* big_tiles;          // the chunks / tiles of the whole-GPU passes (the LevelLaunch ranges index it),
+  const int* ld;                  // the leading dimension per launch slot
+  const double* dA;
+  const double* bperm;   // the forward step fused into the factorisation: permuted right-hand side, pivot solutions (null: none)
+  double* yout;
+  int dep;
+  int* flag;         // non-null: pivot blocks and panel tiles of the level in one launch (big_level_kernel), per-front flags
+  bool fwd;          // the forward step rides along in the pivot-block and panel kernels (big_forward_carried)
+  int merge_tiles;   // the fused panel kernel on levels of at most this many tiles (merge_tiles_of)
+  hipStream_t st;
+  int parts;   // bit 0 = the fronts held in LDS / registers, bit 1 = the scratch-slab fronts (the two halves of a level are
+               // independent: factor_phase may put them on different streams)
 };
 
 __global__ void __launch_bounds__(256) fill_zero_kernel(double* __restrict__ p, size_t n) {
@@ -2914,127 +2912,128 @@ __global__ void __launch_bounds__(256) fill_zero_kernel(double* __restrict__ p, 
     if (e_ != hipSuccess) throw StateFailure(std::string("launch of ") + name_ + " refused: " + hipGetErrorString(e_)); \
   } while (0)
 template <int BS, bool VIRT>
-void launch_factor_level(const CholPlanDev& P, const int* d_tasks, const long long* d_scratch_off, double* d_scratch,
-                         const double* dA, int lds_begin, int lds_count, int lds_max_m, int glb_begin, int glb_count,
-                         int lds_idx_ints, int glb_idx_ints, int sm_count, int sm_max_m, int sm_idx_ints, int wcap,
-                         const double* bperm, double* yout, int dep, const int4* big_tiles, int bt_count, const BigLaunch& big,
-                         int wide_doubles, bool wv, int wv_pn, int wv_idx_ints, hipStream_t st, int parts = 3) {
-  // parts: bit 0 = the fronts held in LDS / registers, bit 1 = the scratch-slab fronts (the two halves of a level are
-  // independent: factor_phase may put them on different streams)
-  if (!(parts & 1)) {
+void launch_factor_level(const CholPlanDev& P, const LevelLaunch& LL, const FactorArgs& A) {
+  hipStream_t st = A.st;
+  double* const d_scratch = A.scratch;
+  const long long* const d_scratch_off = A.scratch_off;
+  const int wcap = LL.lds_vec_m, bt_count = LL.bt_count;
+  const int4* const big_tiles = A.big_tiles + LL.bt_begin;
+  int lds_begin = LL.lds_begin, lds_count = LL.lds_count, sm_count = LL.sm_count;
+  if (!(A.parts & 1)) {
     lds_begin += sm_count;
     lds_count = 0;
     sm_count = 0;
-  } else if (wv) {   // every front of the launch fits the register-resident wave kernel: one wavefront per task
+  } else if (LL.wv) {   // every front of the launch fits the register-resident wave kernel: one wavefront per task
     const size_t sh = ((size_t)kWvTiles * 256 + 64 + 2 * kWvT * 64) * sizeof(double) + (size_t)(8 * 64 + 2 * 16 * kWvT + 2 * 64) * sizeof(int);
-    hipLaunchKernelGGL((wave_front_kernel<BS, VIRT>), dim3(lds_count), dim3(64 * kWvWaves), sh, st, wv_plan(P), lds_begin, dA, bperm, yout, dep);
+    hipLaunchKernelGGL((wave_front_kernel<BS, VIRT>), dim3(lds_count), dim3(64 * kWvWaves), sh, st, wv_plan(P), lds_begin, A.dA, A.bperm, A.yout, A.dep);
     G2OHIP_LAUNCH_CHECK("wave_front_kernel");
     return;
   }
   if (sm_count > 0) {   // wide launch: two waves per front
-    const int idx_off = sm_max_m + 2 * wcap + 2 * (BS * BS + BS);
-    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(sm_idx_ints + 4) * sizeof(int);
-    hipLaunchKernelGGL((front_factor_kernel<BS, true, 128, VIRT>), dim3(sm_count), dim3(128), sh, st, P, lds_begin, dA, d_scratch,
-                       d_scratch_off + lds_begin, idx_off, wcap, bperm, yout, dep);
+    const int idx_off = LL.sm_max_m + 2 * wcap + 2 * (BS * BS + BS);
+    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(LL.sm_idx_ints + 4) * sizeof(int);
+    hipLaunchKernelGGL((front_factor_kernel<BS, true, 128, VIRT>), dim3(sm_count), dim3(128), sh, st, P, lds_begin, A.dA, d_scratch,
+                       d_scratch_off + lds_begin, idx_off, wcap, A.bperm, A.yout, A.dep);
     G2OHIP_LAUNCH_CHECK("front_factor_kernel");
     lds_begin += sm_count;
     lds_count -= sm_count;
   }
   if (lds_count > 0) {
-    const int idx_off = lds_max_m + 2 * wcap + 2 * (BS * BS + BS);   // F (packed doubles) | tv | wprev | mailboxes | index lists
-    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(lds_idx_ints + 4) * sizeof(int);
+    const int idx_off = LL.lds_max_m + 2 * wcap + 2 * (BS * BS + BS);   // F (packed doubles) | tv | wprev | mailboxes | index lists
+    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(LL.lds_idx_ints + 4) * sizeof(int);
     // fronts of a hundred rows and more (pose graphs; they keep a CU to themselves anyway): eight waves per front
-    if (lds_max_m >= wide_doubles)
-      hipLaunchKernelGGL((front_factor_kernel<BS, true, 512, VIRT>), dim3(lds_count), dim3(512), sh, st, P, lds_begin, dA, d_scratch,
-                         d_scratch_off + lds_begin, idx_off, wcap, bperm, yout, dep);
+    if (LL.lds_max_m >= kWideFrontDoubles)
+      hipLaunchKernelGGL((front_factor_kernel<BS, true, 512, VIRT>), dim3(lds_count), dim3(512), sh, st, P, lds_begin, A.dA, d_scratch,
+                         d_scratch_off + lds_begin, idx_off, wcap, A.bperm, A.yout, A.dep);
     else
-      hipLaunchKernelGGL((front_factor_kernel<BS, true, kFactorThreads, VIRT>), dim3(lds_count), dim3(kFactorThreads), sh, st, P, lds_begin, dA, d_scratch,
-                         d_scratch_off + lds_begin, idx_off, wcap, bperm, yout, dep);
+      hipLaunchKernelGGL((front_factor_kernel<BS, true, kFactorThreads, VIRT>), dim3(lds_count), dim3(kFactorThreads), sh, st, P, lds_begin, A.dA, d_scratch,
+                         d_scratch_off + lds_begin, idx_off, wcap, A.bperm, A.yout, A.dep);
     if (hipPeekAtLastError() != hipSuccess)
-      fprintf(stderr, "g2ohip: LDS front launch: %zu bytes of LDS (blocks %d doubles, vectors %d, index tables %d ints)\n", sh, lds_max_m, wcap,
-              lds_idx_ints);
+      fprintf(stderr, "g2ohip: LDS front launch: %zu bytes of LDS (blocks %d doubles, vectors %d, index tables %d ints)\n", sh, LL.lds_max_m, wcap,
+              LL.lds_idx_ints);
     G2OHIP_LAUNCH_CHECK("front_factor_kernel (LDS fronts)");
   }
-  if (!(parts & 2)) return;
-  if (glb_count > 0 && big.ok) {   // large fronts as whole-GPU passes
-    if (big.fz_count > 0 && !big.hoisted) {   // zero the regions that start at this level (a kernel: hipMemsetAsync reaches ~1 TB/s only)
-      hipLaunchKernelGGL(big_fill_kernel, dim3(big.fz_count), dim3(256), 0, st, big.chunks + big.fz_begin, d_scratch, d_scratch_off, big.ld);
+  if (!(A.parts & 2)) return;
+  const int glb_begin = LL.glb_begin, glb_count = LL.glb_count;
+  if (glb_count > 0 && LL.big_passes) {   // large fronts as whole-GPU passes (all ranges index A.big_tiles)
+    if (LL.fz_count > 0 && !LL.hoisted) {   // zero the regions that start at this level (a kernel: hipMemsetAsync reaches ~1 TB/s only)
+      hipLaunchKernelGGL(big_fill_kernel, dim3(LL.fz_count), dim3(256), 0, st, A.big_tiles + LL.fz_begin, d_scratch, d_scratch_off, A.ld);
       G2OHIP_LAUNCH_CHECK("big_fill_kernel");
     }
-    if (big.ba_count > 0 && !big.hoisted)
-      hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(big.ba_count), dim3(256), 0, st, P, big.chunks + big.ba_begin, dA, d_scratch,
-                         d_scratch_off, big.ld);
+    if (LL.ba_count > 0 && !LL.hoisted)   // (hoisted: fill + assembly already done by the phase-wide passes)
+      hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(LL.ba_count), dim3(256), 0, st, P, A.big_tiles + LL.ba_begin, A.dA, d_scratch,
+                         d_scratch_off, A.ld);
     G2OHIP_LAUNCH_CHECK("big_assemble_kernel");
-    const bool level_launch = big.flag && bt_count > 0 && bt_count <= big.merge_tiles;
+    const bool level_launch = A.flag && bt_count > 0 && bt_count <= A.merge_tiles;
     bool any_pass = false;
-    for (const auto& pass : *big.be_pass) any_pass = any_pass || pass.second > 0;
-    const bool gather = level_launch && big.gather && any_pass;   // (the level's launch adds the children's update matrices where it loads the fronts)
-    if (big.eg_write) {   // every child ordinal in one launch, into regions that were not zero-filled; then the original blocks
-      if (big.eg_maxc <= 2)
-        hipLaunchKernelGGL((big_extend_gather_kernel<BS, true, 2>), dim3(big.eg_count), dim3(kEgThreads), 0, st, P, big.chunks + big.eg_begin, d_scratch, d_scratch_off);
+    for (const auto& pass : LL.be_pass) any_pass = any_pass || pass.second > 0;
+    const bool gather = level_launch && LL.gather && any_pass;   // (the level's launch adds the children's update matrices where it loads the fronts)
+    if (LL.eg_write) {   // every child ordinal in one launch, into regions that were not zero-filled; then the original blocks
+      if (LL.eg_maxc <= 2)
+        hipLaunchKernelGGL((big_extend_gather_kernel<BS, true, 2>), dim3(LL.eg_count), dim3(kEgThreads), 0, st, P, A.big_tiles + LL.eg_begin, d_scratch, d_scratch_off);
       else
-        hipLaunchKernelGGL((big_extend_gather_kernel<BS, true, 7>), dim3(big.eg_count), dim3(kEgThreads), 0, st, P, big.chunks + big.eg_begin, d_scratch, d_scratch_off);
+        hipLaunchKernelGGL((big_extend_gather_kernel<BS, true, 7>), dim3(LL.eg_count), dim3(kEgThreads), 0, st, P, A.big_tiles + LL.eg_begin, d_scratch, d_scratch_off);
       G2OHIP_LAUNCH_CHECK("big_extend_gather_kernel");
-      if (big.la_count > 0)
-        hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(big.la_count), dim3(256), 0, st, P, big.chunks + big.la_begin, dA, d_scratch,
-                           d_scratch_off, big.ld);
+      if (LL.la_count > 0)
+        hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(LL.la_count), dim3(256), 0, st, P, A.big_tiles + LL.la_begin, A.dA, d_scratch,
+                           d_scratch_off, A.ld);
       G2OHIP_LAUNCH_CHECK("big_assemble_kernel");
-    } else if (!gather && big.eg_count > 0) {   // every child ordinal in one launch
-      if (big.eg_maxc <= 2)
-        hipLaunchKernelGGL((big_extend_gather_kernel<BS, false, 2>), dim3(big.eg_count), dim3(kEgThreads), 0, st, P, big.chunks + big.eg_begin, d_scratch, d_scratch_off);
+    } else if (!gather && LL.eg_count > 0) {   // every child ordinal in one launch
+      if (LL.eg_maxc <= 2)
+        hipLaunchKernelGGL((big_extend_gather_kernel<BS, false, 2>), dim3(LL.eg_count), dim3(kEgThreads), 0, st, P, A.big_tiles + LL.eg_begin, d_scratch, d_scratch_off);
       else
-        hipLaunchKernelGGL((big_extend_gather_kernel<BS, false, 7>), dim3(big.eg_count), dim3(kEgThreads), 0, st, P, big.chunks + big.eg_begin, d_scratch, d_scratch_off);
+        hipLaunchKernelGGL((big_extend_gather_kernel<BS, false, 7>), dim3(LL.eg_count), dim3(kEgThreads), 0, st, P, A.big_tiles + LL.eg_begin, d_scratch, d_scratch_off);
       G2OHIP_LAUNCH_CHECK("big_extend_gather_kernel");
     } else if (!gather)
-      for (const auto& pass : *big.be_pass)
+      for (const auto& pass : LL.be_pass)   // one extend-add pass per child ordinal
         if (pass.second > 0)
-          hipLaunchKernelGGL((big_extend_add_kernel<BS>), dim3(pass.second), dim3(256), 0, st, P, big.chunks + pass.first, d_scratch,
+          hipLaunchKernelGGL((big_extend_add_kernel<BS>), dim3(pass.second), dim3(256), 0, st, P, A.big_tiles + pass.first, d_scratch,
                              d_scratch_off);
     G2OHIP_LAUNCH_CHECK("big_extend_add_kernel");
     if (level_launch) {
       const size_t shp = (size_t)(3 * 64 * 65 + 64 + 128) * sizeof(double) + (gather ? kGatherInts * sizeof(int) : 0);   // (the pivot-block role needs 4 800 doubles of it)
-#define G2OHIP_BIG_LEVEL(FW_, GA_, B_, Y_)                                                                                                     \
-  hipLaunchKernelGGL((big_level_kernel<BS, FW_, GA_>), dim3(glb_count + bt_count), dim3(256), shp, st, P, glb_begin, glb_count, big_tiles, d_scratch, \
-                     d_scratch_off, big.ld, B_, Y_, big.flag)
-      if (big.fwd && gather) G2OHIP_BIG_LEVEL(true, true, bperm, yout);
-      else if (big.fwd) G2OHIP_BIG_LEVEL(true, false, bperm, yout);
-      else if (gather) G2OHIP_BIG_LEVEL(false, true, (const double*)nullptr, (double*)nullptr);
-      else G2OHIP_BIG_LEVEL(false, false, (const double*)nullptr, (double*)nullptr);
-#undef G2OHIP_BIG_LEVEL
+      with_bool(A.fwd, [&](auto fw) {
+        constexpr bool FW = fw;
+        with_bool(gather, [&](auto ga) {
+          constexpr bool GA = ga;
+          hipLaunchKernelGGL((big_level_kernel<BS, FW, GA>), dim3(glb_count + bt_count), dim3(256), shp, st, P, glb_begin, glb_count, big_tiles, d_scratch,
+                             d_scratch_off, A.ld, FW ? A.bperm : (const double*)nullptr, FW ? A.yout : (double*)nullptr, A.flag);
+        });
+      });
       G2OHIP_LAUNCH_CHECK("big_level_kernel");
       return;
     }
     // (at most kPanelSolveWgs workgroups: each repeats the pivot block on one wave and holds a CU's registers meanwhile -- a level of many
     // fronts is faster with the two separate launches; profiles/r6_grid_sweep.txt)
     constexpr int ps_max = kPanelSolveWgs;
-    if (!big.fwd && big.panel_solve && big.tr_count > 0 && 4 * big.tr_count <= ps_max && bt_count > big.merge_tiles) {
-      // pivot blocks + panel rows in one launch (every front of the level has boundary rows: BigLaunch::panel_solve)
-      hipLaunchKernelGGL((big_panel_solve_kernel<BS>), dim3(4 * big.tr_count), dim3(256), 0, st, P, big.chunks + big.tr_begin, d_scratch,
-                         d_scratch_off, big.ld);
+    if (!A.fwd && LL.tr_all && LL.tr_count > 0 && 4 * LL.tr_count <= ps_max && bt_count > A.merge_tiles) {
+      // pivot blocks + panel rows in one launch (every front of the level has boundary rows: LevelLaunch::tr_all)
+      hipLaunchKernelGGL((big_panel_solve_kernel<BS>), dim3(4 * LL.tr_count), dim3(256), 0, st, P, A.big_tiles + LL.tr_begin, d_scratch,
+                         d_scratch_off, A.ld);
       G2OHIP_LAUNCH_CHECK("big_panel_solve_kernel");
     } else {
-      if (big.fwd)
-        hipLaunchKernelGGL((big_diag_mfma_kernel<BS, true>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, big.ld, bperm, yout);
+      if (A.fwd)
+        hipLaunchKernelGGL((big_diag_mfma_kernel<BS, true>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, A.ld, A.bperm, A.yout);
       else
-        hipLaunchKernelGGL((big_diag_mfma_kernel<BS, false>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, big.ld,
+        hipLaunchKernelGGL((big_diag_mfma_kernel<BS, false>), dim3(glb_count), dim3(256), 0, st, P, glb_begin, d_scratch, d_scratch_off, A.ld,
                            (const double*)nullptr, (double*)nullptr);
       G2OHIP_LAUNCH_CHECK("big_diag_mfma_kernel");
-      if (bt_count <= big.merge_tiles) {   // panel solve + update in one launch -- while the level is a latency chain (at most one
-                                                 // workgroup per CU); a level that fills the GPU pays for the rows solved more than once
+      if (bt_count <= A.merge_tiles) {   // panel solve + update in one launch -- while the level is a latency chain (at most one
+                                         // workgroup per CU); a level that fills the GPU pays for the rows solved more than once
         if (bt_count > 0) {
           const size_t shp = (size_t)(3 * 64 * 65 + 64 + 128) * sizeof(double);
-          if (big.fwd)
-            hipLaunchKernelGGL((big_panel_kernel<BS, true>), dim3(bt_count), dim3(256), shp, st, P, big_tiles, d_scratch, d_scratch_off, big.ld, bperm, yout);
+          if (A.fwd)
+            hipLaunchKernelGGL((big_panel_kernel<BS, true>), dim3(bt_count), dim3(256), shp, st, P, big_tiles, d_scratch, d_scratch_off, A.ld, A.bperm, A.yout);
           else
-            hipLaunchKernelGGL((big_panel_kernel<BS, false>), dim3(bt_count), dim3(256), shp, st, P, big_tiles, d_scratch, d_scratch_off, big.ld,
+            hipLaunchKernelGGL((big_panel_kernel<BS, false>), dim3(bt_count), dim3(256), shp, st, P, big_tiles, d_scratch, d_scratch_off, A.ld,
                                (const double*)nullptr, (double*)nullptr);
           G2OHIP_LAUNCH_CHECK("big_panel_kernel");
         }
         return;
       }
-      if (big.tr_count > 0)
-        hipLaunchKernelGGL((big_trsm_kernel<BS>), dim3(big.tr_count), dim3(256), 0, st, P, big.chunks + big.tr_begin, d_scratch,
-                           d_scratch_off, big.ld);
+      if (LL.tr_count > 0)
+        hipLaunchKernelGGL((big_trsm_kernel<BS>), dim3(LL.tr_count), dim3(256), 0, st, P, A.big_tiles + LL.tr_begin, d_scratch,
+                           d_scratch_off, A.ld);
       G2OHIP_LAUNCH_CHECK("big_trsm_kernel");
     }
     if (bt_count > 0)
@@ -3042,18 +3041,18 @@ void launch_factor_level(const CholPlanDev& P, const int* d_tasks, const long lo
       // (a launch that fills the GPU several times over is served better by four waves per SIMD than by one round trip per panel:
       // 116 against 180 registers; 16.5 -> 16.3 / 80.8 -> 79.4 ms on the grid graphs, profiles/r6_grid_sweep.txt)
       constexpr int ks_split = 4096;
-      if (bt_count > ks_split) hipLaunchKernelGGL((big_front_update_kernel<BS, 6>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, big.ld);
-      else hipLaunchKernelGGL((big_front_update_kernel<BS, 15>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, big.ld);
+      if (bt_count > ks_split) hipLaunchKernelGGL((big_front_update_kernel<BS, 6>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, A.ld);
+      else hipLaunchKernelGGL((big_front_update_kernel<BS, 15>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, A.ld);
     }
     G2OHIP_LAUNCH_CHECK("big_front_update_kernel");
   } else if (glb_count > 0) {
     const int idx_off = 2 * (BS * BS + BS);
-    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(glb_idx_ints + 4) * sizeof(int);
-    hipLaunchKernelGGL((front_factor_kernel<BS, false, kFactorThreadsGlobal, VIRT>), dim3(glb_count), dim3(kFactorThreadsGlobal), sh, st, P, glb_begin, dA,
+    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(LL.glb_idx_ints + 4) * sizeof(int);
+    hipLaunchKernelGGL((front_factor_kernel<BS, false, kFactorThreadsGlobal, VIRT>), dim3(glb_count), dim3(kFactorThreadsGlobal), sh, st, P, glb_begin, A.dA,
                        d_scratch, d_scratch_off + glb_begin, idx_off, 0, (const double*)nullptr, (double*)nullptr, 0);
     G2OHIP_LAUNCH_CHECK("front_factor_kernel");
     if (bt_count > 0)   // their trailing matrices: one MFMA pass over all of them
-      hipLaunchKernelGGL((big_front_update_kernel<BS>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, big.ld);
+      hipLaunchKernelGGL((big_front_update_kernel<BS>), dim3(bt_count), dim3(256), 0, st, P, big_tiles, d_scratch, d_scratch_off, A.ld);
     G2OHIP_LAUNCH_CHECK("big_front_update_kernel");
   }
 }
@@ -3137,32 +3136,18 @@ void SparseCholesky::launch_factor(const LevelLaunch& LL, const double* dA, bool
 #endif
   CholPlanDev fplan = plan_;
   fplan.slots = d_fslots.p;
-  const BigLaunch big{LL.big_passes, d_big_tiles.p, LL.ba_begin, LL.ba_count, LL.tr_begin, LL.tr_count, &LL.be_pass,
-                      LL.fz_begin, LL.fz_count, LL.hoisted, fwd && big_forward_carried(LL),
-                      !dep_off_ ? d_sw_flag.p : (int*)nullptr, d_scratch_ld.p, merge_tiles_of(LL), LL.gather,
-                      LL.eg_begin, LL.eg_count, LL.eg_write, LL.eg_maxc, LL.la_begin, LL.la_count, LL.tr_all};
   const bool virt = dA == nullptr;   // assemble from the virtual source (set_virtual_blocks)
   if (virt && !has_virtual_blocks()) throw StateFailure("SparseCholesky::factor: no matrix and no virtual source");
-#define G2OHIP_FACTOR_LEVEL(BS_, V_)                                                                                          \
-  launch_factor_level<BS_, V_>(fplan, d_level_fronts.p, d_scratch_off.p, d_scratch.p, dA, LL.lds_begin, LL.lds_count, LL.lds_max_m, \
-                               LL.glb_begin, LL.glb_count, LL.lds_idx_ints, LL.glb_idx_ints, LL.sm_count, LL.sm_max_m,            \
-                               LL.sm_idx_ints, LL.lds_vec_m, fwd ? d_xp.p : (const double*)nullptr, fwd ? d_y.p : (double*)nullptr,   \
-                               dep ? 1 : 0, d_big_tiles.p + LL.bt_begin, LL.bt_count, big, kWideFrontDoubles, LL.wv, LL.wv_pn,   \
-                               LL.wv_idx_ints, st, parts)
-  switch (bs_) {
-    case 3:
-      if (virt) G2OHIP_FACTOR_LEVEL(3, true); else G2OHIP_FACTOR_LEVEL(3, false);
-      break;
-    case 6:
-      if (virt) G2OHIP_FACTOR_LEVEL(6, true); else G2OHIP_FACTOR_LEVEL(6, false);
-      break;
-    case 7:
-      if (virt) G2OHIP_FACTOR_LEVEL(7, true); else G2OHIP_FACTOR_LEVEL(7, false);
-      break;
-    default:
-      throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-  }
-#undef G2OHIP_FACTOR_LEVEL
+  const FactorArgs A{d_scratch_off.p, d_scratch.p, d_big_tiles.p, d_scratch_ld.p, dA, fwd ? d_xp.p : (const double*)nullptr,
+                     fwd ? d_y.p : (double*)nullptr, dep ? 1 : 0, !dep_off_ ? d_sw_flag.p : (int*)nullptr,
+                     fwd && big_forward_carried(LL), merge_tiles_of(LL), st, parts};
+  with_block_size(bs_, [&](auto bs) {
+    constexpr int BS = bs;
+    with_bool(virt, [&](auto v) {
+      constexpr bool VIRT = v;
+      launch_factor_level<BS, VIRT>(fplan, LL, A);
+    });
+  });
 }
 
 bool SparseCholesky::band_usable(const FactorGroup& G, const double* dA) const {
@@ -3200,42 +3185,21 @@ void SparseCholesky::prepare_kernels() {
   static bool attr_done = false;
   if (!attr_done) {
     // allow > 64 KiB dynamic LDS for the LDS-resident front kernels
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true, kFactorThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<3, true, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true, kFactorThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<6, true, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true, kFactorThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)front_factor_kernel<7, true, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<6, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_panel_kernel<7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<3, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<6, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<6, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<7, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<3, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<6, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<6, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)big_level_kernel<7, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    for_each_value<3, 6, 7>([](auto bs) {
+      constexpr int BS = bs;
+      for_each_value<0, 1>([](auto v) {
+        constexpr bool V = v != 0;   // (VIRT of the front kernels, FWD of the panel / level kernels)
+        for_each_value<kFactorThreads, 128, 512>([](auto nt) {
+          constexpr int NT = nt;
+          (void)hipFuncSetAttribute((const void*)front_factor_kernel<BS, true, NT, V>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+        (void)hipFuncSetAttribute((const void*)big_panel_kernel<BS, V>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        for_each_value<0, 1>([](auto ga) {
+          constexpr bool GA = ga != 0;
+          (void)hipFuncSetAttribute((const void*)big_level_kernel<BS, V, GA>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        });
+      });
+    });
     (void)hipGetLastError();
     attr_done = true;
   }
@@ -3267,16 +3231,13 @@ void SparseCholesky::factor_phase(const double* dA, int phase, hipStream_t st, b
       const int4* ch = d_big_tiles.p + hplan_.ha_begin[phase];
       CholPlanDev fplan = plan_;
       fplan.slots = d_fslots.p;   // (as launch_factor)
-#define G2OHIP_HOIST_ASM(BS_)                                                                                                    \
-  if (virt) hipLaunchKernelGGL((big_assemble_kernel<BS_, true>), dim3(hplan_.ha_count[phase]), dim3(256), 0, st, fplan, ch, dA, d_scratch.p, d_scratch_off.p, d_scratch_ld.p); \
-  else hipLaunchKernelGGL((big_assemble_kernel<BS_, false>), dim3(hplan_.ha_count[phase]), dim3(256), 0, st, fplan, ch, dA, d_scratch.p, d_scratch_off.p, d_scratch_ld.p)
-      switch (bs_) {
-        case 3: G2OHIP_HOIST_ASM(3); break;
-        case 6: G2OHIP_HOIST_ASM(6); break;
-        case 7: G2OHIP_HOIST_ASM(7); break;
-        default: throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-      }
-#undef G2OHIP_HOIST_ASM
+      with_block_size(bs_, [&](auto bs) {
+        constexpr int BS = bs;
+        with_bool(virt, [&](auto v) {
+          constexpr bool VIRT = v;
+          hipLaunchKernelGGL((big_assemble_kernel<BS, VIRT>), dim3(hplan_.ha_count[phase]), dim3(256), 0, st, fplan, ch, dA, d_scratch.p, d_scratch_off.p, d_scratch_ld.p);
+        });
+      });
       G2OHIP_LAUNCH_CHECK("big_assemble_kernel");
     }
   }
@@ -3632,16 +3593,11 @@ void SparseCholesky::launch_solve(const LevelLaunch& LL, bool fwd, hipStream_t s
     // the scratch-slab fronts of the level: several workgroups per front; the LDS / register fronts (independent of
     // them: same level) follow in their own launch, sized for themselves
     const int4* ch = d_big_tiles.p + LL.sw_begin;
-#define G2OHIP_SPLIT_SWEEP(BS_)                                                                                                 \
-  if (fwd) hipLaunchKernelGGL((big_forward_kernel<BS_>), dim3(LL.sw_count), dim3(256), 0, st, plan_, ch, d_xp.p, d_y.p);          \
-  else hipLaunchKernelGGL((big_backward_kernel<BS_, false>), dim3(LL.sw_count), dim3(256), 0, st, plan_, ch, d_y.p, d_xp.p, d_sw_part.p, d_sw_cnt.p, (int*)nullptr)
-    switch (bs_) {
-      case 3: G2OHIP_SPLIT_SWEEP(3); break;
-      case 6: G2OHIP_SPLIT_SWEEP(6); break;
-      case 7: G2OHIP_SPLIT_SWEEP(7); break;
-      default: throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-    }
-#undef G2OHIP_SPLIT_SWEEP
+    with_block_size(bs_, [&](auto bs) {
+      constexpr int BS = bs;
+      if (fwd) hipLaunchKernelGGL((big_forward_kernel<BS>), dim3(LL.sw_count), dim3(256), 0, st, plan_, ch, d_xp.p, d_y.p);
+      else hipLaunchKernelGGL((big_backward_kernel<BS, false>), dim3(LL.sw_count), dim3(256), 0, st, plan_, ch, d_y.p, d_xp.p, d_sw_part.p, d_sw_cnt.p, (int*)nullptr);
+    });
     G2OHIP_LAUNCH_CHECK("big_forward_kernel / big_backward_kernel");
     if (glb_only || LL.lds_count == 0) return;
     count = LL.lds_count;
@@ -3663,43 +3619,35 @@ void SparseCholesky::launch_solve(const LevelLaunch& LL, bool fwd, hipStream_t s
   if (sh > 64 * 1024) {   // (fronts of several thousand rows: dense couplings, e.g. a landmark seen by hundreds of poses)
     static bool attr_done = false;
     if (!attr_done) {
-#define G2OHIP_SWEEP_ATTR(BS_)                                                                                                 \
-  (void)hipFuncSetAttribute((const void*)front_forward_kernel<BS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-  (void)hipFuncSetAttribute((const void*)front_forward_kernel<BS_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  (void)hipFuncSetAttribute((const void*)front_backward_kernel<BS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  (void)hipFuncSetAttribute((const void*)front_backward_kernel<BS_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      G2OHIP_SWEEP_ATTR(3);
-      G2OHIP_SWEEP_ATTR(6);
-      G2OHIP_SWEEP_ATTR(7);
-#undef G2OHIP_SWEEP_ATTR
+      for_each_value<3, 6, 7>([](auto bs) {
+        constexpr int BS = bs;
+        for_each_value<0, 1>([](auto pn) {
+          constexpr bool PANEL = pn != 0;
+          (void)hipFuncSetAttribute((const void*)front_forward_kernel<BS, PANEL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          (void)hipFuncSetAttribute((const void*)front_backward_kernel<BS, PANEL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+      });
       (void)hipGetLastError();
       attr_done = true;
     }
   }
-#define G2OHIP_SOLVE_LAUNCH(BS_)                                                                                              \
-  if (gvec) {   /* (fronts beyond the LDS limit: never with a staged panel) */                                                \
-    if (fwd)                                                                                                                  \
-      hipLaunchKernelGGL((front_forward_kernel<BS_, false, true>), dim3(count), dim3(nthreads), sh, st, plan_, slot0, d_xp.p, d_y.p, 0, max_m, gvec); \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((front_backward_kernel<BS_, false, true>), dim3(count), dim3(nthreads), sh, st, bplan, slot0, d_y.p, d_xp.p, 0, max_m, depi, gvec); \
-  } else if (fwd) {                                                                                                           \
-    if (panel)                                                                                                                \
-      hipLaunchKernelGGL((front_forward_kernel<BS_, true>), dim3(count), dim3(nthreads), sh, st, plan_, slot0, d_xp.p, d_y.p, cap, max_m, gvec);  \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((front_forward_kernel<BS_, false>), dim3(count), dim3(nthreads), sh, st, plan_, slot0, d_xp.p, d_y.p, cap, max_m, gvec); \
-  } else {                                                                                                                    \
-    if (panel)                                                                                                                \
-      hipLaunchKernelGGL((front_backward_kernel<BS_, true>), dim3(count), dim3(nthreads), sh, st, bplan, slot0, d_y.p, d_xp.p, cap, max_m, depi, gvec); \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((front_backward_kernel<BS_, false>), dim3(count), dim3(nthreads), sh, st, bplan, slot0, d_y.p, d_xp.p, cap, max_m, depi, gvec); \
-  }
-  switch (bs_) {
-    case 3: G2OHIP_SOLVE_LAUNCH(3) break;
-    case 6: G2OHIP_SOLVE_LAUNCH(6) break;
-    case 7: G2OHIP_SOLVE_LAUNCH(7) break;
-    default: throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-  }
-#undef G2OHIP_SOLVE_LAUNCH
+  with_block_size(bs_, [&](auto bs) {
+    constexpr int BS = bs;
+    if (gvec) {   // (fronts beyond the LDS limit: never with a staged panel)
+      if (fwd)
+        hipLaunchKernelGGL((front_forward_kernel<BS, false, true>), dim3(count), dim3(nthreads), sh, st, plan_, slot0, d_xp.p, d_y.p, 0, max_m, gvec);
+      else
+        hipLaunchKernelGGL((front_backward_kernel<BS, false, true>), dim3(count), dim3(nthreads), sh, st, bplan, slot0, d_y.p, d_xp.p, 0, max_m, depi, gvec);
+      return;
+    }
+    with_bool(panel, [&](auto pn) {
+      constexpr bool PANEL = pn;
+      if (fwd)
+        hipLaunchKernelGGL((front_forward_kernel<BS, PANEL>), dim3(count), dim3(nthreads), sh, st, plan_, slot0, d_xp.p, d_y.p, cap, max_m, gvec);
+      else
+        hipLaunchKernelGGL((front_backward_kernel<BS, PANEL>), dim3(count), dim3(nthreads), sh, st, bplan, slot0, d_y.p, d_xp.p, cap, max_m, depi, gvec);
+    });
+  });
 }
 
 void SparseCholesky::solve_begin(const double* d_b, hipStream_t st) {
@@ -3722,15 +3670,10 @@ void SparseCholesky::solve_backward_phase(int phase, hipStream_t st) {
       if (G.tb_ngrp > 0) {   // the tree levels by groups of fronts, then the levels below them task by task
         const int nt_ref = G.LL.max_m <= 64 ? 64 : (G.LL.max_m <= 128 ? 128 : 256);   // (launch_solve's workgroup size: bw_parts)
         const TreeGroupRec* gr = reinterpret_cast<const TreeGroupRec*>(d_tb_grec.p) + G.tb_grp0;
-#define G2OHIP_TREE_BACKWARD(BS_) \
-  hipLaunchKernelGGL((tree_backward_kernel<BS_>), dim3(G.tb_ngrp), dim3(kTreeWaves * 64), 0, st, plan_, gr, d_tb_front.p, d_tb_rows.p, d_y.p, d_xp.p, nt_ref)
-        switch (bs_) {
-          case 3: G2OHIP_TREE_BACKWARD(3); break;
-          case 6: G2OHIP_TREE_BACKWARD(6); break;
-          case 7: G2OHIP_TREE_BACKWARD(7); break;
-          default: throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-        }
-#undef G2OHIP_TREE_BACKWARD
+        with_block_size(bs_, [&](auto bs) {
+          constexpr int BS = bs;
+          hipLaunchKernelGGL((tree_backward_kernel<BS>), dim3(G.tb_ngrp), dim3(kTreeWaves * 64), 0, st, plan_, gr, d_tb_front.p, d_tb_rows.p, d_y.p, d_xp.p, nt_ref);
+        });
         G2OHIP_LAUNCH_CHECK("tree_backward_kernel");
         if (G.tb_low > 0) {
           launch_solve(G.LL, false, st, false, true, false, G.tb_low);
@@ -3749,15 +3692,10 @@ void SparseCholesky::solve_backward_phase(int phase, hipStream_t st) {
             flags_zeroed = true;
           }
           const int4* ch = d_big_tiles.p + B.begin;
-#define G2OHIP_MERGED_BACKWARD(BS_) \
-  hipLaunchKernelGGL((big_backward_kernel<BS_, true>), dim3(B.count), dim3(256), 0, st, plan_, ch, d_y.p, d_xp.p, d_sw_part.p, d_sw_cnt.p, d_sw_flag.p)
-          switch (bs_) {
-            case 3: G2OHIP_MERGED_BACKWARD(3); break;
-            case 6: G2OHIP_MERGED_BACKWARD(6); break;
-            case 7: G2OHIP_MERGED_BACKWARD(7); break;
-            default: throw ArgFailure("SparseCholesky: unsupported block size (3, 6, 7)");
-          }
-#undef G2OHIP_MERGED_BACKWARD
+          with_block_size(bs_, [&](auto bs) {
+            constexpr int BS = bs;
+            hipLaunchKernelGGL((big_backward_kernel<BS, true>), dim3(B.count), dim3(256), 0, st, plan_, ch, d_y.p, d_xp.p, d_sw_part.p, d_sw_cnt.p, d_sw_flag.p);
+          });
           G2OHIP_LAUNCH_CHECK("big_backward_kernel (merged levels)");
           continue;
         }

@@ -532,54 +532,126 @@ def test_sharded_path_single_rank_rccl():
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("p,l,d", [(7, 3, 2), (7, 3, 3), (3, 2, 2), (3, 2, 1), (6, 3, 3), (6, 3, 1)])
-def test_block_solver_dimension_families(p, l, d):
-    """The fixed-size solver families of the reference (BlockSolver_7_3 / _3_2 / _6_3, block_solver.h:163-175) with the
-    edge shapes its type libraries produce for them: sim3 projections (d=2/3 on 7-dof poses, types_seven_dof_expmap.h),
-    SE2 landmark observations (d=2) and bearings (d=1, types_slam2d), 3D point observations (d=3) and depth-only (d=1).
-    Random Jacobians / information through the generic edge-data path, Schur on, against the oracle."""
+def _dimension_family(p, l, d, pose_d=(), prior_d=0, schur=True):
+    """One case of test_block_solver_dimension_families: 40 poses, 150 landmarks.  Edge sets: landmark observations of error
+    dimension d (Schur only), a chain of pose-pose edges of full dimension, further pose-pose sets of the error dimensions
+    pose_d (pose k -- pose k + 2, k + 3, ...) and, for prior_d > 0, unary edges of that error dimension on every landmark."""
     capi = _capi()
     rng = np.random.default_rng(100 * p + 10 * l + d)
-    nP, nL, K = 40, 150, 4 if d > 1 else 6
-    pt = np.repeat(np.arange(nL), K)
-    cam = (rng.integers(0, nP - K, size=nL)[:, None] + np.arange(K)[None, :]).reshape(-1)
-    cam[rng.random(len(cam)) < 0.03] = -1                         # a few observations from fixed poses
-    v0, v1 = (nP + pt).astype(np.int32), cam.astype(np.int32)
-    E = len(v0)
-    J0, J1 = rng.normal(size=(E, d * l)), rng.normal(size=(E, d * p))
-    W = rng.normal(size=(E, d, d))
-    om = (W @ W.transpose(0, 2, 1) + d * np.eye(d)).reshape(E, d * d)
-    err = rng.normal(size=(E, d))
+    nP, nL, K = 40, 150 if schur else 0, 4 if d > 1 else 6
+
+    def spd(n, m):
+        W = rng.normal(size=(n, m, m))
+        return (W @ W.transpose(0, 2, 1) + m * np.eye(m)).reshape(n, m * m)
+
+    sets = []   # (error dim, v0, v1, dim0, dim1, J0, J1, omega, err, huber delta)
+    if schur:
+        pt = np.repeat(np.arange(nL), K)
+        cam = (rng.integers(0, nP - K, size=nL)[:, None] + np.arange(K)[None, :]).reshape(-1)
+        cam[rng.random(len(cam)) < 0.03] = -1                         # a few observations from fixed poses
+        v0, v1 = (nP + pt).astype(np.int32), cam.astype(np.int32)
+        E = len(v0)
+        J0, J1 = rng.normal(size=(E, d * l)), rng.normal(size=(E, d * p))
+        om = spd(E, d)
+        sets.append((d, v0, v1, l, p, J0, J1, om, rng.normal(size=(E, d)), 1.5))
     # pose-pose edges of full dimension keep the pose system connected (EdgeSim3 / EdgeSE2 / EdgeSE3)
-    a, b = np.arange(0, nP - 1, dtype=np.int32), np.arange(1, nP, dtype=np.int32)
-    JA, JB = rng.normal(size=(nP - 1, p * p)), rng.normal(size=(nP - 1, p * p))
-    W2 = rng.normal(size=(nP - 1, p, p))
-    O2 = (W2 @ W2.transpose(0, 2, 1) + p * np.eye(p)).reshape(nP - 1, p * p)
-    e2 = rng.normal(size=(nP - 1, p))
+    for step, dd in enumerate((p,) + tuple(pose_d), 1):
+        a, b = np.arange(0, nP - step, dtype=np.int32), np.arange(step, nP, dtype=np.int32)
+        n = len(a)
+        JA, JB = rng.normal(size=(n, dd * p)), rng.normal(size=(n, dd * p))
+        O2 = spd(n, dd)
+        sets.append((dd, a, b, p, p, JA, JB, O2, rng.normal(size=(n, dd)), 0.0))
+    if prior_d:
+        u = (nP + np.arange(nL)).astype(np.int32)
+        sets.append((prior_d, u, None, l, 0, rng.normal(size=(nL, prior_d * l)), None, spd(nL, prior_d), rng.normal(size=(nL, prior_d)), 0.0))
     s = capi.HipBlockSolver(p, l, 0)
-    k0, k1 = s.addEdgeSet(d, v0, v1), s.addEdgeSet(p, a, b)
-    s.buildStructure(nP, nL, True)
-    s.setEdgeData(k0, J0, J1, om, err)
-    s.setEdgeData(k1, JA, JB, O2, e2)
-    s.setRobustKernel(k0, capi.KERNEL_HUBER, 1.5)
-    o = O.OracleSolver(p, l, nP, nL, True)
-    q0 = o.add_edge_set(d, v0, v1); o.set_dims(q0, l, p)
-    q1 = o.add_edge_set(p, a, b); o.set_dims(q1, p, p)
+    ks = [s.addEdgeSet(dd, v0, v1) for dd, v0, v1, *_ in sets]
+    s.buildStructure(nP, nL, schur)
+    o = O.OracleSolver(p, l, nP, nL, schur)
+    qs = []
+    for dd, v0, v1, dim0, dim1, *_ in sets:
+        qs.append(o.add_edge_set(dd, v0, v1))
+        o.set_dims(qs[-1], dim0, dim1)
     o.build_structure()
-    o.set_edge_data(q0, J0, J1, om, err, 1.5)
-    o.set_edge_data(q1, JA, JB, O2, e2)
+    for k, q, (dd, v0, v1, dim0, dim1, J0, J1, om, err, delta) in zip(ks, qs, sets):
+        s.setEdgeData(k, J0, J1, om, err)
+        if delta:
+            s.setRobustKernel(k, capi.KERNEL_HUBER, delta)
+            o.set_edge_data(q, J0, J1, om, err, delta)
+        else:
+            o.set_edge_data(q, J0, J1, om, err)
     s.buildSystem()
     o.build_system()
-    _cmp_system(s, o, capi)
+    if schur:
+        _cmp_system(s, o, capi)
+    else:
+        assert relerr(s.values(capi.HPP), o.values("Hpp")) < TOL_MAT
+        assert relerr(s.b(), o.b()) < TOL_MAT
     assert abs(s.chi2() - o.chi2()) <= 1e-12 * o.chi2()
     lam = 1e-3 * o.max_diagonal()
     s.setLambda(lam, True)
     o.set_lambda(lam, True)
     assert s.solve() and o.solve()
-    assert relerr(s.values(capi.HSCHUR), o.values("Hschur")) < TOL_MAT
+    if schur:
+        assert relerr(s.values(capi.HSCHUR), o.values("Hschur")) < TOL_MAT
     assert relerr(s.x(), o.x()) < 1e-9
     r = s.multiplyHessian(s.x()) - s.b()
     assert np.abs(r).max() <= TOL_RES * np.abs(s.b()).max()
+
+
+@pytest.mark.parametrize("p,l,d", [(7, 3, 2), (7, 3, 3), (3, 2, 2), (3, 2, 1), (6, 3, 3), (6, 3, 1), (6, 3, 2), (3, 3, 2)])
+def test_block_solver_dimension_families(p, l, d):
+    """The fixed-size solver families of the reference (BlockSolver_7_3 / _3_2 / _6_3, block_solver.h:163-175) with the
+    edge shapes its type libraries produce for them: sim3 projections (d=2/3 on 7-dof poses, types_seven_dof_expmap.h),
+    SE2 landmark observations (d=2) and bearings (d=1, types_slam2d), 3D point observations (d=3) and depth-only (d=1),
+    projections onto 6-dof poses (d=2) and the (3, 3) family.
+    Random Jacobians / information through the generic edge-data path, Schur on, against the oracle."""
+    _dimension_family(p, l, d)
+
+
+@pytest.mark.parametrize("p,l,d,pose_d,prior_d,schur", [(6, 3, 2, (2, 3), 0, False), (3, 2, 2, (2,), 0, False), (3, 2, 2, (), 3, True)],
+                         ids=["6-pose_d23-noschur", "3-pose_d2-noschur", "3-2-2-prior3"])
+def test_block_solver_dimension_families_table_rows(p, l, d, pose_d, prior_d, schur):
+    """The rows of the assembly tables the families above do not reach: pose-pose edges of an error dimension below the pose
+    dimension (off-diagonal shapes (2,6,6), (3,6,6), (2,3,3): no Schur complement, poses only) and unary edges of error
+    dimension 3 on 2D landmarks (vertex row (3,2)).  With the cases above, every row of dispatch_vertex and dispatch_offdiag,
+    every chi2 dimension and the Schur pairs (6,3), (3,2), (7,3), (3,3) are launched at least once.  Not reachable through the
+    edge-set interface: the Schur pair (6,2) -- no off-diagonal row (d,6,2) exists, so no pose-landmark set of it can be assembled."""
+    _dimension_family(p, l, d, pose_d, prior_d, schur)
+
+
+def test_unsupported_shapes_are_argument_errors():
+    """A shape outside the assembly tables comes back as G2OHIP_ERR_ARG (-1) with the table's message, and the handle stays usable.
+    (The block-size messages of the Cholesky / PCG launches cannot be reached through the C ABI: g2ohip_create and g2ohip_ls_create
+    refuse a dimension other than 3, 6, 7.)"""
+    capi = _capi()
+    rng = np.random.default_rng(11)
+    nP = 6
+    a, b = np.arange(0, nP - 1, dtype=np.int32), np.arange(1, nP, dtype=np.int32)
+
+    def pose_solver(p, d):
+        s = capi.HipBlockSolver(p, 2 if p == 3 else 3, 0)
+        k = s.addEdgeSet(d, a, b)
+        s.buildStructure(nP, 0, False)
+        s.setEdgeData(k, rng.normal(size=(nP - 1, d * p)), rng.normal(size=(nP - 1, d * p)), np.tile(np.eye(d).reshape(-1), (nP - 1, 1)),
+                      rng.normal(size=(nP - 1, d)))
+        return s
+
+    def message(call):
+        with pytest.raises(capi.G2oHipError) as e:
+            call()
+        assert "(-1)" in str(e.value)
+        return str(e.value)
+
+    s = pose_solver(6, 4)
+    assert "chi2: unsupported error dimension" in message(s.chi2)
+    assert "unsupported (error_dim, vertex_dim) = (4,6)" in message(s.buildSystem)
+    s = pose_solver(3, 1)   # the vertex row (1,3) exists, the pose-pose off-diagonal shape (1,3,3) does not
+    assert "unsupported off-diagonal block shape (d,rows,cols) = (1,3,3)" in message(s.buildSystem)
+    s = pose_solver(3, 3)
+    s.buildSystem()
+    s.setLambda(1.0, True)
+    assert s.solve()
 
 
 def test_dependency_driven_launches_and_stall_fallback():
