@@ -241,7 +241,8 @@ int g2ohip_trial_stats(g2ohip_solver* s, double lambda, int* solve_ok, double* c
  * Block solver: "schur_tile_bytes" (39936: LDS budget of one Schur tile), "fuse_schur_reduce" (1: g2ohip_solve on
  * one GPU folds the Schur reduction into the factorisation; Hschur is then written only when it is asked for),
  * "ba_fused" (1: the BA edge set's errors and Jacobians evaluated inside the assembly kernels), "ba_fuse_landmarks" (1: the
- * landmark side of the fused BA path assembled by the Schur tiles of the solve), "use_graph" (0), "mask_solution" (1),
+ * landmark side of the fused BA path assembled by the Schur tiles of the solve), "pg_landmark_staged" (1: the landmark linearize
+ * kernels of the pose-graph front end store through LDS; 0: one lane per edge, for the comparison), "use_graph" (0), "mask_solution" (1),
  * "marginals_reduced" (0) / "marginals_recursion" (1) (see g2ohip_compute_marginals), "setup_overlap" (1: the symbolic
  * analysis next to the Schur tiles' set-up), "pcg_check_every" (16: PCG iterations between looks at the convergence flag),
  * "sharded_graph" (1: g2ohip_solve_sharded as one hipGraph where nothing crosses the host; 2: with RCCL too),

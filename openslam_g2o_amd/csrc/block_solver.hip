@@ -5571,15 +5571,6 @@ void BlockSolver::pg_discard_top() {
   pg_.has_backup = false;
 }
 
-// Blocks (rows[i], cols[i]) of the inverse of the system the linear solver factorises (Hpp without Schur, the reduced
-// pose system with it: the pose marginals with the landmarks integrated out).  One factorisation, then a pair of
-// triangular sweeps per requested scalar column.  Replaces BlockSolver::computeMarginals -> LinearSolver::solvePattern
-// (block_solver.hpp:489-498, linear_solver.h:63-69, marginal_covariance_cholesky.cpp:71-220 computes the same entries
-// by recursion on the factor).
-__global__ void set_unit_kernel(double* __restrict__ v, size_t n, size_t k) {
-  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (i < n) v[i] = (i == k) ? 1.0 : 0.0;
-}
 // Hpp (+ lambda on the diagonal of the diagonal blocks) laid out on the pattern of Hschur, which the factorisation was
 // analysed for (a superset of Hpp's pattern): the matrix BlockSolver::computeMarginals hands to solvePattern
 __global__ void hpp_on_schur_pattern_kernel(size_t n, int bb, int pd, const int* __restrict__ hs_src, const int* __restrict__ hs_diag,
@@ -5593,16 +5584,10 @@ __global__ void hpp_on_schur_pattern_kernel(size_t n, int bb, int pd, const int*
   Hs[t] = v;
 }
 
-// block i of the output <- block at off[i] of the sparse-inverse slab (leading dimension ld[i], transposed if tr[i])
-__global__ void gather_inverse_blocks_kernel(int n, int p, const long long* __restrict__ off, const int* __restrict__ ld,
-                                             const int* __restrict__ tr, const double* __restrict__ Z, double* __restrict__ out) {
-  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * p * p) return;
-  const int b = (int)(t / (p * p)), e = (int)(t % (p * p)), i = e % p, j = e / p;
-  if (off[b] < 0) return;
-  out[t] = tr[b] ? Z[off[b] + j + (long long)ld[b] * i] : Z[off[b] + i + (long long)ld[b] * j];
-}
-
+// Blocks (rows[i], cols[i]) of the inverse of the system the linear solver factorises (Hpp without Schur, the reduced
+// pose system with it: the pose marginals with the landmarks integrated out).  One factorisation, then
+// SparseCholesky::inverse_blocks.  Replaces BlockSolver::computeMarginals -> LinearSolver::solvePattern
+// (block_solver.hpp:489-498, linear_solver.h:63-69).
 int BlockSolver::compute_marginals(int n, const int* rows, const int* cols, double* out) {
   require_structure();
   if (!system_built_) throw StateFailure("compute_marginals before build_system");
@@ -5622,77 +5607,15 @@ int BlockSolver::compute_marginals(int n, const int* rows, const int* cols, doub
     hschur_valid_ = false;    // d_Hschur no longer holds the reduced system
   }
   const double* H = schur_ ? d_Hschur.p : d_Hpp.p;
-  chol_->factor(H, st_);
-  if (chol_->failed(st_)) {
-    // a dependency-driven launch that gave up waiting is not "not positive definite": the factorisation has switched to
-    // one launch per level -- once more (as g2ohip_solve does)
-    if (!(chol_->dependency_stall() && ++dependency_fallbacks)) return 1;
-    invalidate_graphs();
+  const bool ok = chol_->factor_checked([&](bool again) {
+    if (again) {   // (as g2ohip_solve does)
+      ++dependency_fallbacks;
+      invalidate_graphs();
+    }
     chol_->factor(H, st_);
-    if (chol_->failed(st_)) return 1;
-  }
-  // Blocks inside the pattern of the factor: one top-down pass over the frontal matrices gives ALL of them (sparse
-  // inverse); what lies outside the pattern (fill-free pairs of distant poses) falls back to a pair of triangular
-  // sweeps per requested column.
-  std::vector<char> done(n, 0);
-  if (marginals_recursion && chol_opt.world == 1 && n > 0) {
-    chol_->sparse_inverse(st_);
-    std::vector<long long> off(n, -1);
-    std::vector<int> ldv(n, 0), trv(n, 0);
-    int found = 0;
-    for (int i = 0; i < n; ++i) {
-      bool tr = false;
-      if (chol_->inverse_block(rows[i], cols[i], &off[i], &ldv[i], &tr)) {
-        trv[i] = tr ? 1 : 0;
-        done[i] = 1;
-        ++found;
-      } else {
-        off[i] = -1;
-      }
-    }
-    if (found > 0) {
-      DevBuf<long long> d_off;
-      DevBuf<int> d_ld, d_tr;
-      DevBuf<double> d_out;
-      d_off.upload(off, st_);
-      d_ld.upload(ldv, st_);
-      d_tr.upload(trv, st_);
-      d_out.alloc((size_t)n * p_ * p_);
-      hipLaunchKernelGGL(gather_inverse_blocks_kernel, dim3(grid_for((size_t)n * p_ * p_)), dim3(kThreads), 0, st_, n, p_, d_off.p, d_ld.p,
-                         d_tr.p, chol_->inverse_slab(), d_out.p);
-      std::vector<double> ho((size_t)n * p_ * p_);
-      d_out.download(ho.data(), ho.size(), st_);
-      for (int i = 0; i < n; ++i)
-        if (done[i]) std::copy(ho.begin() + (size_t)i * p_ * p_, ho.begin() + (size_t)(i + 1) * p_ * p_, out + (size_t)i * p_ * p_);
-    }
-    if (found == n) return 0;
-  }
-  const size_t np = (size_t)nP_ * p_;
-  DevBuf<double> rhs, sol;
-  rhs.alloc(np);
-  sol.alloc(np);
-  std::vector<double> h(np);
-  std::vector<int> order;
-  for (int i = 0; i < n; ++i)
-    if (!done[i]) order.push_back(i);
-  n = (int)order.size();
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cols[a] < cols[b]; });
-  for (int i = 0; i < n;) {
-    const int c = cols[order[i]];
-    int i1 = i;
-    while (i1 < n && cols[order[i1]] == c) ++i1;
-    for (int k = 0; k < p_; ++k) {
-      hipLaunchKernelGGL(set_unit_kernel, dim3(grid_for(np)), dim3(kThreads), 0, st_, rhs.p, np, (size_t)c * p_ + k);
-      chol_->solve(rhs.p, sol.p, st_);
-      sol.download(h.data(), np, st_);
-      for (int j = i; j < i1; ++j) {
-        const int r = rows[order[j]];
-        double* blk = out + (size_t)order[j] * p_ * p_;
-        for (int rr = 0; rr < p_; ++rr) blk[rr + p_ * k] = h[(size_t)r * p_ + rr];
-      }
-    }
-    i = i1;
-  }
+  }, st_);
+  if (!ok) return 1;
+  chol_->inverse_blocks(n, rows, cols, out, marginals_recursion && chol_opt.world == 1, st_);
   return 0;
 }
 

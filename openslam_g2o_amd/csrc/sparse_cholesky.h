@@ -293,7 +293,10 @@ class SparseCholesky {
   // the pattern of L + L'.  One GPU only (world == 1).
   void sparse_inverse(hipStream_t st);
   bool inverse_block(int r, int c, long long* offset, int* ld, bool* transposed) const;
-  const double* inverse_slab() const { return d_Z.p; }
+  // Blocks (rows[i], cols[i]) of A^-1 after factor(), on the host: out_host [n][bs*bs], column-major blocks.  With
+  // `recursion` the blocks inside the pattern of L + L' are gathered from sparse_inverse(); the others (all of them
+  // without it) cost a pair of triangular sweeps per distinct column and scalar.  Synchronises st.
+  void inverse_blocks(int n, const int* rows, const int* cols, double* out_host, bool recursion, hipStream_t st);
   double* exchange_buffer(size_t* count) { *count = xbuf_count_; return d_xbuf.p; }
   // room for `n` more doubles BEHIND the subtree-root segments of the exchange buffer (the caller's own payload travels in
   // the same all-reduce: BlockSolver's boundary blocks); pack_exchange clears and fills the head only
@@ -330,6 +333,19 @@ class SparseCholesky {
   // true once after failed() saw a dependency-driven launch give up waiting; those launches are off from then on
   // (the caller drops its captured graphs and repeats the solve)
   bool dependency_stall() { const bool v = dep_stalled_; dep_stalled_ = false; return v; }
+  // attempt(false) enqueues a factorisation (and what shall share its status read); false: not positive definite.  A
+  // dependency-driven launch that gave up waiting is not that: the launches are per level from then on, and
+  // attempt(true) runs once more.
+  template <class Attempt>
+  bool factor_checked(Attempt&& attempt, hipStream_t st) {
+    attempt(false);
+    bool bad = failed(st);
+    if (bad && dependency_stall()) {
+      attempt(true);
+      bad = failed(st);
+    }
+    return !bad;
+  }
 
   const CholOptions& options() const { return hplan_.opt; }   // those of the last analyze()
   const CholStats& stats() const { return hplan_.stats; }

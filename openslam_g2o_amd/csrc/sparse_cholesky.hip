@@ -3554,6 +3554,86 @@ bool SparseCholesky::inverse_block(int r, int c, long long* offset, int* ld, boo
   return true;
 }
 
+namespace {
+// block i of the output <- block at off[i] of the sparse-inverse slab (leading dimension ld[i], transposed if tr[i])
+__global__ void gather_inverse_blocks_kernel(int n, int p, const long long* __restrict__ off, const int* __restrict__ ld,
+                                             const int* __restrict__ tr, const double* __restrict__ Z, double* __restrict__ out) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (t >= (size_t)n * p * p) return;
+  const int b = (int)(t / (p * p)), e = (int)(t % (p * p)), i = e % p, j = e / p;
+  if (off[b] < 0) return;
+  out[t] = tr[b] ? Z[off[b] + j + (long long)ld[b] * i] : Z[off[b] + i + (long long)ld[b] * j];
+}
+__global__ void set_unit_kernel(double* __restrict__ v, size_t n, size_t k) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < n) v[i] = (i == k) ? 1.0 : 0.0;
+}
+}  // namespace
+
+// BlockSolver::computeMarginals and LinearSolver::solvePattern both end here (block_solver.hpp:489-498,
+// linear_solver.h:63-69; marginal_covariance_cholesky.cpp:71-220 computes the same entries by recursion on the factor).
+void SparseCholesky::inverse_blocks(int n, const int* rows, const int* cols, double* out_host, bool recursion, hipStream_t st) {
+  if (n <= 0) return;
+  const size_t pp = (size_t)bs_ * bs_;
+  std::vector<int> order;   // the requests that are left to the sweeps
+  if (recursion) {
+    // Blocks inside the pattern of the factor: one top-down pass over the frontal matrices gives ALL of them; what lies
+    // outside (fill-free pairs of distant blocks) is left over.
+    sparse_inverse(st);
+    std::vector<long long> off(n, -1);
+    std::vector<int> ldv(n, 0), trv(n, 0);
+    for (int i = 0; i < n; ++i) {
+      bool tr = false;
+      if (inverse_block(rows[i], cols[i], &off[i], &ldv[i], &tr))
+        trv[i] = tr ? 1 : 0;
+      else
+        order.push_back(i);   // (off[i] stays -1: the gather skips it)
+    }
+    if ((int)order.size() < n) {
+      DevBuf<long long> d_off;
+      DevBuf<int> d_ld, d_tr;
+      DevBuf<double> d_out;
+      d_off.upload(off, st);
+      d_ld.upload(ldv, st);
+      d_tr.upload(trv, st);
+      d_out.alloc(n * pp);
+      hipLaunchKernelGGL(gather_inverse_blocks_kernel, dim3((unsigned)((n * pp + 255) / 256)), dim3(256), 0, st, n, bs_, d_off.p, d_ld.p,
+                         d_tr.p, d_Z.p, d_out.p);
+      std::vector<double> ho(n * pp);
+      d_out.download(ho.data(), ho.size(), st);
+      for (int i = 0; i < n; ++i)
+        if (off[i] >= 0) std::copy(ho.begin() + i * pp, ho.begin() + (i + 1) * pp, out_host + i * pp);
+    }
+  } else {
+    order.resize(n);
+    std::iota(order.begin(), order.end(), 0);
+  }
+  // a pair of triangular sweeps per distinct column and scalar serves every request of that column
+  n = (int)order.size();
+  if (n == 0) return;
+  const size_t nv = (size_t)hplan_.sym.nb * bs_;
+  DevBuf<double> rhs, sol;
+  rhs.alloc(nv);
+  sol.alloc(nv);
+  std::vector<double> h(nv);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cols[a] < cols[b]; });
+  for (int i = 0; i < n;) {
+    const int c = cols[order[i]];
+    int i1 = i;
+    while (i1 < n && cols[order[i1]] == c) ++i1;
+    for (int k = 0; k < bs_; ++k) {
+      hipLaunchKernelGGL(set_unit_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, rhs.p, nv, (size_t)c * bs_ + k);
+      solve(rhs.p, sol.p, st);
+      sol.download(h.data(), nv, st);
+      for (int j = i; j < i1; ++j) {
+        double* blk = out_host + order[j] * pp;
+        for (int r = 0; r < bs_; ++r) blk[r + bs_ * k] = h[(size_t)rows[order[j]] * bs_ + r];
+      }
+    }
+    i = i1;
+  }
+}
+
 void SparseCholesky::factor(const double* dA, hipStream_t st) {
   factor_phase(dA, 0, st);
   factor_phase(dA, 1, st);

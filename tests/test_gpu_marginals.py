@@ -150,3 +150,66 @@ def test_sparse_inverse_with_large_fronts_matches_column_solves():
     M0 = s.computeMarginals(rows, cols)
     assert M is not None and M0 is not None
     assert np.abs(M - M0).max() <= 1e-9 * np.abs(M0).max()
+
+
+@pytest.mark.parametrize("bs", [3, 6])
+def test_inverse_blocks_inside_and_outside_the_pattern_on_both_seams(bs):
+    """SparseCholesky::inverse_blocks behind LinearSolver::solvePattern and BlockSolver::computeMarginals: a block-tridiagonal
+    system of 40 blocks.  Every diagonal and sub-diagonal block lies inside the pattern of the factor (gathered from the
+    sparse inverse); the far corner (0, nb-1), its transpose and (1, nb-1) -- which shares a column with the corner -- lie
+    outside it (an interior separator is eliminated last) and come from the unit-vector sweeps, one pair per distinct
+    column; the corner is requested twice (two outputs from one pair of sweeps).  Against the dense inverse, to the tolerance of the tests above."""
+    from openslam_g2o_amd import capi
+    nb = 40
+    rng = np.random.default_rng(400 + bs)
+    pairs = [(c, c) for c in range(nb)] + [(c, c - 1) for c in range(1, nb)] + [(0, nb - 1), (nb - 1, 0), (1, nb - 1), (0, nb - 1)]
+    rows, cols = np.array([r for r, _ in pairs], np.int32), np.array([c for _, c in pairs], np.int32)
+
+    def check(M, Ainv):
+        assert M is not None and M.shape == (len(rows), bs, bs)
+        for i in range(len(rows)):
+            ref = Ainv[bs * rows[i]:bs * rows[i] + bs, bs * cols[i]:bs * cols[i] + bs]
+            assert np.abs(M[i] - ref).max() <= 1e-9 * np.abs(Ainv).max(), (rows[i], cols[i])
+
+    # narrow seam: diagonally dominant block-tridiagonal matrix, upper block CCS with column-major blocks
+    n = nb * bs
+    A = np.zeros((n, n))
+    for c in range(1, nb):
+        A[bs * (c - 1):bs * c, bs * c:bs * (c + 1)] = rng.normal(size=(bs, bs))
+    A = A + A.T
+    A += np.eye(n) * (np.abs(A).sum(axis=1).max() + 1.0)
+    cp, ri, vals = [0], [], []
+    for c in range(nb):
+        for r in ([c - 1, c] if c else [c]):
+            ri.append(r)
+            vals.append(A[bs * r:bs * (r + 1), bs * c:bs * (c + 1)].T.reshape(-1))
+        cp.append(len(ri))
+    ls = capi.HipLinearSolver(bs, 0)
+    check(ls.solvePattern(np.array(cp, np.int32), np.array(ri, np.int32), np.array(vals), rows, cols), np.linalg.inv(A))
+
+    # wide seam: a chain of binary pose-pose edges plus one unary prior gives Hpp that pattern
+    s = capi.HipBlockSolver(bs, 2 if bs == 3 else 3, 0)
+    ne = nb - 1
+    k = s.addEdgeSet(bs, np.arange(ne), np.arange(1, nb))
+    u = s.addEdgeSet(bs, np.array([0]))
+    s.buildStructure(nb, 0, False)
+    eye = np.eye(bs).reshape(-1)
+    s.setEdgeData(k, -eye + 0.1 * rng.normal(size=(ne, bs * bs)), eye + 0.1 * rng.normal(size=(ne, bs * bs)), np.tile(eye, (ne, 1)),
+                  rng.normal(size=(ne, bs)))
+    s.setEdgeData(u, eye[None], None, eye[None], np.zeros((1, bs)))
+    s.buildSystem()
+    hcp, hri = s.pattern(capi.HPP)
+    assert list(hcp) == cp and list(hri) == ri
+    hv = s.values(capi.HPP).reshape(-1, bs, bs)
+    H = np.zeros((n, n))
+    for c in range(nb):
+        for q in range(hcp[c], hcp[c + 1]):
+            H[bs * hri[q]:bs * (hri[q] + 1), bs * c:bs * (c + 1)] = hv[q].T
+    Hinv = np.linalg.inv(np.triu(H) + np.triu(H, 1).T)
+    s.setOption("marginals_recursion", 1)
+    M1 = s.computeMarginals(rows, cols)
+    s.setOption("marginals_recursion", 0)
+    M0 = s.computeMarginals(rows, cols)
+    check(M1, Hinv)
+    check(M0, Hinv)
+    assert np.abs(M1 - M0).max() <= 1e-9 * np.abs(Hinv).max()

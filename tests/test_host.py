@@ -103,3 +103,29 @@ def test_g2o_reader(tmp_path):
     assert np.allclose(g["info"][0], [[10, 1, 2], [1, 20, 3], [2, 3, 30]])
     h, n = g2o_io.hessian_index(2, g["fixed"])
     assert list(h) == [-1, 0] and n == 1
+
+
+def test_every_handle_entry_refuses_a_null_handle():
+    """Every entry point that takes a solver handle and returns a status refuses NULL with G2OHIP_ERR_ARG (-1) AND leaves
+    its own text: g2ohip_last_error() must not still hold the message of an earlier, unrelated failure (capi._check
+    raises with that text).  The accessors that return a value instead of a status give 0 / NULL."""
+    L = capi.load()
+    skip = {"g2ohip_create", "g2ohip_ls_create", "g2ohip_destroy", "g2ohip_ls_destroy", "g2ohip_partition_poses",
+            "g2ohip_comm_unique_id"}
+    entries = []
+    for name in capi.EXPORTS:
+        fn = getattr(L, name)
+        if name in skip or not fn.argtypes or fn.argtypes[0] is not ctypes.c_void_p or fn.restype is not ctypes.c_int:
+            continue      # (no handle, or not a status: vector_size, x_device, b_device, kernel_name, last_error)
+        entries.append((name, fn))
+    assert len(entries) >= 90
+    for name, fn in entries:
+        h = ctypes.c_void_p()
+        assert L.g2ohip_ls_create(ctypes.byref(h), 5, 0) < 0      # an unrelated failure, with or without a GPU
+        stale = L.g2ohip_last_error()
+        assert stale and b"handle" not in stale
+        rc = fn(*[t() for t in fn.argtypes])                        # NULL handle, zero / NULL for everything else
+        assert rc == -1, name
+        assert b"handle" in L.g2ohip_last_error(), (name, L.g2ohip_last_error())
+    assert L.g2ohip_vector_size(None) == 0
+    assert L.g2ohip_x_device(None) is None and L.g2ohip_b_device(None) is None
