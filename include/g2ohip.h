@@ -487,6 +487,20 @@ int g2ohip_pg_discard_top(g2ohip_solver* s);
  * pose block alone (x_p = Hpp^-1 b_p, the landmark part of x stays zero), as for every system with landmarks. */
 int g2ohip_pg_set_landmark_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
                                  const double* meas, const double* info, const double* offset);
+/* The projective pose -> point edges of an RGB-D / stereo front end, bound to the SAME single landmark slot of the handle (a
+ * later call of either entry replaces the binding), beside a type-2 (EdgeSE3) pose set only, landmarks (x, y, z):
+ *   type 5 = EdgeSE3PointXYZDepth (g2o/types/slam3d/edge_se3_pointxyz_depth.cpp:91-138 computeError / linearizeOplus):
+ *            e = (p0 / p2, p1 / p2, p2) - z, measurement (u, v, depth);
+ *   type 6 = EdgeSE3PointXYZDisparity (edge_se3_pointxyz_disparity.cpp:96-168, analytic Jacobian as enabled by
+ *            edge_se3_pointxyz_disparity.h:36): e = (p0 / p2, p1 / p2, 1 / p2) - z, measurement (u, v, 1 / depth);
+ * with p = Kcam (X offset)^-1 l and ONE ParameterCamera / CacheCamera for the whole set (parameter_camera.cpp:45-59, 93-96):
+ * offset an isometry [12] = R (column-major) | t or NULL for the identity, kcam[4] = fx, fy, cx, cy (required, finite, fx and
+ * fy not zero).  meas [n][3], info [n][3x3].  Like the reference there is no guard for a point on or behind the image plane
+ * (p2 <= 0).  Preconditions, validation and error codes are those of g2ohip_pg_set_landmark_edges (which keeps rejecting
+ * types other than 3 and 4); everything after the binding -- g2ohip_pg_set_landmark_estimates, g2ohip_pg_linearize / update /
+ * push / pop / discard_top, robust kernels, g2ohip_clear_edge_sets -- acts on it unchanged. */
+int g2ohip_pg_set_landmark_camera_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                        const double* meas, const double* info, const double* offset, const double* kcam);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -60,6 +60,7 @@ EXPORTS = [
     "g2ohip_pg_set_edges", "g2ohip_pg_set_estimates", "g2ohip_pg_get_estimates", "g2ohip_pg_linearize", "g2ohip_pg_update",
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
+    "g2ohip_pg_set_landmark_camera_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -161,6 +162,7 @@ def load():
     L.g2ohip_pg_get_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_pg_linearize.argtypes = [vp, C.c_int]
     L.g2ohip_pg_set_landmark_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_landmark_camera_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_copy_edge_data.argtypes = [vp, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -711,7 +713,7 @@ class HipBlockSolver:
     def pgDiscardTop(self):
         _check(self.L.g2ohip_pg_discard_top(self.h), "pgDiscardTop")
 
-    # ---- ... its landmark half (EdgeSE2PointXY = 3 beside EdgeSE2, EdgeSE3PointXYZ = 4 beside EdgeSE3) ----
+    # ---- ... its landmark half (EdgeSE2PointXY = 3 beside EdgeSE2; EdgeSE3PointXYZ = 4, ...Depth = 5, ...Disparity = 6 beside EdgeSE3) ----
     def pgSetLandmarkEdges(self, set_id, edge_type, pose_vertex, point_vertex, meas, info, offset=None):
         """Observations of point landmarks: pose_vertex / point_vertex index the tables of pgSetEstimates /
         pgSetLandmarkEstimates, meas [n][2|3], info [n][2x2|3x3], offset: isometry [12] of the set's ParameterSE3Offset
@@ -727,6 +729,25 @@ class HipBlockSolver:
                 raise ValueError("pgSetLandmarkEdges: offset is an isometry [12] (R column-major | t)")
         _check(self.L.g2ohip_pg_set_landmark_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
                                                    None if off is None else _dp(off)), "pgSetLandmarkEdges")
+
+    def pgSetLandmarkCameraEdges(self, set_id, edge_type, pose_vertex, point_vertex, meas, info, offset, kcam):
+        """Projective observations of point landmarks beside an EdgeSE3 pose set: edge_type 5 = EdgeSE3PointXYZDepth
+        (measurement u, v, depth), 6 = EdgeSE3PointXYZDisparity (u, v, 1 / depth); meas [n][3], info [n][3x3], offset:
+        isometry [12] of the set's ParameterCamera (None = identity), kcam = (fx, fy, cx, cy).  After pgSetEdges."""
+        pv, lv, meas, info = _i32(pose_vertex), _i32(point_vertex), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        if len(pv) != n or len(lv) != n or meas.size != n * 3 or info.size != n * 9:
+            raise ValueError("pgSetLandmarkCameraEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        off = None
+        if offset is not None:
+            off = _f64(offset).reshape(-1)
+            if off.size != 12:
+                raise ValueError("pgSetLandmarkCameraEdges: offset is an isometry [12] (R column-major | t)")
+        kc = _f64(kcam).reshape(-1)
+        if kc.size != 4:
+            raise ValueError("pgSetLandmarkCameraEdges: kcam is (fx, fy, cx, cy)")
+        _check(self.L.g2ohip_pg_set_landmark_camera_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
+                                                          None if off is None else _dp(off), _dp(kc)), "pgSetLandmarkCameraEdges")
 
     def pgSetLandmarkEstimates(self, points, hidx):
         """points [n][landmark_dim]; hidx[v] = the landmark's hessian index in the whole system (>= num_poses) or -1."""

@@ -85,6 +85,12 @@ class HipBlockSolver {
     return ok(g2ohip_set_option(h_, "linear_solver", on ? 1.0 : 0.0), "set_option") &&
            ok(g2ohip_set_option(h_, "pcg_tolerance", tolerance), "set_option");
   }
+  // EdgeSE3PointXYZDepth (type 5) / EdgeSE3PointXYZDisparity (type 6) observations with one ParameterCamera, kept on the device
+  // beside an EdgeSE3 pose set of g2ohip_pg_set_edges (handle()): offset isometry [12] or nullptr, kcam = fx, fy, cx, cy
+  bool pgSetLandmarkCameraEdges(int set, int type, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas,
+                                const double* info, const double* offset, const double* kcam) {
+    return ok(g2ohip_pg_set_landmark_camera_edges(h_, set, type, poseVertex, pointVertex, meas, info, offset, kcam), "pgSetLandmarkCameraEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -93,6 +93,8 @@ class BlockSolver {
   void pg_get_estimates(double* poses);
   void pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
                              const double* offset);
+  void pg_set_landmark_camera_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                    const double* info, const double* offset, const double* kcam);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
   void pg_linearize(bool jacobians);
@@ -341,6 +343,8 @@ class BlockSolver {
   bool ll_hbm_partial_ = false;   // ... but the Schur tiles that assembled them wrote b_l only (Hll and the errors stayed on chip)
   void pg_validate();
   void pg_validate_landmarks();
+  void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                              const double* info, const double* offset, const double* kcam);
   struct BaFrontEnd {
     int set = -1, n_edges = 0, n_cams = 0, n_points = 0;
     double f = 0, cx = 0, cy = 0;
@@ -380,7 +384,8 @@ class BlockSolver {
   } ba_;
   // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
-  // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)).  Vertex 0 of an observation
+  // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one ParameterCamera
+  // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges).  Vertex 0 of an observation
   // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); pt_hidx[v] is the landmark's index in
   // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
   // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
@@ -400,7 +405,8 @@ class BlockSolver {
     DevBuf<int> vp, vl, pt_hidx;
     std::vector<int> h_vp, h_vl, h_pt_hidx;   // host copies: index validation (pg_validate_landmarks)
     DevBuf<double> lm_meas, points, points_bak;
-    double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4)
+    double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
+    double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

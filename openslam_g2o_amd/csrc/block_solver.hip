@@ -5389,7 +5389,8 @@ void BlockSolver::pg_get_estimates(double* poses) {
   pg_.poses.download(poses, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12), st_);
 }
 
-// ---- ... its landmark half (EdgeSE2PointXY / EdgeSE3PointXYZ over VertexPointXY / VertexPointXYZ) -----------------------
+// ---- ... its landmark half (EdgeSE2PointXY / EdgeSE3PointXYZ / EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity over
+// VertexPointXY / VertexPointXYZ) -----------------------------------------------------------------------------------------
 void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                         const double* info, const double* offset) {
   invalidate_graphs();
@@ -5398,13 +5399,36 @@ void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_verte
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
   if (type != 3 && type != 4) throw ArgFailure("pg_set_landmark_edges: type must be 3 (EdgeSE2PointXY) or 4 (EdgeSE3PointXYZ)");
   if (type != pg_.type + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
-  if (set == pg_.set) throw ArgFailure("pg_set_landmark_edges: the set is bound as the pose-pose set");
+  if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
+  pg_bind_landmark_edges("pg_set_landmark_edges", set, type, pose_vertex, point_vertex, meas, info, offset, nullptr);
+}
+
+// EdgeSE3PointXYZDepth (5) / EdgeSE3PointXYZDisparity (6) with ONE ParameterCamera (offset + Kcam) for the whole set
+void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                               const double* info, const double* offset, const double* kcam) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_camera_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 5 && type != 6) throw ArgFailure("pg_set_landmark_camera_edges: type must be 5 (EdgeSE3PointXYZDepth) or 6 (EdgeSE3PointXYZDisparity)");
+  if (pg_.type != 2) throw ArgFailure("pg_set_landmark_camera_edges: the camera edges go with an EdgeSE3 pose set (2)");
+  if (!kcam) throw ArgFailure("pg_set_landmark_camera_edges: null kcam (fx, fy, cx, cy)");
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(kcam[i])) throw ArgFailure("pg_set_landmark_camera_edges: non-finite camera intrinsics");
+  if (kcam[0] == 0.0 || kcam[1] == 0.0) throw ArgFailure("pg_set_landmark_camera_edges: fx and fy must not be zero");
+  pg_bind_landmark_edges("pg_set_landmark_camera_edges", set, type, pose_vertex, point_vertex, meas, info, offset, kcam);
+}
+
+// what both entries share: the set's dimensions, index validation (rolled back when it fails), the uploads
+void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
+                                         const double* meas, const double* info, const double* offset, const double* kcam) {
+  const std::string w(who);
+  if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
   EdgeSet& es = *sets_[set];
   const int d = type == 3 ? 2 : 3, dp = type == 3 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != d || p_ != dp || l_ != d)
-    throw ArgFailure("pg_set_landmark_edges: the set must be a binary pose-landmark set with (error, pose, landmark) dimensions (2, 3, 2) or (3, 6, 3)");
-  if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure("pg_set_landmark_edges: null array");
-  if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
+    throw ArgFailure(w + ": the set must be a binary pose-landmark set with (error, pose, landmark) dimensions (2, 3, 2) or (3, 6, 3)");
+  if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure(w + ": null array");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   // (a failed validation must not leave half a binding)
@@ -5424,6 +5448,9 @@ void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_verte
     throw;
   }
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
+  for (int i = 0; i < 4; ++i) pg_.kcam[i] = kcam ? kcam[i] : (i < 2 ? 1.0 : 0.0);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
   pg_.vp.upload(pose_vertex, n, st_);
   pg_.vl.upload(point_vertex, n, st_);
   pg_.lm_meas.upload(meas, n * d, st_);
@@ -5510,6 +5537,18 @@ void BlockSolver::pg_linearize(bool jacobians) {
       else
         hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<false>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
                            pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+    } else if (pg_.lm_type == 5 || pg_.lm_type == 6) {
+      PgIso off;
+      for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
+      const PgKcam kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3]};
+      with_bool(pg_.lm_type == 6, [&](auto disparity) {
+        with_bool(pg_landmark_staged, [&](auto staged) {
+          constexpr bool DISPARITY = disparity, STAGED = staged;
+          hipLaunchKernelGGL((pg_se3_camera_linearize_kernel<DISPARITY, STAGED>), grid, block, 0, st_,
+                             el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, off, kc, el->own_J0.p, el->own_J1.p,
+                             el->own_err.p, jac);
+        });
+      });
     } else {
       PgIso off;
       for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];

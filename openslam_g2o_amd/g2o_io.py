@@ -6,7 +6,8 @@ Mirrors what OptimizableGraph::load (g2o/core/optimizable_graph.cpp:356-480) doe
 the information matrix is given as its upper triangle, row-major (edge_se2.cpp:46-51).
 Landmark SLAM files add `VERTEX_XY` / `EDGE_SE2_XY` (g2o/types/slam2d/{vertex_point_xy,edge_se2_pointxy}.cpp read()) and
 `VERTEX_TRACKXYZ` / `EDGE_SE3_TRACKXYZ` / `PARAMS_SE3OFFSET` (g2o/types/slam3d/{vertex_pointxyz,edge_se3_pointxyz,
-parameter_se3_offset}.cpp read()).
+parameter_se3_offset}.cpp read()); RGB-D / stereo files `EDGE_PROJECT_DEPTH` / `EDGE_PROJECT_DISPARITY` / `PARAMS_CAMERACALIB`
+(g2o/types/slam3d/{edge_se3_pointxyz_depth,edge_se3_pointxyz_disparity,parameter_camera}.cpp read()).
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -27,9 +28,13 @@ def read_g2o(path):
     A file with point landmarks (VERTEX_XY / EDGE_SE2_XY, VERTEX_TRACKXYZ / EDGE_SE3_TRACKXYZ, PARAMS_SE3OFFSET) gives the same
     keys for its poses and pose-pose edges plus: point_ids, points [L][2|3] (sorted by id), lm_vp / lm_vl (pose-table and
     point-table index of every observation), lm_meas, lm_info [M][d][d], lm_param (offset parameter id per observation, 3-D),
-    offsets {id: (x y z qx qy qz qw), quaternion normalised as ParameterSE3Offset::read does}, fixed_points."""
+    offsets {id: (x y z qx qy qz qw), quaternion normalised as ParameterSE3Offset::read does}, fixed_points.
+    A file with EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY (pose point paramId u v d + upper triangle) or PARAMS_CAMERACALIB
+    (id x y z qx qy qz qw fx fy cx cy) also gives lm_kind (per observation: "xyz" | "depth" | "disparity") and cameras
+    {id: (x y z qx qy qz qw fx fy cx cy)}; files without these tags return exactly the keys above."""
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
+    lkind, cameras = [], {}
     kind = None
     with open(path) as f:
         for line in f:
@@ -72,6 +77,18 @@ def read_g2o(path):
                 lparam.append(int(t[3]))
                 lmeas.append([float(x) for x in t[4:7]])
                 linfo.append(_upper_to_full([float(x) for x in t[7:13]], 3))
+                lkind.append("xyz")
+            elif tag in ("EDGE_PROJECT_DEPTH", "EDGE_PROJECT_DISPARITY"):
+                lp.append(int(t[1]))
+                ll.append(int(t[2]))
+                lparam.append(int(t[3]))
+                lmeas.append([float(x) for x in t[4:7]])
+                linfo.append(_upper_to_full([float(x) for x in t[7:13]], 3))
+                lkind.append("depth" if tag == "EDGE_PROJECT_DEPTH" else "disparity")
+            elif tag == "PARAMS_CAMERACALIB":
+                o = np.asarray([float(x) for x in t[2:13]])
+                o[3:7] /= np.linalg.norm(o[3:7])
+                cameras[int(t[1])] = o
             elif tag == "PARAMS_SE3OFFSET":
                 o = np.asarray([float(x) for x in t[2:9]])
                 o[3:] /= np.linalg.norm(o[3:])
@@ -87,7 +104,7 @@ def read_g2o(path):
     vj = np.asarray([lut[a] for a in ej], np.int32)
     out = dict(kind=kind, ids=vid, estimates=vest, vi=vi, vj=vj, meas=np.asarray(meas, np.float64),
                info=np.asarray(info, np.float64), fixed=[lut[f] for f in fixed if f in lut])
-    if pid or lp or offsets:
+    if pid or lp or offsets or cameras:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
         pid = pid[po]
@@ -96,6 +113,8 @@ def read_g2o(path):
                    lm_vp=np.asarray([lut[a] for a in lp], np.int32), lm_vl=np.asarray([plut[a] for a in ll], np.int32),
                    lm_meas=np.asarray(lmeas, np.float64), lm_info=np.asarray(linfo, np.float64),
                    lm_param=np.asarray(lparam, np.int32), offsets=offsets, fixed_points=[plut[f] for f in fixed if f in plut])
+        if cameras or any(k != "xyz" for k in lkind):
+            out.update(lm_kind=lkind, cameras=cameras)
     return out
 
 
@@ -129,7 +148,9 @@ def _iso_from_qt(qt):
 def landmark_problem(rd, fixed_poses=None, fixed_points=None):
     """read_g2o() result of a landmark SLAM file -> the problem dict of openslam_g2o_amd.synthetic.make_landmark_slam (what
     lm.setup_device_landmark_slam takes).  fixed_*: indices into the pose / point tables (default: the file's FIX lines; a file
-    without any gets pose 0 fixed as the gauge).  All 3-D observations must name the same PARAMS_SE3OFFSET."""
+    without any gets pose 0 fixed as the gauge).  All 3-D observations must name the same PARAMS_SE3OFFSET.  A file of
+    EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY observations gives observation = "depth" | "disparity", kcam = (fx, fy, cx, cy)
+    and the offset of its PARAMS_CAMERACALIB; observations of different kinds or naming several camera parameters are refused."""
     if "points" not in rd:
         raise ValueError("the file has no point landmarks")
     se2 = rd["kind"] == "se2"
@@ -141,6 +162,7 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
     hidx, pt_hidx, nP, nL = landmark_hessian_index(n, L, fp, fl)
     dp, dl = (3, 2) if se2 else (6, 3)
     offset = None
+    camera = {}
     if se2:
         poses, Z = rd["estimates"].copy(), rd["meas"].copy()
     else:
@@ -150,12 +172,24 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
             return qt
         poses, Z = _iso_from_qt(unit(rd["estimates"])), _iso_from_qt(unit(rd["meas"]))
         ids = set(int(v) for v in rd["lm_param"])
-        if len(ids) > 1:
-            raise ValueError("observations with different PARAMS_SE3OFFSET are not one set")
-        if ids:
-            offset = _iso_from_qt(rd["offsets"][ids.pop()])[0]
+        kinds = set(rd.get("lm_kind", ()))
+        if len(kinds) > 1:
+            raise ValueError("observations of different kinds (%s) are not one set" % ", ".join(sorted(kinds)))
+        if kinds and kinds != {"xyz"}:
+            if len(ids) > 1 or len(rd["cameras"]) > 1:
+                raise ValueError("several PARAMS_CAMERACALIB: one camera per observation set")
+            cam = rd["cameras"].get(ids.pop()) if ids else None
+            if cam is None:
+                raise ValueError("the observations name a PARAMS_CAMERACALIB the file does not define")
+            camera = dict(observation=kinds.pop(), kcam=cam[7:11].copy())
+            offset = _iso_from_qt(cam[0:7])[0]
+        else:
+            if len(ids) > 1:
+                raise ValueError("observations with different PARAMS_SE3OFFSET are not one set")
+            if ids:
+                offset = _iso_from_qt(rd["offsets"][ids.pop()])[0]
     E, M = len(rd["vi"]), len(rd["lm_vp"])
-    return dict(kind=rd["kind"], n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=rd["vi"], vj=rd["vj"], Z=Z,
+    return dict(camera, kind=rd["kind"], n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=rd["vi"], vj=rd["vj"], Z=Z,
                 omega=np.asarray(rd["info"]).transpose(0, 2, 1).reshape(E, dp * dp).copy(), vp=rd["lm_vp"], vl=rd["lm_vl"],
                 zl=rd["lm_meas"], omega_l=np.asarray(rd["lm_info"]).transpose(0, 2, 1).reshape(M, dl * dl).copy(), offset=offset,
                 poses=poses, points=rd["points"].copy(), hidx=hidx, pt_hidx=pt_hidx)
@@ -163,8 +197,11 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
 
 def write_g2o_landmarks(path, prob):
     """make_landmark_slam-style problem -> `.g2o` text with the reference's tags (poses get the ids 0..n-1, landmarks
-    n..n+L-1, the sensor offset parameter id 0); fixed vertices (hessian index -1) go into a FIX line."""
+    n..n+L-1, the sensor offset parameter id 0); fixed vertices (hessian index -1) go into a FIX line.  A problem with
+    observation = "depth" | "disparity" writes PARAMS_CAMERACALIB and EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY."""
     se2 = prob["kind"] == "se2"
+    obs = prob.get("observation", "xyz")
+    obs_tag = {"xyz": "EDGE_SE3_TRACKXYZ", "depth": "EDGE_PROJECT_DEPTH", "disparity": "EDGE_PROJECT_DISPARITY"}[obs]
     n = len(prob["poses"])
     fmt = lambda v: " ".join("%.17g" % x for x in v)
     upper = lambda Mx, d: fmt(Mx.reshape(d, d)[i, j] for i in range(d) for j in range(i, d))
@@ -181,7 +218,10 @@ def write_g2o_landmarks(path, prob):
         else:
             off = prob.get("offset")
             off = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]) if off is None else off
-            f.write("PARAMS_SE3OFFSET 0 %s\n" % fmt(qt(off)[0]))
+            if obs == "xyz":
+                f.write("PARAMS_SE3OFFSET 0 %s\n" % fmt(qt(off)[0]))
+            else:
+                f.write("PARAMS_CAMERACALIB 0 %s %s\n" % (fmt(qt(off)[0]), fmt(prob["kcam"])))
             for i, v in enumerate(qt(prob["poses"])):
                 f.write("VERTEX_SE3:QUAT %d %s\n" % (i, fmt(v)))
             for j, pt in enumerate(prob["points"]):
@@ -195,7 +235,7 @@ def write_g2o_landmarks(path, prob):
             f.write("%s %d %d %s %s\n" % ("EDGE_SE2" if se2 else "EDGE_SE3:QUAT", prob["vi"][e], prob["vj"][e], fmt(Zq[e]),
                                           upper(np.asarray(prob["omega"][e]), dp)))
         for e in range(len(prob["vp"])):
-            f.write("%s %d %d %s%s %s\n" % ("EDGE_SE2_XY" if se2 else "EDGE_SE3_TRACKXYZ", prob["vp"][e], n + prob["vl"][e],
+            f.write("%s %d %d %s%s %s\n" % ("EDGE_SE2_XY" if se2 else obs_tag, prob["vp"][e], n + prob["vl"][e],
                                             "" if se2 else "0 ", fmt(prob["zl"][e]), upper(np.asarray(prob["omega_l"][e]), dl)))
 
 

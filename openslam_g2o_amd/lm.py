@@ -354,13 +354,17 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
 
 def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, options=None):
     """HipBlockSolver for an openslam_g2o_amd.synthetic.make_landmark_slam (or g2o_io.landmark_problem) graph: odometry edges
-    between poses (EdgeSE2 / EdgeSE3) plus observations of point landmarks (EdgeSE2PointXY / EdgeSE3PointXYZ), pose and
+    between poses (EdgeSE2 / EdgeSE3) plus observations of point landmarks (EdgeSE2PointXY / EdgeSE3PointXYZ, or -- when prob
+    carries observation = "depth" | "disparity" and kcam -- EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity), pose and
     landmark estimates, errors and Jacobians on the device; BlockSolver_3_2 / BlockSolver_6_3 semantics, landmarks
     marginalised (schur=True).  huber_delta > 0: Huber kernel on the observation set.  Returns (solver, DevicePoseGraph);
     solver.landmark_sets = (odometry set id, observation set id)."""
     import numpy as np
     from . import capi
     se2 = prob["kind"] == "se2"
+    obs = prob.get("observation", "xyz")
+    if obs in ("depth", "disparity") and prob.get("kcam") is None:
+        raise ValueError("setup_device_landmark_slam: observation = %r needs kcam = (fx, fy, cx, cy)" % obs)
     p, l = (3, 2) if se2 else (6, 3)
     s = capi.HipBlockSolver(p, l, device)
     for name, value in (options or {}).items():
@@ -371,7 +375,11 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     s.buildStructure(prob["nP"], prob["nL"], schur)
     s.pgSetEdges(k0, 1 if se2 else 2, prob["vi"], prob["vj"], prob["Z"], prob["omega"])
     s.pgSetEstimates(prob["poses"], hidx)
-    s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
+    if obs in ("depth", "disparity"):
+        s.pgSetLandmarkCameraEdges(k1, 5 if obs == "depth" else 6, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"],
+                                   prob.get("offset"), prob["kcam"])
+    else:
+        s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
     s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
     if huber_delta > 0:
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)

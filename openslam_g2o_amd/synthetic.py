@@ -376,7 +376,7 @@ def _wrap(theta):
 
 def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, window=2, max_obs=None, seed=42,
                        noise_odometry=(0.02, 0.01), noise_landmark=0.05, outlier_frac=0.0, perturb=(0.1, 0.02, 0.2),
-                       closure_stride=5, fixed_landmarks=0):
+                       closure_stride=5, fixed_landmarks=0, observation="xyz", kcam=(525.0, 515.0, 319.5, 239.5), z_min=1.0):
     """Landmark SLAM graph: odometry between poses plus point landmarks observed from them.
     kind "se2": VertexSE2 / VertexPointXY with EdgeSE2 + EdgeSE2PointXY; "se3": VertexSE3 / VertexPointXYZ with EdgeSE3 +
     EdgeSE3PointXYZ and one non-identity sensor offset (ParameterSE3Offset).
@@ -390,10 +390,25 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
     by N(0, perturb = (pose translation, pose rotation, landmark)).  Pose 0 is fixed (gauge) and the first `fixed_landmarks`
     landmarks.  Counter-based RNG: the same seed gives the same graph anywhere.  Ground truth: poses_true, points_true.
     Layout: SE2 poses (x, y, theta), SE3 poses / measurements isometries [12]; hidx / pt_hidx hessian indices (landmarks
-    behind the poses: nP + number among the free landmarks; -1 fixed)."""
+    behind the poses: nP + number among the free landmarks; -1 fixed).
+    observation = "depth" | "disparity" (kind "se3" only): the observations are EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity
+    of one forward-looking camera (ParameterCamera: the returned `offset` and `kcam` = (fx, fy, cx, cy)), measurements (u, v,
+    depth) / (u, v, 1 / depth).  Landmark j then lies in front of the camera of its anchor pose, and of the candidate
+    observers only those are kept that see it at a sensor-frame depth in [z_min, sensor_range], z_min > 0, both at the ground
+    truth and at the initial estimates (the reference has no guard for a point behind the image plane); a landmark left with
+    no observation is an error.  Information: the reference's defaults diag(1, 1, 100) (depth) / diag(1, 1, 1000) (disparity);
+    the noise matches them: sigma 1 pixel, 0.1 m, 1000^-1/2 m^-1.  Outliers: up to 50 pixels and half the depth / disparity
+    range.  The dict then also carries `observation` and `kcam`."""
     if kind not in ("se2", "se3"):
         raise ValueError("kind must be 'se2' or 'se3'")
+    if observation not in ("xyz", "depth", "disparity"):
+        raise ValueError("observation must be 'xyz', 'depth' or 'disparity'")
     se2 = kind == "se2"
+    camera = observation != "xyz"
+    if camera and se2:
+        raise ValueError("depth / disparity observations belong to kind 'se3'")
+    if camera and not z_min > 0:
+        raise ValueError("z_min must be positive")
     rng = CounterRng(seed)
     n, L = int(n_poses), int(n_landmarks)
     per_lap = max(4, n // laps)
@@ -426,6 +441,29 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
     dist = np.where(cand < n, dist, np.inf)
     seen = dist <= sensor_range
     seen[np.arange(L), np.argmin(dist, axis=1)] = True              # every landmark is observed at least once
+    if camera:
+        # a camera looking along the robot's x axis (image x to the right, y down), slightly tilted and off-centre
+        Ro = np.array([[0.0, 0, 1], [-1, 0, 0], [0, -1, 0]]) @ _exp_so3(np.array([[0.05, -0.03, 0.04]]))[0][0]
+        to = np.array([0.2, -0.1, 0.3])
+        u = (off + 1.0) * 0.5
+        depth = sensor_range * (0.5 + 0.4 * u[:, 0])
+        q = np.stack([0.6 * depth * (2.0 * u[:, 1] - 1.0), 0.4 * depth * (2.0 * u[:, 2] - 1.0), depth], axis=1)
+        points_true = np.einsum("nij,nj->ni", R[anchor] @ Ro, q) + np.einsum("nij,j->ni", R[anchor], to) + pos[anchor]
+        # the initial estimates (the same draws as below) decide with the ground truth which observations are kept
+        Ri = R @ _exp_so3(np.stack([rng.normal(223 + c, n) for c in range(3)], axis=1) * perturb[1])[0]
+        ti = pos + perturb[0] * np.stack([rng.normal(220 + c, n) for c in range(3)], axis=1)
+        Ri[0], ti[0] = R[0], pos[0]
+        pi = points_true + perturb[2] * np.stack([rng.normal(250 + c, L) for c in range(dl)], axis=1)
+        pi[:fixed_landmarks] = points_true[:fixed_landmarks]
+        seen = cand < n
+        cc = np.minimum(cand, n - 1)
+        for Rx, tx, px_ in ((R, pos, points_true), (Ri, ti, pi)):
+            zax = Rx[cc] @ Ro[:, 2]                                     # the camera's viewing direction in the world
+            z = np.einsum("lki,lki->lk", zax, px_[:, None, :] - (np.einsum("lkij,j->lki", Rx[cc], to) + tx[cc]))
+            seen &= (z >= z_min) & (z <= sensor_range)
+        if not seen.any(axis=1).all():
+            raise ValueError("landmark %d is seen by no candidate pose at a depth in [z_min, sensor_range]: smaller perturb or "
+                             "z_min, larger window or sensor_range" % int(np.argmin(seen.any(axis=1))))
     if max_obs is not None:
         seen &= np.cumsum(seen, axis=1) <= max_obs
     lm_i, slot = np.nonzero(seen)
@@ -464,8 +502,9 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
         info = np.zeros((6, 6))
         info[:3, :3] = np.eye(3) / st ** 2
         info[3:, 3:] = np.eye(3) / (0.5 * sr) ** 2                  # (the error's rotation part is the quaternion vector: half the angle)
-        Ro = _exp_so3(np.array([[0.1, -0.2, 0.3]]))[0][0]           # the sensor is mounted off-centre and rotated
-        to = np.array([0.2, -0.1, 0.3])
+        if not camera:
+            Ro = _exp_so3(np.array([[0.1, -0.2, 0.3]]))[0][0]       # the sensor is mounted off-centre and rotated
+            to = np.array([0.2, -0.1, 0.3])
         offset = _iso_pack(Ro[None], to[None])[0]
         Rn = R[vp] @ Ro                                             # n2w = X * offset
         tn = np.einsum("nij,j->ni", R[vp], to) + pos[vp]
@@ -473,17 +512,30 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
         Rp = R @ _exp_so3(np.stack([rng.normal(223 + q, n) for q in range(3)], axis=1) * perturb[1])[0]
         poses = _iso_pack(Rp, pos + perturb[0] * np.stack([rng.normal(220 + q, n) for q in range(3)], axis=1))
     poses[0] = poses_true[0]
-    zl = zl + noise_landmark * np.stack([rng.normal(230 + q, M) for q in range(dl)], axis=1)
+    if camera:
+        fx, fy, cx, cy = (float(v) for v in kcam)
+        third = zl[:, 2] if observation == "depth" else 1.0 / zl[:, 2]
+        zl = np.stack([(fx * zl[:, 0] + cx * zl[:, 2]) / zl[:, 2], (fy * zl[:, 1] + cy * zl[:, 2]) / zl[:, 2], third], axis=1)
+        info_l = np.diag([1.0, 1.0, 100.0 if observation == "depth" else 1000.0])
+        gross = np.array([50.0, 50.0, 0.5 * sensor_range if observation == "depth" else 0.5 / z_min])
+        zl = zl + np.stack([rng.normal(230 + q, M) for q in range(dl)], axis=1) / np.sqrt(np.diag(info_l))
+    else:
+        info_l = np.eye(dl) / noise_landmark ** 2
+        gross = sensor_range
+        zl = zl + noise_landmark * np.stack([rng.normal(230 + q, M) for q in range(dl)], axis=1)
     if outlier_frac > 0:
         bad = rng.uniform(240, M) < outlier_frac
-        zl = zl + bad[:, None] * sensor_range * (np.stack([rng.uniform(241 + q, M) for q in range(dl)], axis=1) * 2.0 - 1.0)
+        zl = zl + bad[:, None] * gross * (np.stack([rng.uniform(241 + q, M) for q in range(dl)], axis=1) * 2.0 - 1.0)
     points = points_true + perturb[2] * np.stack([rng.normal(250 + q, L) for q in range(dl)], axis=1)
     points[:fixed_landmarks] = points_true[:fixed_landmarks]
     hidx = np.arange(n, dtype=np.int32) - 1                         # pose 0 fixed
     nP, nL = n - 1, L - int(fixed_landmarks)
     pt_hidx = np.where(np.arange(L) < fixed_landmarks, -1, nP + np.arange(L) - int(fixed_landmarks)).astype(np.int32)
     dp = 3 if se2 else 6
-    return dict(kind=kind, n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=vi, vj=vj, Z=Z, omega=np.tile(info.T.reshape(1, dp * dp), (E, 1)),
-                vp=vp, vl=vl, zl=zl, omega_l=np.tile((np.eye(dl) / noise_landmark ** 2).reshape(1, dl * dl), (M, 1)),
-                offset=offset, poses=poses, poses_true=poses_true, points=points, points_true=points_true, hidx=hidx,
-                pt_hidx=pt_hidx)
+    out = dict(kind=kind, n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=vi, vj=vj, Z=Z, omega=np.tile(info.T.reshape(1, dp * dp), (E, 1)),
+               vp=vp, vl=vl, zl=zl, omega_l=np.tile(info_l.reshape(1, dl * dl), (M, 1)),
+               offset=offset, poses=poses, poses_true=poses_true, points=points, points_true=points_true, hidx=hidx,
+               pt_hidx=pt_hidx)
+    if camera:
+        out.update(observation=observation, kcam=np.array([float(v) for v in kcam]))
+    return out

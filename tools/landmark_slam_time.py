@@ -1,5 +1,7 @@
 #!/usr/bin/env python
-"""Landmark SLAM (odometry + point landmarks, openslam_g2o_amd.synthetic.make_landmark_slam), 2-D and 3-D:
+"""Landmark SLAM (odometry + point landmarks, openslam_g2o_amd.synthetic.make_landmark_slam), 2-D and 3-D; --kinds takes
+se2, se3 (EdgeSE2PointXY / EdgeSE3PointXYZ) and depth, disparity (3-D with EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity
+observations of one camera, g2ohip_pg_set_landmark_camera_edges):
 
   default   ms per Levenberg-Marquardt iteration on a large generated graph (a) with the device front end
             (g2ohip_pg_set_landmark_edges: estimates, errors and Jacobians stay on the device) and (b) with the same library
@@ -17,7 +19,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from openslam_g2o_amd import lm, synthetic as S
-from tests import landmark_helpers as LH
+from tests import landmark_helpers as LH, landmark_camera_helpers as CH
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--drift", action="store_true")
@@ -41,11 +43,25 @@ def emit(d):
             f.write(line + "\n")
 
 
+CAMERA = ("depth", "disparity")
+
+
+def make_graph(kind, n, L, **kw):
+    if kind in CAMERA:
+        return S.make_landmark_slam("se3", n, L, observation=kind, **kw)
+    return S.make_landmark_slam(kind, n, L, **kw)
+
+
 if args.drift:
-    for kind, (n, L) in LH.LM_CASES.items():
-        g = LH.lm_test_graph(kind)
-        a = LH.oracle_lm_run(g, 10, dense=False)
-        b = LH.oracle_lm_run(g, 10, dense=True)
+    for kind in args.kinds.split(","):
+        if kind in CAMERA:
+            (_, n, L), g = CH.GRAPH, CH.lm_test_graph(kind)
+            a = CH.oracle_lm_run(g, 10, dense=False)
+            b = CH.oracle_lm_run(g, 10, dense=True)
+        else:
+            (n, L), g = LH.LM_CASES[kind], LH.lm_test_graph(kind)
+            a = LH.oracle_lm_run(g, 10, dense=False)
+            b = LH.oracle_lm_run(g, 10, dense=True)
         emit({"what": "oracle_drift", "kind": kind, "poses": n, "landmarks": L, "observations": int(g["M"]),
               "relative_chi2_gap": [abs(x - y) / y for x, y in zip(a[1], b[1])], "chi2_schur": a[1], "trials_schur": a[3],
               "trials_full_system": b[3]})
@@ -60,7 +76,7 @@ def spread(v):
 
 
 for kind in args.kinds.split(","):
-    g = S.make_landmark_slam(kind, args.poses, args.landmarks, max_obs=args.max_obs)
+    g = make_graph(kind, args.poses, args.landmarks, max_obs=args.max_obs)
     dp, dl = LH.dims(g)
     size = {"kind": kind, "poses": g["n"], "landmarks": g["L"], "odometry_edges": int(g["E"]), "observations": int(g["M"])}
     # (a) device front end
@@ -117,7 +133,7 @@ for kind in args.kinds.split(","):
     def feed_err(k, err):
         err = np.ascontiguousarray(err)
         capi._check(h.L.g2ohip_set_edge_errors(h.h, k, capi._dp(err)), "setEdgeErrors")
-    host = LH.HostLandmarkGraph(g, lambda k, J0, J1, om, err: h.setEdgeData(k, J0, J1, om, err), h.x, h.chi2, feed_err)
+    host = (CH.HostCameraGraph if kind in CAMERA else LH.HostLandmarkGraph)(g, lambda k, J0, J1, om, err: h.setEdgeData(k, J0, J1, om, err), h.x, h.chi2, feed_err)
     lm.optimize(host, h, 2, "lm")
     ms_b, traj_b = [], None
     for r in range(max(2, args.reps // 2)):
