@@ -451,7 +451,11 @@ int g2ohip_ba_discard_top(g2ohip_solver* s);
  * vertex_se3.h:107-116), estimates and measurements as isometries [12] = R (column-major) | t,
  * information [n][6x6].  Edge set `set` was added with error_dim 3 / 6 and hessian indices of its two
  * vertices; vi/vj index the estimate array (all vertices, fixed ones included), hidx[v] = hessianIndex or -1.
- * The calls mirror the g2ohip_ba_* ones (set_edges after g2ohip_build_structure). */
+ * The calls mirror the g2ohip_ba_* ones (set_edges after g2ohip_build_structure).
+ * The set_edges / set_estimates entries of both front ends (g2ohip_ba_*, g2ohip_pg_*, the landmark half below) validate what
+ * they are handed against what is already bound BEFORE they commit any of it: a call rejected with G2OHIP_ERR_ARG leaves the
+ * previous edges and estimate tables bound and usable as they were (after a rejected FIRST g2ohip_*_set_estimates there is no
+ * table, and linearize / update / push / get_estimates return G2OHIP_ERR_STATE until a valid one arrives). */
 int g2ohip_pg_set_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const double* meas,
                         const double* info);
 int g2ohip_pg_set_estimates(g2ohip_solver* s, int n_vertices, const double* poses, const int32_t* hidx);

@@ -12,6 +12,7 @@
 // are done destination-major from precomputed contributor lists: deterministic, no fp64
 // atomics, same summation order as the reference's serial loops.
 #pragma once
+#include <cstring>
 #include <memory>
 
 #include "common.h"
@@ -327,8 +328,8 @@ class BlockSolver {
   bool mf_ready_ = false;
   int solve_matrix_free();
   void mf_prepare_lists();
-  void ba_validate();
-  void ba_validate_edges(const struct EdgeSet& es, const int* cam_v, const int* pt_v, size_t n) const;
+  void ba_validate_edges(const struct EdgeSet& es, const int* cam_v, const int* pt_v, size_t n, const int* cam_hidx, int nc,
+                         const int* pt_hidx, int np) const;
   bool ba_recompute_ok() const;
   bool ba_skip_hpl_ok() const;
   bool ba_fuse_ll_ok() const;
@@ -341,18 +342,50 @@ class BlockSolver {
   bool hpl_valid_ = true;
   bool ll_valid_ = true;   // Hll, b_l and the errors of the fused BA path match the last build_system
   bool ll_hbm_partial_ = false;   // ... but the Schur tiles that assembled them wrote b_l only (Hll and the errors stayed on chip)
-  void pg_validate();
-  void pg_validate_landmarks();
+  void pg_validate(const EdgeSet& es, const int* vi, const int* vj, size_t n, const int* hidx, int nv) const;
+  void pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv, const int* pt_hidx,
+                             int np) const;
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                               const double* info, const double* offset, const double* kcam);
+  // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
+  // values, their backup (an estimate stack of depth one) and every vertex's index in the system (-1: fixed).
+  // Validate, then commit: every committed (edge binding, table) pair has been validated against each other when the later of
+  // the two was committed.  A set_* entry hands its CANDIDATE to ba_validate_edges / pg_validate / pg_validate_landmarks before
+  // it writes any member, so a rejected call leaves the previous binding and tables as they were, and nothing is rolled back.
+  struct EstimateTable {
+    DevBuf<double> val, bak;
+    DevBuf<int> hidx;
+    std::vector<int> h_hidx;   // host copy: index validation and same()
+    int n = 0, stride = 0;     // vertices, doubles per vertex
+    size_t scalars() const { return (size_t)n * stride; }
+    bool same(int count, int str, const int* h) const {   // the committed tables with (possibly) new values?
+      return count == n && str == stride && val.p && std::memcmp(h_hidx.data(), h, sizeof(int) * (size_t)n) == 0;
+    }
+    void set_values(const double* v, hipStream_t st) { val.upload(v, scalars(), st); }   // (after same(): no reallocation)
+    void commit(int count, int str, const double* v, const int* h, hipStream_t st) {
+      n = count;
+      stride = str;
+      h_hidx.assign(h, h + count);
+      val.upload(v, scalars(), st);
+      hidx.upload(h, (size_t)count, st);
+      bak.alloc(scalars());
+    }
+    void push(hipStream_t st) { copy(bak.p, val.p, st); }
+    void pop(hipStream_t st) { copy(val.p, bak.p, st); }
+    void download(double* h, hipStream_t st) const { val.download(h, scalars(), st); }
+    void copy(double* dst, const double* src, hipStream_t st) const {
+      if (n > 0) G2OHIP_HIP_CHECK(hipMemcpyAsync(dst, src, scalars() * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+  };
   struct BaFrontEnd {
-    int set = -1, n_edges = 0, n_cams = 0, n_points = 0;
+    int set = -1, n_edges = 0;
+    EstimateTable cams, pts;    // T[12] per camera, (x, y, z) per point
     double f = 0, cx = 0, cy = 0;
     int n_classes = 1;          // edge classes (ba_set_edges_classes): > 1 = the class of an observation rides in the top byte of its
     DevBuf<double> ctab;        // camera index, ctab[5 c] = (f, cx, cy, robust kernel kind, delta)
     std::vector<double> h_ctab;
-    DevBuf<int> cam_v, pt_v, cam_hidx, pt_hidx, edge_hpl;
-    std::vector<int> h_cam_v, h_pt_v, h_cam_hidx, h_pt_hidx;   // host copies: index validation (ba_validate)
+    DevBuf<int> cam_v, pt_v, edge_hpl;
+    std::vector<int> h_cam_v, h_pt_v;   // host copies: index validation (ba_validate_edges)
     // which estimates the assembled system was built from (back-substitution re-evaluates the Jacobians from them)
     long est_version = 0, bak_version = 0, sys_version = -1;
     int sys_kind = 0;
@@ -361,7 +394,7 @@ class BlockSolver {
     bool err_valid = false, jac_valid = false;   // errors / Jacobians of the set match the current estimates
     DevBuf<double> chi_part;                     // per workgroup of ba_linearize_kernel: partial chi2 (folded into d_red_multi)
     bool fused_ok = false;   // every Hpl block has exactly one observation: fused on-the-fly assembly allowed
-    DevBuf<double> meas, cams, pts, cams_bak, pts_bak;
+    DevBuf<double> meas;
     DevBuf<double> meas_pm, omega_pm;   // pose-major copies (observation-list order of the pose side)
     DevBuf<int> pt_pm, cam_pm;
     DevBuf<double> meas_lm, omega_lm;   // landmark-major copies
@@ -386,7 +419,7 @@ class BlockSolver {
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
   // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one ParameterCamera
   // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges).  Vertex 0 of an observation
-  // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); pt_hidx[v] is the landmark's index in
+  // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); points.hidx[v] is the landmark's index in
   // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
   // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
   // Schur on (landmarks marginalised) is the configuration the front end is meant for.  With do_schur = 0 and landmarks in the
@@ -395,16 +428,18 @@ class BlockSolver {
   // OracleSolver(schur=False) computes); the landmark part of x keeps the zeros of build_structure, so pg_update leaves the
   // landmarks where they are.  The front end adds nothing of its own to that path.
   struct PgFrontEnd {
-    int set = -1, type = 0, nv = 0;
-    DevBuf<int> vi, vj, hidx;
-    std::vector<int> h_vi, h_vj, h_hidx;
-    DevBuf<double> meas, poses, poses_bak;
+    int set = -1, type = 0;
+    DevBuf<int> vi, vj;
+    std::vector<int> h_vi, h_vj;   // host copies: index validation (pg_validate)
+    DevBuf<double> meas;
+    EstimateTable poses;           // (x, y, theta) or T[12] per pose
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
-    int lm_set = -1, lm_type = 0, n_points = 0;
-    DevBuf<int> vp, vl, pt_hidx;
-    std::vector<int> h_vp, h_vl, h_pt_hidx;   // host copies: index validation (pg_validate_landmarks)
-    DevBuf<double> lm_meas, points, points_bak;
+    int lm_set = -1, lm_type = 0;
+    DevBuf<int> vp, vl;
+    std::vector<int> h_vp, h_vl;   // host copies: index validation (pg_validate_landmarks)
+    DevBuf<double> lm_meas;
+    EstimateTable points;          // (x, y) or (x, y, z) per landmark
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
     double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
   } pg_;

@@ -3182,7 +3182,7 @@ void BlockSolver::launch_ba_landmarks(bool write_hpl) {
     constexpr int GG = g;
     constexpr bool CLS = cls;
     hipLaunchKernelGGL((ba_assemble_landmarks_kernel<GG, CLS>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p,
-                       es.vl_ent.p, ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.hpl_lm.p, ba_.f,
+                       es.vl_ent.p, ba_.cams.val.p, ba_.pts.val.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.hpl_lm.p, ba_.f,
                        ba_.cx, ba_.cy, es.kernel_kind, es.delta, d_Hll.p, d_b.p + sizeP, d_Hpl.p, es.own_err.p, ba_.omega_identity ? 1 : 0,
                        d_pl_colptr.p, write_hpl ? 1 : 0, ba_.ctab.p);
   };
@@ -3268,7 +3268,7 @@ void BlockSolver::launch_ba_poses() {
     constexpr int GG = g;
     constexpr bool CLS = cls;
     hipLaunchKernelGGL((ba_assemble_poses_kernel<GG, CLS>), dim3(grid_for((size_t)nPk * GG)), dim3(kThreads), 0, st_, nPk, es.vp_ptr.p,
-                       ba_.cams.p, ba_.pts.p, ba_.cam_pm.p, ba_.pt_pm.p, ba_.meas_pm.p, ba_.omega_pm.p, ba_.f, ba_.cx, ba_.cy,
+                       ba_.cams.val.p, ba_.pts.val.p, ba_.cam_pm.p, ba_.pt_pm.p, ba_.meas_pm.p, ba_.omega_pm.p, ba_.f, ba_.cx, ba_.cy,
                        es.kernel_kind, es.delta, d_Hpp.p, d_pp_diag.p, d_b.p, es.first_pose ? 0 : 1, ba_.omega_identity ? 1 : 0,
                        pact, ba_.ctab.p);
   };
@@ -3289,9 +3289,9 @@ void BlockSolver::build_system_impl() {
     EdgeSet& es = *esp;
     ++set_index;
     if (es.n == 0) continue;
-    if (set_index == ba_.set && ba_.n_classes > 1 && !(ba_fused && ba_.fused_ok && ba_.n_cams > 0))
+    if (set_index == ba_.set && ba_.n_classes > 1 && !(ba_fused && ba_.fused_ok && ba_.cams.n > 0))
       throw StateFailure("build_system: a BA edge set with edge classes needs the fused path (option ba_fused) and its estimates");
-    if (set_index == ba_.set && ba_fused && ba_.fused_ok && ba_.n_cams > 0) {
+    if (set_index == ba_.set && ba_fused && ba_.fused_ok && ba_.cams.n > 0) {
       // fused EdgeProjectXYZ2UV path: errors + Jacobians evaluated inside the assembly kernels
       ba_.sys_version = ba_.est_version;
       ba_.sys_kind = es.kernel_kind;
@@ -3592,14 +3592,14 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
       constexpr bool CLS = cls;
       if (fll)
         hipLaunchKernelGGL((ba_schur_tile_kernel<GG, true, CLS>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,
-                           ba_.cams.p, ba_.pts.p, (const int*)nullptr, (const int*)nullptr, ba_.ll_meas.p, ba_.ll_omega.p, ba_.f, ba_.cx,
+                           ba_.cams.val.p, ba_.pts.val.p, (const int*)nullptr, (const int*)nullptr, ba_.ll_meas.p, ba_.ll_omega.p, ba_.f, ba_.cx,
                            ba_.cy,
                            es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,
                            d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, ba_.ll_rec.p, ba_.tile_ll.p, ba_.ll_edge.p,
                            (double*)nullptr, d_tile_q2.p, schur_abl, d_slot_lm.p, ba_.ctab.p);
       else
         hipLaunchKernelGGL((ba_schur_tile_kernel<GG, false, CLS>), dim3(n_tiles_), dim3(kThreads), schur_lds_bytes_, st_, d_tile_lm0.p,
-                           ba_.cams.p, ba_.pts.p, ba_.cam_q.p, ba_.pt_q.p, ba_.meas_q.p, ba_.omega_q.p, ba_.f, ba_.cx, ba_.cy,
+                           ba_.cams.val.p, ba_.pts.val.p, ba_.cam_q.p, ba_.pt_q.p, ba_.meas_q.p, ba_.omega_q.p, ba_.f, ba_.cx, ba_.cy,
                            es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_td_diag.p, d_td_ptr.p,
                            d_te_pack.p, d_te_lm.p, d_Pd.p, d_Pr.p, d_Hll.p, d_lam.p, (const int4*)nullptr, (const int4*)nullptr,
                            (const int*)nullptr, (double*)nullptr, d_tile_q2.p, 1, d_slot_lm.p, ba_.ctab.p);
@@ -4275,7 +4275,7 @@ void BlockSolver::solve_back_substitute_impl() {
       with_bool(ba_.n_classes > 1, [&](auto cls) {
         constexpr bool CLS = cls;
         hipLaunchKernelGGL((ba_back_substitute_slots_kernel<CLS>), dim3(n_tiles_), dim3(kThreads), 0, st_, d_tile_lm0.p, ba_.tile_ll.p,
-                           ba_.ll_rec.p, ba_.ll_row.p, ba_.ll_meas.p, ba_.ll_omega.p, ba_.cams.p, ba_.pts.p, ba_.f, ba_.cx, ba_.cy,
+                           ba_.ll_rec.p, ba_.ll_row.p, ba_.ll_meas.p, ba_.ll_omega.p, ba_.cams.val.p, ba_.pts.val.p, ba_.f, ba_.cx, ba_.cy,
                            es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p, d_x.p + sizeP, ba_.ctab.p);
       });
     } else {
@@ -4283,7 +4283,7 @@ void BlockSolver::solve_back_substitute_impl() {
         constexpr int GG = g;
         constexpr bool CLS = cls;
         hipLaunchKernelGGL((ba_back_substitute_kernel<GG, CLS>), dim3(grid_for((size_t)nL_ * GG)), dim3(kThreads), 0, st_, nL_, es.vl_ptr.p,
-                           ba_.cams.p, ba_.pts.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.row_lm.p, ba_.f,
+                           ba_.cams.val.p, ba_.pts.val.p, ba_.cam_lm.p, ba_.pt_lm.p, ba_.meas_lm.p, ba_.omega_lm.p, ba_.row_lm.p, ba_.f,
                            ba_.cx, ba_.cy, es.kernel_kind, es.delta, ba_.omega_identity ? 1 : 0, d_Dinv.p, d_b.p + sizeP, d_x.p,
                            d_x.p + sizeP, ba_.ctab.p);
       };
@@ -4829,7 +4829,7 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
       camc[k] = cam_vertex[k] | (edge_class[k] << 24);
     }
   }
-  ba_validate_edges(es, cam_vertex, point_vertex, n);
+  ba_validate_edges(es, cam_vertex, point_vertex, n, ba_.cams.h_hidx.data(), ba_.cams.n, ba_.pts.h_hidx.data(), ba_.pts.n);
   // Hpl block written by each edge; the fused assembly requires one observation per (pose, landmark) pair
   std::vector<int> edge_hpl(n, -1);
   bool unique = es.first_lm && es.first_ol;
@@ -5045,7 +5045,7 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
 // assembly of the CURRENT estimates (an LM trial solves before it updates; a rejected trial pops back to them), with the
 // same robust kernel, and no other edge set may contribute pose-landmark blocks.
 bool BlockSolver::ba_recompute_ok() const {
-  if (!schur_ || p_ != 6 || l_ != 3 || ba_.set < 0 || !ba_fused || !ba_.fused_ok || ba_.n_cams <= 0) return false;
+  if (!schur_ || p_ != 6 || l_ != 3 || ba_.set < 0 || !ba_fused || !ba_.fused_ok || ba_.cams.n <= 0) return false;
   if (ba_.sys_version < 0 || ba_.sys_version != ba_.est_version) return false;
   const EdgeSet& bs = *sets_[ba_.set];
   if (bs.kernel_kind != ba_.sys_kind || bs.delta != ba_.sys_delta) return false;
@@ -5054,20 +5054,18 @@ bool BlockSolver::ba_recompute_ok() const {
   return true;
 }
 
-void BlockSolver::ba_validate() {
-  if (ba_.set < 0 || ba_.h_cam_v.empty() || ba_.h_cam_hidx.empty()) return;
-  ba_validate_edges(*sets_[ba_.set], ba_.h_cam_v.data(), ba_.h_pt_v.data(), ba_.h_cam_v.size());
-}
-// the edges' (camera, point) indices against the estimate tables and the edge set's vertices (nothing to check before the
-// estimates are there: ba_set_estimates validates then)
-void BlockSolver::ba_validate_edges(const EdgeSet& es, const int* cam_v, const int* pt_v, size_t n) const {
-  if (n == 0 || ba_.h_cam_hidx.empty()) return;
-  const int nc = (int)ba_.h_cam_hidx.size(), np = (int)ba_.h_pt_hidx.size();
+// The validators take the CANDIDATE edge indices and estimate tables: the committed ones or the ones a set_* entry has just been
+// handed (EstimateTable in block_solver.h).  Nothing to check while one of the two sides is missing: the entry that brings
+// the second one validates.
+// the edges' (camera, point) indices against the estimate tables and the edge set's vertices
+void BlockSolver::ba_validate_edges(const EdgeSet& es, const int* cam_v, const int* pt_v, size_t n, const int* cam_hidx, int nc,
+                                    const int* pt_hidx, int np) const {
+  if (n == 0 || nc == 0) return;
   for (size_t k = 0; k < n; ++k) {
     const int c = cam_v[k], q = pt_v[k];
     if (c < 0 || c >= nc) throw ArgFailure("ba: camera index " + std::to_string(c) + " of edge " + std::to_string(k) + " outside the estimate table");
     if (q < 0 || q >= np) throw ArgFailure("ba: point index " + std::to_string(q) + " of edge " + std::to_string(k) + " outside the estimate table");
-    const int hc = ba_.h_cam_hidx[c], hp = ba_.h_pt_hidx[q];
+    const int hc = cam_hidx[c], hp = pt_hidx[q];
     if (hc >= nP_ || hp >= nL_) throw ArgFailure("ba: hessian index of an estimate outside the structure");
     const int v1 = hc < 0 ? -1 : hc, v0 = hp < 0 ? -1 : nP_ + hp;
     if (es.v1[k] != v1 || es.v0[k] != v0)
@@ -5076,43 +5074,40 @@ void BlockSolver::ba_validate_edges(const EdgeSet& es, const int* cam_v, const i
   }
 }
 
-void BlockSolver::pg_validate() {
-  if (pg_.set < 0 || pg_.h_vi.empty() || pg_.h_hidx.empty()) return;
-  const EdgeSet& es = *sets_[pg_.set];
-  const int nv = (int)pg_.h_hidx.size();
-  for (size_t k = 0; k < pg_.h_vi.size(); ++k) {
-    const int a = pg_.h_vi[k], b = pg_.h_vj[k];
+void BlockSolver::pg_validate(const EdgeSet& es, const int* vi, const int* vj, size_t n, const int* hidx, int nv) const {
+  if (n == 0 || nv == 0) return;
+  for (size_t k = 0; k < n; ++k) {
+    const int a = vi[k], b = vj[k];
     if (a < 0 || a >= nv || b < 0 || b >= nv) throw ArgFailure("pg: vertex index of edge " + std::to_string(k) + " outside the estimate table");
-    const int ha = pg_.h_hidx[a], hb = pg_.h_hidx[b];
+    const int ha = hidx[a], hb = hidx[b];
     if (ha >= nP_ || hb >= nP_) throw ArgFailure("pg: hessian index of an estimate outside the structure");
     if (es.v0[k] != (ha < 0 ? -1 : ha) || es.v1[k] != (hb < 0 ? -1 : hb))
       throw ArgFailure("pg: edge " + std::to_string(k) + ": the estimates' hessian indices differ from the edge set's");
   }
 }
 
-// the landmark half: hidx_pose[vp[k]] == v0[k] and hidx_point[vl[k]] == v1[k] of the observation set (whatever of the tables
-// has been handed over so far)
-void BlockSolver::pg_validate_landmarks() {
-  if (pg_.lm_set < 0 || pg_.h_vp.empty()) return;
-  const EdgeSet& es = *sets_[pg_.lm_set];
-  const int nv = (int)pg_.h_hidx.size(), np = (int)pg_.h_pt_hidx.size();
+// the landmark half: hidx[vp[k]] == v0[k] and pt_hidx[vl[k]] == v1[k] of the observation set (whatever of the tables has been
+// handed over so far: nv == 0 / np == 0 = not yet)
+void BlockSolver::pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv,
+                                        const int* pt_hidx, int np) const {
+  if (n == 0) return;
   for (int v = 0; v < np; ++v) {
-    const int h = pg_.h_pt_hidx[v];
+    const int h = pt_hidx[v];
     if (h != -1 && (h < nP_ || h >= nP_ + nL_)) throw ArgFailure("pg: hessian index of landmark " + std::to_string(v) + " outside the landmark range of the structure");
   }
-  for (size_t k = 0; k < pg_.h_vp.size(); ++k) {
-    const int a = pg_.h_vp[k], b = pg_.h_vl[k];
+  for (size_t k = 0; k < n; ++k) {
+    const int a = vp[k], b = vl[k];
     if (a < 0 || b < 0) throw ArgFailure("pg: negative vertex index in landmark edge " + std::to_string(k));
     if (nv > 0) {
       if (a >= nv) throw ArgFailure("pg: pose index of landmark edge " + std::to_string(k) + " outside the estimate table");
-      const int ha = pg_.h_hidx[a];
+      const int ha = hidx[a];
       if (ha >= nP_) throw ArgFailure("pg: hessian index of an estimate outside the structure");
       if (es.v0[k] != (ha < 0 ? -1 : ha))
         throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the pose's hessian index differs from the edge set's");
     }
     if (np > 0) {
       if (b >= np) throw ArgFailure("pg: landmark index of landmark edge " + std::to_string(k) + " outside the landmark table");
-      const int hb = pg_.h_pt_hidx[b];
+      const int hb = pt_hidx[b];
       if (es.v1[k] != (hb < 0 ? -1 : hb))
         throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the landmark's hessian index differs from the edge set's");
     }
@@ -5130,39 +5125,30 @@ void BlockSolver::ba_set_estimates(int n_cams, const double* cams, const int* ca
   // The caller of every iteration (the g2o adapter: setEstimate of all vertices before buildSystem) hands over the same
   // tables with new values: only the estimates move -- no index check, no re-upload of the index mapping, and the captured
   // launch sequences stay (the device addresses are the same).
-  if (n_cams == ba_.n_cams && n_points == ba_.n_points && ba_.cams.p && ba_.pts.p && (int)ba_.h_cam_hidx.size() == n_cams &&
-      (int)ba_.h_pt_hidx.size() == n_points && std::memcmp(ba_.h_cam_hidx.data(), cam_hidx, sizeof(int) * (size_t)n_cams) == 0 &&
-      std::memcmp(ba_.h_pt_hidx.data(), point_hidx, sizeof(int) * (size_t)n_points) == 0) {
-    ++ba_.est_version;
-    ba_.err_valid = ba_.jac_valid = false;
-    chi2_valid_ = false;
-    ba_.has_backup = false;
-    ba_.cams.upload(cams, (size_t)n_cams * 12, st_);
-    ba_.pts.upload(points, (size_t)n_points * 3, st_);
-    G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
-    return;
+  const bool same = ba_.cams.same(n_cams, 12, cam_hidx) && ba_.pts.same(n_points, 3, point_hidx);
+  if (!same) {
+    if (ba_.set >= 0)
+      ba_validate_edges(*sets_[ba_.set], ba_.h_cam_v.data(), ba_.h_pt_v.data(), ba_.h_cam_v.size(), cam_hidx, n_cams, point_hidx, n_points);
+    invalidate_graphs();
   }
-  invalidate_graphs();
-  ba_.n_cams = n_cams;
-  ba_.n_points = n_points;
   ++ba_.est_version;
-  ba_.h_cam_hidx.assign(cam_hidx, cam_hidx + n_cams);
-  ba_.h_pt_hidx.assign(point_hidx, point_hidx + n_points);
-  ba_validate();
-  ba_.cams.upload(cams, (size_t)n_cams * 12, st_);
-  ba_.pts.upload(points, (size_t)n_points * 3, st_);
-  ba_.cam_hidx.upload(cam_hidx, n_cams, st_);
-  ba_.pt_hidx.upload(point_hidx, n_points, st_);
-  ba_.cams_bak.alloc((size_t)n_cams * 12);
-  ba_.pts_bak.alloc((size_t)n_points * 3);
+  ba_.err_valid = ba_.jac_valid = false;
+  chi2_valid_ = false;
   ba_.has_backup = false;
+  if (same) {
+    ba_.cams.set_values(cams, st_);
+    ba_.pts.set_values(points, st_);
+  } else {
+    ba_.cams.commit(n_cams, 12, cams, cam_hidx, st_);
+    ba_.pts.commit(n_points, 3, points, point_hidx, st_);
+  }
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 void BlockSolver::ba_get_estimates(double* cams, double* points) {
-  if (ba_.n_cams <= 0) throw StateFailure("ba_get_estimates before ba_set_estimates");
-  if (cams) ba_.cams.download(cams, (size_t)ba_.n_cams * 12, st_);
-  if (points) ba_.pts.download(points, (size_t)ba_.n_points * 3, st_);
+  if (ba_.cams.n <= 0) throw StateFailure("ba_get_estimates before ba_set_estimates");
+  if (cams) ba_.cams.download(cams, st_);
+  if (points) ba_.pts.download(points, st_);
 }
 
 // The estimates of SELECTED vertices (what a caller with a few host-side edges needs of a trial: the adapter's hybrid loop reads the
@@ -5179,13 +5165,13 @@ __global__ void ba_gather_estimates_kernel(int nc, int np, const int* __restrict
 }
 
 void BlockSolver::ba_get_estimates_of(int n_cams, const int* cam_idx, double* cams, int n_points, const int* point_idx, double* points) {
-  if (ba_.n_cams <= 0) throw StateFailure("ba_get_estimates_of before ba_set_estimates");
+  if (ba_.cams.n <= 0) throw StateFailure("ba_get_estimates_of before ba_set_estimates");
   if (n_cams < 0 || n_points < 0 || (n_cams > 0 && (!cam_idx || !cams)) || (n_points > 0 && (!point_idx || !points)))
     throw ArgFailure("ba_get_estimates_of: bad arguments");
   for (int i = 0; i < n_cams; ++i)
-    if (cam_idx[i] < 0 || cam_idx[i] >= ba_.n_cams) throw ArgFailure("ba_get_estimates_of: camera index out of range");
+    if (cam_idx[i] < 0 || cam_idx[i] >= ba_.cams.n) throw ArgFailure("ba_get_estimates_of: camera index out of range");
   for (int i = 0; i < n_points; ++i)
-    if (point_idx[i] < 0 || point_idx[i] >= ba_.n_points) throw ArgFailure("ba_get_estimates_of: point index out of range");
+    if (point_idx[i] < 0 || point_idx[i] >= ba_.pts.n) throw ArgFailure("ba_get_estimates_of: point index out of range");
   const size_t n = (size_t)n_cams * 12 + (size_t)n_points * 3;
   if (n == 0) return;
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
@@ -5194,8 +5180,8 @@ void BlockSolver::ba_get_estimates_of(int n_cams, const int* cam_idx, double* ca
   std::copy(point_idx, point_idx + n_points, idx.begin() + n_cams);
   ba_.sel_idx.upload(idx, st_);
   ba_.sel_out.alloc(n);
-  hipLaunchKernelGGL(ba_gather_estimates_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, n_cams, n_points, ba_.sel_idx.p, ba_.cams.p,
-                     ba_.pts.p, ba_.sel_out.p);
+  hipLaunchKernelGGL(ba_gather_estimates_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, n_cams, n_points, ba_.sel_idx.p, ba_.cams.val.p,
+                     ba_.pts.val.p, ba_.sel_out.p);
   G2OHIP_HIP_CHECK(hipGetLastError());
   std::vector<double> h(n);
   ba_.sel_out.download(h.data(), n, st_);   // (synchronises)
@@ -5209,7 +5195,7 @@ void BlockSolver::ba_get_estimates_of(int n_cams, const int* cam_idx, double* ca
 // its vertices while piece k + 1 is still crossing PCIe -- and the whole copy runs next to the error evaluation of the trial.
 // Anything that WRITES the estimates afterwards (update, pop, set_estimates) makes the solver's stream wait for the copy first.
 void BlockSolver::ba_fetch_begin(double* cams, double* points, int point_pieces) {
-  if (ba_.n_cams <= 0) throw StateFailure("ba_fetch_begin before ba_set_estimates");
+  if (ba_.cams.n <= 0) throw StateFailure("ba_fetch_begin before ba_set_estimates");
   if (!cams || !points || point_pieces < 1 || point_pieces > kFetchMaxPieces - 1) throw ArgFailure("ba_fetch_begin: bad arguments");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   if (!fetch_st_) {
@@ -5219,12 +5205,12 @@ void BlockSolver::ba_fetch_begin(double* cams, double* points, int point_pieces)
   }
   G2OHIP_HIP_CHECK(hipEventRecord(fetch_fork_, st_));
   G2OHIP_HIP_CHECK(hipStreamWaitEvent(fetch_st_, fetch_fork_, 0));
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(cams, ba_.cams.p, (size_t)ba_.n_cams * 12 * sizeof(double), hipMemcpyDeviceToHost, fetch_st_));
+  G2OHIP_HIP_CHECK(hipMemcpyAsync(cams, ba_.cams.val.p, (size_t)ba_.cams.n * 12 * sizeof(double), hipMemcpyDeviceToHost, fetch_st_));
   G2OHIP_HIP_CHECK(hipEventRecord(fetch_ev_[0], fetch_st_));
-  const size_t np = (size_t)ba_.n_points, step = (np + point_pieces - 1) / point_pieces;
+  const size_t np = (size_t)ba_.pts.n, step = (np + point_pieces - 1) / point_pieces;
   for (int k = 0; k < point_pieces; ++k) {
     const size_t b = std::min(np, k * step), e = std::min(np, b + step);
-    if (e > b) G2OHIP_HIP_CHECK(hipMemcpyAsync(points + 3 * b, ba_.pts.p + 3 * b, (e - b) * 3 * sizeof(double), hipMemcpyDeviceToHost, fetch_st_));
+    if (e > b) G2OHIP_HIP_CHECK(hipMemcpyAsync(points + 3 * b, ba_.pts.val.p + 3 * b, (e - b) * 3 * sizeof(double), hipMemcpyDeviceToHost, fetch_st_));
     G2OHIP_HIP_CHECK(hipEventRecord(fetch_ev_[1 + k], fetch_st_));
   }
   fetch_pieces_ = 1 + point_pieces;
@@ -5240,7 +5226,7 @@ void BlockSolver::ba_fetch_fence() {
 }
 
 void BlockSolver::ba_linearize(bool jacobians) {
-  if (ba_.set < 0 || ba_.n_cams <= 0) throw StateFailure("ba_linearize: call ba_set_edges and ba_set_estimates first");
+  if (ba_.set < 0 || ba_.cams.n <= 0) throw StateFailure("ba_linearize: call ba_set_edges and ba_set_estimates first");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   EdgeSet& es = *sets_[ba_.set];
   const bool fused = ba_fused && ba_.fused_ok;
@@ -5266,7 +5252,7 @@ void BlockSolver::ba_linearize(bool jacobians) {
   const int lgrid = grid_for(es.n);
   if (d_red_multi.n < (sets_.size() + 1) * kMaxBlocks) d_red_multi.alloc((sets_.size() + 1) * kMaxBlocks);
   if (ba_.chi_part.n < (size_t)lgrid) ba_.chi_part.alloc(lgrid);
-  hipLaunchKernelGGL(ba_linearize_kernel, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.p, ba_.pts.p, ba_.cam_v.p,
+  hipLaunchKernelGGL(ba_linearize_kernel, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.val.p, ba_.pts.val.p, ba_.cam_v.p,
                      ba_.pt_v.p, ba_.meas.p, ba_.f, ba_.cx, ba_.cy, es.own_J0.p, es.own_J1.p, es.own_err.p, (jacobians && !fused) ? 1 : 0,
                      es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, ba_.chi_part.p,
                      ba_.n_classes > 1 ? ba_.ctab.p : (const double*)nullptr);
@@ -5282,16 +5268,16 @@ void BlockSolver::ba_linearize(bool jacobians) {
 
 void BlockSolver::ba_update() {
   require_structure();
-  if (ba_.n_cams <= 0) throw StateFailure("ba_update before ba_set_estimates");
+  if (ba_.cams.n <= 0) throw StateFailure("ba_update before ba_set_estimates");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   ba_.err_valid = ba_.jac_valid = false;
   ++ba_.est_version;
   ba_fetch_fence();
   if (profiling) tfe_.start(st_);
-  hipLaunchKernelGGL(ba_update_cams_kernel, dim3(grid_for(ba_.n_cams)), dim3(kThreads), 0, st_, ba_.n_cams, ba_.cams.p, ba_.cam_hidx.p,
+  hipLaunchKernelGGL(ba_update_cams_kernel, dim3(grid_for(ba_.cams.n)), dim3(kThreads), 0, st_, ba_.cams.n, ba_.cams.val.p, ba_.cams.hidx.p,
                      d_x.p);
-  hipLaunchKernelGGL(ba_update_pts_kernel, dim3(grid_for((size_t)ba_.n_points * 3)), dim3(kThreads), 0, st_, ba_.n_points, ba_.pts.p,
-                     ba_.pt_hidx.p, d_x.p + (size_t)nP_ * p_);
+  hipLaunchKernelGGL(ba_update_pts_kernel, dim3(grid_for((size_t)ba_.pts.n * 3)), dim3(kThreads), 0, st_, ba_.pts.n, ba_.pts.val.p,
+                     ba_.pts.hidx.p, d_x.p + (size_t)nP_ * p_);
   if (profiling) {
     tfe_.stop(st_);
     times.update = tfe_.seconds();
@@ -5302,10 +5288,10 @@ void BlockSolver::ba_update() {
 // estimate stack of depth one: what the LM trial loop needs (push / pop / discardTop,
 // optimization_algorithm_levenberg.cpp:96,135,139; base_vertex.h:96-99)
 void BlockSolver::ba_push() {
-  if (ba_.n_cams <= 0) throw StateFailure("ba_push before ba_set_estimates");
+  if (ba_.cams.n <= 0) throw StateFailure("ba_push before ba_set_estimates");
   if (ba_.has_backup) throw StateFailure("ba_push: the estimate stack holds one level");
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(ba_.cams_bak.p, ba_.cams.p, (size_t)ba_.n_cams * 12 * sizeof(double), hipMemcpyDeviceToDevice, st_));
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(ba_.pts_bak.p, ba_.pts.p, (size_t)ba_.n_points * 3 * sizeof(double), hipMemcpyDeviceToDevice, st_));
+  ba_.cams.push(st_);
+  ba_.pts.push(st_);
   ba_.has_backup = true;
   ba_.bak_version = ba_.est_version;
 }
@@ -5313,8 +5299,8 @@ void BlockSolver::ba_pop() {
   if (!ba_.has_backup) throw StateFailure("ba_pop without push");
   ba_.err_valid = ba_.jac_valid = false;
   ba_fetch_fence();
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(ba_.cams.p, ba_.cams_bak.p, (size_t)ba_.n_cams * 12 * sizeof(double), hipMemcpyDeviceToDevice, st_));
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(ba_.pts.p, ba_.pts_bak.p, (size_t)ba_.n_points * 3 * sizeof(double), hipMemcpyDeviceToDevice, st_));
+  ba_.cams.pop(st_);
+  ba_.pts.pop(st_);
   ba_.has_backup = false;
   ba_.est_version = ba_.bak_version;
 }
@@ -5336,11 +5322,11 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (!vi || !vj || !meas || !info) throw ArgFailure("pg_set_edges: null array");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n, ms = type == 1 ? 3 : 12;
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   pg_.set = set;
   pg_.type = type;
   pg_.h_vi.assign(vi, vi + n);
   pg_.h_vj.assign(vj, vj + n);
-  pg_validate();
   pg_.vi.upload(vi, n, st_);
   pg_.vj.upload(vj, n, st_);
   pg_.meas.upload(meas, n * ms, st_);
@@ -5357,36 +5343,26 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
 void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx) {
   if (pg_.type == 0) throw StateFailure("pg_set_estimates: call pg_set_edges first");
   if (nv <= 0 || !poses || !hidx) throw ArgFailure("pg_set_estimates: bad arguments");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const int ps = pg_.type == 1 ? 3 : 12;
+  const bool same = pg_.poses.same(nv, ps, hidx);   // (same tables, new values: see ba_set_estimates)
+  if (!same) {
+    pg_validate(*sets_[pg_.set], pg_.h_vi.data(), pg_.h_vj.data(), pg_.h_vi.size(), hidx, nv);
+    if (pg_.lm_set >= 0)
+      pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
+                            pg_.points.n);
+  }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
-  G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const size_t ps = pg_.type == 1 ? 3 : 12;
-  if (nv == pg_.nv && pg_.poses.p && (int)pg_.h_hidx.size() == nv && std::memcmp(pg_.h_hidx.data(), hidx, sizeof(int) * (size_t)nv) == 0) {
-    pg_.has_backup = false;   // (same tables, new values: see ba_set_estimates)
-    pg_.poses.upload(poses, (size_t)nv * ps, st_);
-    G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
-    return;
-  }
-  pg_.nv = nv;
-  pg_.h_hidx.assign(hidx, hidx + nv);
-  try {
-    pg_validate();
-    pg_validate_landmarks();
-  } catch (...) {   // (no estimate table rather than one the edges do not fit: pg_linearize refuses until a valid one arrives)
-    pg_.nv = 0;
-    pg_.h_hidx.clear();
-    throw;
-  }
-  pg_.poses.upload(poses, (size_t)nv * ps, st_);
-  pg_.hidx.upload(hidx, (size_t)nv, st_);
-  pg_.poses_bak.alloc((size_t)nv * ps);
   pg_.has_backup = false;
+  if (same) pg_.poses.set_values(poses, st_);
+  else pg_.poses.commit(nv, ps, poses, hidx, st_);
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 void BlockSolver::pg_get_estimates(double* poses) {
-  if (pg_.nv <= 0) throw StateFailure("pg_get_estimates before pg_set_estimates");
-  pg_.poses.download(poses, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12), st_);
+  if (pg_.poses.n <= 0) throw StateFailure("pg_get_estimates before pg_set_estimates");
+  pg_.poses.download(poses, st_);
 }
 
 // ---- ... its landmark half (EdgeSE2PointXY / EdgeSE3PointXYZ / EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity over
@@ -5419,7 +5395,7 @@ void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pos
   pg_bind_landmark_edges("pg_set_landmark_camera_edges", set, type, pose_vertex, point_vertex, meas, info, offset, kcam);
 }
 
-// what both entries share: the set's dimensions, index validation (rolled back when it fails), the uploads
+// what both entries share: the set's dimensions, index validation, the uploads
 void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
                                          const double* meas, const double* info, const double* offset, const double* kcam) {
   const std::string w(who);
@@ -5431,22 +5407,11 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure(w + ": null array");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
-  // (a failed validation must not leave half a binding)
-  const int old_set = pg_.lm_set, old_type = pg_.lm_type;
-  std::vector<int> old_vp = std::move(pg_.h_vp), old_vl = std::move(pg_.h_vl);
+  pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
   pg_.lm_set = set;
   pg_.lm_type = type;
   pg_.h_vp.assign(pose_vertex, pose_vertex + n);
   pg_.h_vl.assign(point_vertex, point_vertex + n);
-  try {
-    pg_validate_landmarks();
-  } catch (...) {
-    pg_.lm_set = old_set;
-    pg_.lm_type = old_type;
-    pg_.h_vp = std::move(old_vp);
-    pg_.h_vl = std::move(old_vl);
-    throw;
-  }
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
   for (int i = 0; i < 4; ++i) pg_.kcam[i] = kcam ? kcam[i] : (i < 2 ? 1.0 : 0.0);
   pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
@@ -5468,48 +5433,37 @@ void BlockSolver::pg_set_landmark_estimates(int n_points, const double* points, 
   require_structure();
   if (pg_.type == 0) throw StateFailure("pg_set_landmark_estimates: call pg_set_edges first");
   if (n_points <= 0 || !points || !hidx) throw ArgFailure("pg_set_landmark_estimates: bad arguments");
-  const size_t l = pg_.type == 1 ? 2 : 3;
-  if ((int)l != l_) throw ArgFailure("pg_set_landmark_estimates: the solver's landmark dimension does not fit the pose set's type");
+  const int l = pg_.type == 1 ? 2 : 3;
+  if (l != l_) throw ArgFailure("pg_set_landmark_estimates: the solver's landmark dimension does not fit the pose set's type");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const bool same = pg_.points.same(n_points, l, hidx);   // (same tables, new values: see ba_set_estimates)
+  if (!same) {
+    if (pg_.lm_set >= 0)
+      pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), pg_.poses.h_hidx.data(), pg_.poses.n,
+                            hidx, n_points);
+    invalidate_graphs();
+  }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
-  G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  if (n_points == pg_.n_points && pg_.points.p && (int)pg_.h_pt_hidx.size() == n_points &&
-      std::memcmp(pg_.h_pt_hidx.data(), hidx, sizeof(int) * (size_t)n_points) == 0) {
-    pg_.has_backup = false;   // (same tables, new values: see pg_set_estimates)
-    pg_.points.upload(points, (size_t)n_points * l, st_);
-    G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
-    return;
-  }
-  std::vector<int> old = std::move(pg_.h_pt_hidx);
-  pg_.h_pt_hidx.assign(hidx, hidx + n_points);
-  try {
-    pg_validate_landmarks();
-  } catch (...) {
-    pg_.h_pt_hidx = std::move(old);
-    throw;
-  }
-  invalidate_graphs();
-  pg_.n_points = n_points;
-  pg_.points.upload(points, (size_t)n_points * l, st_);
-  pg_.pt_hidx.upload(hidx, (size_t)n_points, st_);
-  pg_.points_bak.alloc((size_t)n_points * l);
   pg_.has_backup = false;
+  if (same) pg_.points.set_values(points, st_);
+  else pg_.points.commit(n_points, l, points, hidx, st_);
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 void BlockSolver::pg_get_landmark_estimates(double* points) {
-  if (pg_.n_points <= 0) throw StateFailure("pg_get_landmark_estimates before pg_set_landmark_estimates");
-  pg_.points.download(points, (size_t)pg_.n_points * (pg_.type == 1 ? 2 : 3), st_);
+  if (pg_.points.n <= 0) throw StateFailure("pg_get_landmark_estimates before pg_set_landmark_estimates");
+  pg_.points.download(points, st_);
 }
 
 void BlockSolver::pg_linearize(bool jacobians) {
-  if (pg_.set < 0 || pg_.nv <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
+  if (pg_.set < 0 || pg_.poses.n <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   EdgeSet& es = *sets_[pg_.set];
   if ((int)pg_.h_vi.size() != es.n) throw StateFailure("pg_linearize: the edge set has grown since pg_set_edges (g2ohip_update_structure): call pg_set_edges again");
   EdgeSet* el = pg_.lm_set >= 0 ? sets_[pg_.lm_set].get() : nullptr;
   if (el) {
-    if (pg_.n_points <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
+    if (pg_.points.n <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
     if ((int)pg_.h_vp.size() != el->n) throw StateFailure("pg_linearize: the landmark edge set has changed since pg_set_landmark_edges: call it again");
   }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
@@ -5521,44 +5475,30 @@ void BlockSolver::pg_linearize(bool jacobians) {
   if (jacobians) pg_.jac_valid = true;
   chi2_valid_ = false;
   if (pg_.type == 1)
-    hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.p, pg_.vi.p, pg_.vj.p,
+    hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
   else
-    hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.p, pg_.vi.p, pg_.vj.p,
+    hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
   if (el && el->n > 0) {
     prof.begin(KernelProf::kPgLandmark, st_);
     const dim3 grid(grid_for(el->n)), block(kThreads);
     const int jac = jacobians ? 1 : 0;
-    if (pg_.lm_type == 3) {
-      if (pg_landmark_staged)
-        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<true>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
-                           pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+    PgIso off;
+    for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
+    const PgKcam kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3]};
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      if (pg_.lm_type == 3)
+        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<STAGED>, grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p, pg_.vp.p,
+                           pg_.vl.p, pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
       else
-        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<false>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
-                           pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
-    } else if (pg_.lm_type == 5 || pg_.lm_type == 6) {
-      PgIso off;
-      for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
-      const PgKcam kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3]};
-      with_bool(pg_.lm_type == 6, [&](auto disparity) {
-        with_bool(pg_landmark_staged, [&](auto staged) {
-          constexpr bool DISPARITY = disparity, STAGED = staged;
-          hipLaunchKernelGGL((pg_se3_camera_linearize_kernel<DISPARITY, STAGED>), grid, block, 0, st_,
-                             el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, off, kc, el->own_J0.p, el->own_J1.p,
-                             el->own_err.p, jac);
+        dispatch_value<4, 5, 6>(pg_.lm_type, [&](auto obs) {
+          constexpr int OBS = obs;
+          hipLaunchKernelGGL((pg_se3_point_linearize_kernel<OBS, STAGED>), grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
+                             pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, off, kc, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
         });
-      });
-    } else {
-      PgIso off;
-      for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
-      if (pg_landmark_staged)
-        hipLaunchKernelGGL(pg_se3_pointxyz_linearize_kernel<true>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
-                           pg_.lm_meas.p, off, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
-      else
-        hipLaunchKernelGGL(pg_se3_pointxyz_linearize_kernel<false>, grid, block, 0, st_, el->n, pg_.poses.p, pg_.points.p, pg_.vp.p, pg_.vl.p,
-                           pg_.lm_meas.p, off, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
-    }
+    });
     prof.end(KernelProf::kPgLandmark, st_);
   }
   G2OHIP_HIP_CHECK(hipGetLastError());
@@ -5572,37 +5512,35 @@ void BlockSolver::pg_linearize(bool jacobians) {
 
 void BlockSolver::pg_update() {
   require_structure();
-  if (pg_.nv <= 0) throw StateFailure("pg_update before pg_set_estimates");
+  if (pg_.poses.n <= 0) throw StateFailure("pg_update before pg_set_estimates");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   pg_.err_valid = pg_.jac_valid = false;
   if (pg_.type == 1)
-    hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.nv)), dim3(kThreads), 0, st_, pg_.nv, pg_.poses.p, pg_.hidx.p, d_x.p);
+    hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, d_x.p);
   else
-    hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.nv)), dim3(kThreads), 0, st_, pg_.nv, pg_.poses.p, pg_.hidx.p, d_x.p);
-  if (pg_.n_points > 0) {
-    const size_t ns = (size_t)pg_.n_points * l_;
-    hipLaunchKernelGGL(pg_points_update_kernel, dim3(grid_for(ns)), dim3(kThreads), 0, st_, ns, l_, pg_.points.p, pg_.pt_hidx.p, d_x.p,
+    hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, d_x.p);
+  if (pg_.points.n > 0) {
+    const size_t ns = (size_t)pg_.points.n * l_;
+    hipLaunchKernelGGL(pg_points_update_kernel, dim3(grid_for(ns)), dim3(kThreads), 0, st_, ns, l_, pg_.points.val.p, pg_.points.hidx.p, d_x.p,
                        (size_t)nP_ * p_, nP_);
   }
   G2OHIP_HIP_CHECK(hipGetLastError());
 }
 
 void BlockSolver::pg_push() {
-  if (pg_.nv <= 0) throw StateFailure("pg_push before pg_set_estimates");
+  if (pg_.poses.n <= 0) throw StateFailure("pg_push before pg_set_estimates");
   if (pg_.has_backup) throw StateFailure("pg_push: the estimate stack holds one level");
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.poses_bak.p, pg_.poses.p, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12) * sizeof(double),
-                                  hipMemcpyDeviceToDevice, st_));
-  if (pg_.n_points > 0)
-    G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.points_bak.p, pg_.points.p, (size_t)pg_.n_points * l_ * sizeof(double), hipMemcpyDeviceToDevice, st_));
+  pg_.poses.push(st_);
+  pg_.points.push(st_);
   pg_.has_backup = true;
 }
 void BlockSolver::pg_pop() {
   if (!pg_.has_backup) throw StateFailure("pg_pop without push");
   pg_.err_valid = pg_.jac_valid = false;
-  G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.poses.p, pg_.poses_bak.p, (size_t)pg_.nv * (pg_.type == 1 ? 3 : 12) * sizeof(double),
-                                  hipMemcpyDeviceToDevice, st_));
-  if (pg_.n_points > 0)
-    G2OHIP_HIP_CHECK(hipMemcpyAsync(pg_.points.p, pg_.points_bak.p, (size_t)pg_.n_points * l_ * sizeof(double), hipMemcpyDeviceToDevice, st_));
+  pg_.poses.pop(st_);
+  pg_.points.pop(st_);
   pg_.has_backup = false;
 }
 void BlockSolver::pg_discard_top() {

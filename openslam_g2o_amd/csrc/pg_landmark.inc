@@ -2,7 +2,7 @@
 //   EdgeSE2PointXY::computeError / linearizeOplus    g2o/types/slam2d/edge_se2_pointxy.h:44-49, edge_se2_pointxy.cpp:66-90
 //   EdgeSE3PointXYZ::computeError / linearizeOplus   g2o/types/slam3d/edge_se3_pointxyz.cpp:95-131
 //   CacheSE3Offset::updateImpl                       g2o/types/slam3d/parameter_se3_offset.cpp:44-50 (w2n, w2l)
-//   EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity  g2o/types/slam3d/edge_se3_pointxyz_{depth,disparity}.cpp (see their kernel)
+//   EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity  g2o/types/slam3d/edge_se3_pointxyz_{depth,disparity}.cpp (see the SE3 kernel)
 //   VertexPointXY / VertexPointXYZ::oplusImpl        g2o/types/slam2d/vertex_point_xy.h:77-81, slam3d/vertex_pointxyz.h:48-51
 // Vertex 0 of an edge is the pose, vertex 1 the landmark.  Output in the layout of g2ohip_set_edge_data: J0 [n][d x dim0],
 // J1 [n][d x dim1] column-major, err [n][d].
@@ -82,71 +82,31 @@ struct PgIso {
   double v[12];
 };
 
-// w2n = (X offset)^-1, w2l = X^-1, e = w2n l - z; J = Roff' [-I | 2 [w2l l]x | R(w2l)], split 6 | 3
-template <bool STAGED>
-__global__ void __launch_bounds__(kThreads) pg_se3_pointxyz_linearize_kernel(int n, const double* __restrict__ poses,
-                                                                           const double* __restrict__ points, const int* __restrict__ vp,
-                                                                           const int* __restrict__ vl, const double* __restrict__ meas,
-                                                                           PgIso offset, double* __restrict__ J0,
-                                                                           double* __restrict__ J1, double* __restrict__ err, int jac) {
-  __shared__ double lds[STAGED ? kThreads * 19 : 1];
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int kk = min(k, n - 1);
-  const double* Xp = poses + 12 * (size_t)vp[kk];
-  const double* lp = points + 3 * (size_t)vl[kk];
-  double X[12], n2w[12], w2n[12], w2l[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) X[i] = Xp[i];
-  const double l[3] = {lp[0], lp[1], lp[2]};
-  pg_iso_mul(X, offset.v, n2w);
-  pg_iso_inv(n2w, w2n);
-  double e[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    e[r] = PG_R(w2n, r, 0) * l[0] + PG_R(w2n, r, 1) * l[1] + PG_R(w2n, r, 2) * l[2] + w2n[9 + r] - meas[3 * (size_t)kk + r];
-  pg_store<STAGED, 3>(lds, e, err, k, n);
-  if (!jac) return;
-  pg_iso_inv(X, w2l);
-  double Z[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) Z[r] = PG_R(w2l, r, 0) * l[0] + PG_R(w2l, r, 1) * l[1] + PG_R(w2l, r, 2) * l[2] + w2l[9 + r];
-  // J (3 x 9, column-major) as EdgeSE3PointXYZ::linearizeOplus fills it
-  const double J[27] = {-1, 0, 0, 0, -1, 0, 0, 0, -1,
-                        0, 2 * Z[2], -2 * Z[1], -2 * Z[2], 0, 2 * Z[0], 2 * Z[1], -2 * Z[0], 0,
-                        w2l[0], w2l[1], w2l[2], w2l[3], w2l[4], w2l[5], w2l[6], w2l[7], w2l[8]};
-  double a[18], b[9];
-#pragma unroll
-  for (int cidx = 0; cidx < 9; ++cidx)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      // row r of inverseOffset().rotation() = column r of R(offset)
-      const double h = PG_R(offset.v, 0, r) * J[3 * cidx] + PG_R(offset.v, 1, r) * J[3 * cidx + 1] + PG_R(offset.v, 2, r) * J[3 * cidx + 2];
-      if (cidx < 6) a[r + 3 * cidx] = h;
-      else b[r + 3 * (cidx - 6)] = h;
-    }
-  pg_store<STAGED, 18>(lds, a, J0, k, n);
-  pg_store<STAGED, 9>(lds, b, J1, k, n);
-}
-
 struct PgKcam {
   double fx, fy, cx, cy;
 };
 
-// The two projective pose -> point edges over ParameterCamera / CacheCamera (one sensor offset + Kcam = (fx, fy, cx, cy)):
-//   EdgeSE3PointXYZDepth::computeError / linearizeOplus       g2o/types/slam3d/edge_se3_pointxyz_depth.cpp:91-138
-//   EdgeSE3PointXYZDisparity::computeError / linearizeOplus   g2o/types/slam3d/edge_se3_pointxyz_disparity.cpp:96-168
-//   ParameterCamera::setKcam / setOffset, CacheCamera::updateImpl   g2o/types/slam3d/parameter_camera.cpp:45-59, 93-96
-// p = K (w2n l) with K = [fx 0 cx; 0 fy cy; 0 0 1], so p2 is the depth in the sensor frame; e = (p0 / p2, p1 / p2, p2) - z
-// (depth) or (p0 / p2, p1 / p2, 1 / p2) - z (disparity).  J is the 3 x 9 matrix of the kernel above, J' = K Roff' J, rows 0-1 of
-// the result (J'[0:2] p2 - p[0:2] J'[2]) / p2^2, row 2 J'[2] (depth) or -J'[2] / p2^2 (disparity), split 6 | 3.
+// The three SE3 pose -> point edges, OBS = the edge type of the C ABI:
+//   4  EdgeSE3PointXYZ over ParameterSE3Offset            g2o/types/slam3d/edge_se3_pointxyz.cpp:95-131
+//   5  EdgeSE3PointXYZDepth, 6 EdgeSE3PointXYZDisparity over ParameterCamera / CacheCamera (one sensor offset + Kcam = (fx, fy,
+//      cx, cy))   g2o/types/slam3d/edge_se3_pointxyz_depth.cpp:91-138, edge_se3_pointxyz_disparity.cpp:96-168,
+//      parameter_camera.cpp:45-59, 93-96 (setKcam / setOffset, CacheCamera::updateImpl)
+// Shared: w2n = (X offset)^-1, w2l = X^-1, q = w2n l the point in the sensor frame, J = [-I | 2 [w2l l]x | R(w2l)] (3 x 9) and
+// the columns h of Roff' J.  What differs is the error taken from q and the output column made of h, split 6 | 3:
+//   4     e = q - z, the column is h itself (kc is not read);
+//   5, 6  p = K q with K = [fx 0 cx; 0 fy cy; 0 0 1], so p2 is the depth in the sensor frame; e = (p0 / p2, p1 / p2, p2) - z
+//         (depth) or (p0 / p2, p1 / p2, 1 / p2) - z (disparity); with J' = K h, rows 0-1 of the column are
+//         (J'[0:2] p2 - p[0:2] J'[2]) / p2^2, row 2 J'[2] (depth) or -J'[2] / p2^2 (disparity).
 // The reference has no guard for a point on or behind the image plane (p2 <= 0), and neither has this kernel: such an edge
 // gives the same infinities / NaNs here as there.
-template <bool DISPARITY, bool STAGED>
-__global__ void __launch_bounds__(kThreads) pg_se3_camera_linearize_kernel(int n, const double* __restrict__ poses,
-                                                                         const double* __restrict__ points, const int* __restrict__ vp,
-                                                                         const int* __restrict__ vl, const double* __restrict__ meas,
-                                                                         PgIso offset, PgKcam kc, double* __restrict__ J0,
-                                                                         double* __restrict__ J1, double* __restrict__ err, int jac) {
+template <int OBS, bool STAGED>
+__global__ void __launch_bounds__(kThreads) pg_se3_point_linearize_kernel(int n, const double* __restrict__ poses,
+                                                                        const double* __restrict__ points, const int* __restrict__ vp,
+                                                                        const int* __restrict__ vl, const double* __restrict__ meas,
+                                                                        PgIso offset, PgKcam kc, double* __restrict__ J0,
+                                                                        double* __restrict__ J1, double* __restrict__ err, int jac) {
+  static_assert(OBS == 4 || OBS == 5 || OBS == 6, "EdgeSE3PointXYZ, ...Depth, ...Disparity");
+  constexpr bool DISPARITY = OBS == 6;
   __shared__ double lds[STAGED ? kThreads * 19 : 1];
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   const int kk = min(k, n - 1);   // (lanes past the end evaluate the last edge and store nothing)
@@ -158,31 +118,50 @@ __global__ void __launch_bounds__(kThreads) pg_se3_camera_linearize_kernel(int n
   const double l[3] = {lp[0], lp[1], lp[2]};
   pg_iso_mul(X, offset.v, n2w);
   pg_iso_inv(n2w, w2n);
-  double q[3];
+  double e[3], p[3];   // (p: the camera edges only)
+  if constexpr (OBS == 4) {
 #pragma unroll
-  for (int r = 0; r < 3; ++r) q[r] = PG_R(w2n, r, 0) * l[0] + PG_R(w2n, r, 1) * l[1] + PG_R(w2n, r, 2) * l[2] + w2n[9 + r];
-  const double p[3] = {kc.fx * q[0] + kc.cx * q[2], kc.fy * q[1] + kc.cy * q[2], q[2]};
-  const double e[3] = {p[0] / p[2] - meas[3 * (size_t)kk], p[1] / p[2] - meas[3 * (size_t)kk + 1],
-                       (DISPARITY ? 1.0 / p[2] : p[2]) - meas[3 * (size_t)kk + 2]};
+    for (int r = 0; r < 3; ++r)
+      e[r] = PG_R(w2n, r, 0) * l[0] + PG_R(w2n, r, 1) * l[1] + PG_R(w2n, r, 2) * l[2] + w2n[9 + r] - meas[3 * (size_t)kk + r];
+  } else {
+    double q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = PG_R(w2n, r, 0) * l[0] + PG_R(w2n, r, 1) * l[1] + PG_R(w2n, r, 2) * l[2] + w2n[9 + r];
+    p[0] = kc.fx * q[0] + kc.cx * q[2];
+    p[1] = kc.fy * q[1] + kc.cy * q[2];
+    p[2] = q[2];
+    e[0] = p[0] / p[2] - meas[3 * (size_t)kk];
+    e[1] = p[1] / p[2] - meas[3 * (size_t)kk + 1];
+    e[2] = (DISPARITY ? 1.0 / p[2] : p[2]) - meas[3 * (size_t)kk + 2];
+  }
   pg_store<STAGED, 3>(lds, e, err, k, n);
   if (!jac) return;
   pg_iso_inv(X, w2l);
   double Z[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) Z[r] = PG_R(w2l, r, 0) * l[0] + PG_R(w2l, r, 1) * l[1] + PG_R(w2l, r, 2) * l[2] + w2l[9 + r];
+  // J (3 x 9, column-major) as EdgeSE3PointXYZ::linearizeOplus fills it
   const double J[27] = {-1, 0, 0, 0, -1, 0, 0, 0, -1,
                         0, 2 * Z[2], -2 * Z[1], -2 * Z[2], 0, 2 * Z[0], 2 * Z[1], -2 * Z[0], 0,
                         w2l[0], w2l[1], w2l[2], w2l[3], w2l[4], w2l[5], w2l[6], w2l[7], w2l[8]};
-  const double iz2 = 1.0 / (p[2] * p[2]);
+  double iz2 = 0.0;
+  if constexpr (OBS != 4) iz2 = 1.0 / (p[2] * p[2]);
   double a[18], b[9];
 #pragma unroll
   for (int cidx = 0; cidx < 9; ++cidx) {
-    double h[3];   // column cidx of Roff' J
+    double h[3], g[3];   // column cidx of Roff' J (row r of inverseOffset().rotation() = column r of R(offset)), ... of the output
 #pragma unroll
     for (int r = 0; r < 3; ++r)
       h[r] = PG_R(offset.v, 0, r) * J[3 * cidx] + PG_R(offset.v, 1, r) * J[3 * cidx + 1] + PG_R(offset.v, 2, r) * J[3 * cidx + 2];
-    const double jp[3] = {kc.fx * h[0] + kc.cx * h[2], kc.fy * h[1] + kc.cy * h[2], h[2]};   // ... of J' = K Roff' J
-    const double g[3] = {iz2 * (jp[0] * p[2] - p[0] * jp[2]), iz2 * (jp[1] * p[2] - p[1] * jp[2]), DISPARITY ? -iz2 * jp[2] : jp[2]};
+    if constexpr (OBS == 4) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) g[r] = h[r];
+    } else {
+      const double jp[3] = {kc.fx * h[0] + kc.cx * h[2], kc.fy * h[1] + kc.cy * h[2], h[2]};   // ... of J' = K Roff' J
+      g[0] = iz2 * (jp[0] * p[2] - p[0] * jp[2]);
+      g[1] = iz2 * (jp[1] * p[2] - p[1] * jp[2]);
+      g[2] = DISPARITY ? -iz2 * jp[2] : jp[2];
+    }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       if (cidx < 6) a[r + 3 * cidx] = g[r];

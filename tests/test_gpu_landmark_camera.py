@@ -281,7 +281,7 @@ def test_error_paths(obs):
     assert L.g2ohip_pg_set_landmark_estimates(s.h, g["L"], _dp(pts), _ip(_i32(hl))) == ARG   # ... now it is
     assert set_cam(s, k1, typ, offset=None) == 0                     # NULL offset: identity
     s.pgSetLandmarkEstimates(pts, hl)
-    assert set_cam(s, k1, typ, b=bad) == ARG                         # rolled back: the good binding stays
+    assert set_cam(s, k1, typ, b=bad) == ARG                         # rejected: the good binding stays
     s.pgLinearize(True)
     e_id = CH.landmark_edges(dict(g, offset=None), jac=False)
     assert relerr(s.edgeData(k1, g["M"], 3, 6, 3)[2], e_id) < TOL_J

@@ -301,6 +301,25 @@ def test_error_paths():
     assert L.g2ohip_pg_linearize(s.h, 1) == STATE
     s.pgSetLandmarkEstimates(pts, hl)
     assert L.g2ohip_pg_linearize(s.h, 1) == 0
+    # a rejected call commits nothing: the previous table / binding stands
+    s.buildSystem()
+    chi0, est0 = s.chi2(), s.pgGetEstimates()
+    wrong = _i32(h).copy()
+    wrong[3], wrong[4] = wrong[4], wrong[3]
+    assert wrong[3] != wrong[4]
+    assert L.g2ohip_pg_set_estimates(s.h, len(wrong), _dp(_f64(g["poses"] + 0.25)), _ip(wrong)) == ARG
+    assert np.array_equal(s.pgGetEstimates(), est0)
+    assert L.g2ohip_pg_linearize(s.h, 1) == 0
+    s.buildSystem()
+    assert s.chi2() == chi0
+    bad = vi.copy()                                                  # one vi whose hessian index disagrees with the edge set
+    bad[7] = (bad[7] + 1) % len(h)
+    assert h[bad[7]] != h[vi[7]]
+    assert L.g2ohip_pg_set_edges(s.h, k0, 1, _ip(bad), _ip(vj), _dp(_f64(Z + 0.25)), _dp(om)) == ARG
+    assert L.g2ohip_pg_linearize(s.h, 1) == 0
+    s.buildSystem()
+    assert s.chi2() == chi0
+    assert np.array_equal(s.pgGetEstimates(), est0)
     # type 3 beside an SE3 pose set
     g3 = _graph("se3")
     h3, hl3 = g3["hidx"], g3["pt_hidx"]

@@ -353,10 +353,15 @@ def test_batch_statistics_line_is_g2o_stats_compatible():
 def test_front_end_rejects_inconsistent_indices():
     """g2ohip_ba_set_edges / g2ohip_ba_set_estimates validate the edge -> estimate indices and their hessian indices
     against the edge set (an out-of-range index would be an out-of-bounds device read, a mismatch a silently inconsistent
-    system); the wrappers check array lengths."""
+    system); the wrappers check array lengths.  A rejected g2ohip_ba_set_estimates commits nothing: after a rejected
+    first call there is no table (G2OHIP_ERR_STATE from everything that needs one), after a rejected later call the
+    previous table stands, values and chi2 bit for bit."""
     from openslam_g2o_amd import capi
+    from openslam_g2o_amd.capi import _dp, _f64, _i32, _ip
+    ARG, STATE = -1, -3      # G2OHIP_ERR_ARG, G2OHIP_ERR_STATE
     pr = ba_case(20, 120)
     s = capi.HipBlockSolver(6, 3, 0)
+    L = s.L
     k = s.addEdgeSet(2, pr["v0"], pr["v1"])
     s.buildStructure(pr["nP"], pr["nL"], True)
     with pytest.raises(ValueError):
@@ -366,10 +371,28 @@ def test_front_end_rejects_inconsistent_indices():
     bad[5], bad[6] = bad[6], bad[5]                      # two cameras swap their hessian indices
     with pytest.raises(capi.G2oHipError):
         s.baSetEstimates(pr["cams"], bad, pr["pts"], np.arange(pr["L"], dtype=np.int32))
+    assert L.g2ohip_ba_linearize(s.h, 1) == STATE        # (no table: nothing launches on a null one)
+    assert L.g2ohip_ba_update(s.h) == STATE
+    assert L.g2ohip_ba_push(s.h) == STATE
     with pytest.raises(capi.G2oHipError):                # a point table that is too short
         s.baSetEstimates(pr["cams"], pr["cam_hidx"], pr["pts"][:-3], np.arange(pr["L"] - 3, dtype=np.int32))
+    assert L.g2ohip_ba_linearize(s.h, 1) == STATE
     s.baSetEstimates(pr["cams"], pr["cam_hidx"], pr["pts"], np.arange(pr["L"], dtype=np.int32))
     s.baLinearize(True)
+    chi0 = s.chi2()
+    cams0, pts0 = s.baGetEstimates()
+    # rejected later calls (through the C entry: the wrapper remembers the sizes it was handed): the swapped hessian indices,
+    # and a table of 3 more points (three fixed ones in front, so every edge's point has moved)
+    cams_b, pts_b = _f64(pr["cams"] + 0.25), _f64(np.concatenate([np.zeros((3, 3)), pr["pts"] + 0.25]))
+    hc, hp = _i32(pr["cam_hidx"]), _i32(np.arange(pr["L"]))
+    hp_b = _i32(np.concatenate([[-1, -1, -1], np.arange(pr["L"])]))
+    for args in ((pr["nP"], _dp(cams_b), _ip(_i32(bad)), pr["L"], _dp(pts_b[3:].copy()), _ip(hp)),
+                 (pr["nP"], _dp(cams_b), _ip(hc), pr["L"] + 3, _dp(pts_b), _ip(hp_b))):
+        assert L.g2ohip_ba_set_estimates(s.h, *args) == ARG
+        cams1, pts1 = s.baGetEstimates()
+        assert np.array_equal(cams1, cams0) and np.array_equal(pts1, pts0)
+        s.baLinearize(True)
+        assert s.chi2() == chi0
     s.buildSystem()
     s.setLambda(1.0, True)
     assert s.solve()
