@@ -505,6 +505,35 @@ int g2ohip_pg_set_landmark_edges(g2ohip_solver* s, int set, int type, const int3
  * push / pop / discard_top, robust kernels, g2ohip_clear_edge_sets -- acts on it unchanged. */
 int g2ohip_pg_set_landmark_camera_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
                                         const double* meas, const double* info, const double* offset, const double* kcam);
+/* ---- ... its unary pose priors: GPS fixes, an anchor on the first pose, surveyed checkpoints ------------------------
+ * One UNARY edge set of the same handle beside the pose-pose set of g2ohip_pg_set_edges, in a slot of its own (independent of
+ * the landmark slot: with or without a landmark set, do_schur 0 or 1; a later call replaces the binding):
+ *   type 7 = EdgeSE2Prior over VertexSE2 (g2o/types/slam2d/edge_se2_prior.h:45-50 computeError): e = (Z^-1 X).toVector() =
+ *            (Rz' (t - tz), normalize(theta - theta_z)), measurements [n][3] = (x, y, theta), information [n][3x3].  The
+ *            reference compiles its analytic linearizeOplus out (edge_se2_prior.h:52-58) and differentiates numerically; the
+ *            device writes the exact derivative with respect to VertexSE2::oplusImpl (vertex_se2.h:51-58), J = [Rz' 0; 0 1],
+ *            which is what the disabled reference code states;
+ *   type 8 = EdgeSE2XYPrior over VertexSE2 (edge_se2_xyprior.h:66-70 computeError, edge_se2_xyprior.cpp:60-63
+ *            linearizeOplus): e = t - z, J = [1 0 0; 0 1 0], measurements [n][2], information [n][2x2];
+ *            types 7 and 8 beside a type-1 pose set only;
+ *   type 9 = EdgeSE3Prior over VertexSE3 (g2o/types/slam3d/edge_se3_prior.cpp:94-107 computeError / linearizeOplus,
+ *            isometry3d_gradients.h:269-330 computeEdgeSE3PriorGradient, parameter_se3_offset.cpp:44-50) with ONE
+ *            ParameterSE3Offset P for the whole set: E = Z^-1 X P, e = toVectorMQT(E) in the convention of type 2,
+ *            measurements isometries [n][12] = R (column-major) | t, information [n][6x6], offset an isometry [12] or NULL
+ *            for the identity (type 9 only, finite); beside a type-2 pose set only.
+ * Edge set `set` was added as a unary set (v1 == NULL) with error_dim 3 / 2 / 6 over the poses' hessian indices (-1: a prior
+ * on a fixed pose, legal as in g2o: it contributes to chi2 and nothing else); pose_vertex[k] indexes the pose table of
+ * g2ohip_pg_set_estimates.  Call after g2ohip_build_structure and after g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).
+ * G2OHIP_ERR_ARG: a wrong pairing of types, a set that is not unary or has other dimensions, the set already bound as the
+ * pose-pose or landmark set, an offset with type 7 or 8, a non-finite offset, a null array, a pose_vertex out of range, a
+ * hessian index that differs from the set's vertex 0 -- validated before anything is committed, as for the entries above;
+ * g2ohip_pg_set_estimates with changed tables validates the prior set again.  g2ohip_pg_linearize then fills the set's
+ * Jacobians and errors after the other two; update / push / pop / discard_top are not concerned (priors own no vertices).
+ * Robust kernels of the set: g2ohip_set_robust_kernel(_per_edge) as for any set.  g2ohip_clear_edge_sets drops the binding;
+ * a prior set grown by g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.
+ * The kernel is timed under the "pg_landmark_linearize" slot. */
+int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const double* meas, const double* info,
+                              const double* offset);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -60,7 +60,7 @@ EXPORTS = [
     "g2ohip_pg_set_edges", "g2ohip_pg_set_estimates", "g2ohip_pg_get_estimates", "g2ohip_pg_linearize", "g2ohip_pg_update",
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
-    "g2ohip_pg_set_landmark_camera_edges",
+    "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -163,6 +163,7 @@ def load():
     L.g2ohip_pg_linearize.argtypes = [vp, C.c_int]
     L.g2ohip_pg_set_landmark_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_camera_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_copy_edge_data.argtypes = [vp, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -748,6 +749,24 @@ class HipBlockSolver:
             raise ValueError("pgSetLandmarkCameraEdges: kcam is (fx, fy, cx, cy)")
         _check(self.L.g2ohip_pg_set_landmark_camera_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
                                                           None if off is None else _dp(off), _dp(kc)), "pgSetLandmarkCameraEdges")
+
+    def pgSetPriorEdges(self, set_id, edge_type, pose_vertex, meas, info, offset=None):
+        """Unary priors on poses: edge_type 7 = EdgeSE2Prior (meas [n][3]), 8 = EdgeSE2XYPrior ([n][2]) beside EdgeSE2,
+        9 = EdgeSE3Prior (isometries [n][12]) beside EdgeSE3; pose_vertex indexes the table of pgSetEstimates, info
+        [n][3x3 | 2x2 | 6x6], offset: isometry [12] of the set's ParameterSE3Offset (type 9 only, None = identity).  The set
+        is a unary one (addEdgeSet(d, v0, None)).  After pgSetEdges."""
+        pv, meas, info = _i32(pose_vertex), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        d, ms = {7: (3, 3), 8: (2, 2)}.get(edge_type, (6, 12))
+        if len(pv) != n or meas.size != n * ms or info.size != n * d * d:
+            raise ValueError("pgSetPriorEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        off = None
+        if offset is not None:
+            off = _f64(offset).reshape(-1)
+            if off.size != 12:
+                raise ValueError("pgSetPriorEdges: offset is an isometry [12] (R column-major | t)")
+        _check(self.L.g2ohip_pg_set_prior_edges(self.h, set_id, edge_type, _ip(pv), _dp(meas), _dp(info),
+                                                None if off is None else _dp(off)), "pgSetPriorEdges")
 
     def pgSetLandmarkEstimates(self, points, hidx):
         """points [n][landmark_dim]; hidx[v] = the landmark's hessian index in the whole system (>= num_poses) or -1."""

@@ -91,6 +91,11 @@ class HipBlockSolver {
                                 const double* info, const double* offset, const double* kcam) {
     return ok(g2ohip_pg_set_landmark_camera_edges(h_, set, type, poseVertex, pointVertex, meas, info, offset, kcam), "pgSetLandmarkCameraEdges");
   }
+  // unary pose priors (g2ohip_pg_set_prior_edges): type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior beside an EdgeSE2 pose set, 9 =
+  // EdgeSE3Prior beside an EdgeSE3 one; `set` is a unary set (addEdgeSet with v1 == nullptr), offset isometry [12] or nullptr (type 9)
+  bool pgSetPriorEdges(int set, int type, const int32_t* poseVertex, const double* meas, const double* info, const double* offset) {
+    return ok(g2ohip_pg_set_prior_edges(h_, set, type, poseVertex, meas, info, offset), "pgSetPriorEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -96,6 +96,7 @@ class BlockSolver {
                              const double* offset);
   void pg_set_landmark_camera_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                     const double* info, const double* offset, const double* kcam);
+  void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
   void pg_linearize(bool jacobians);
@@ -345,6 +346,7 @@ class BlockSolver {
   void pg_validate(const EdgeSet& es, const int* vi, const int* vj, size_t n, const int* hidx, int nv) const;
   void pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv, const int* pt_hidx,
                              int np) const;
+  void pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const;
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                               const double* info, const double* offset, const double* kcam);
   // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
@@ -442,6 +444,14 @@ class BlockSolver {
     EstimateTable points;          // (x, y) or (x, y, z) per landmark
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
     double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
+    // ONE unary set of pose priors `pr_set`, independent of the landmark slot: pr_type 7 = EdgeSE2Prior (measurement (x, y, theta)),
+    // 8 = EdgeSE2XYPrior ((x, y)) beside type 1, 9 = EdgeSE3Prior (isometry [12], one ParameterSE3Offset pr_offset) beside type 2.
+    // vq indexes `poses`.  Priors own no vertices: pg_linearize fills the set's own_J0 / own_err, nothing else knows of them.
+    int pr_set = -1, pr_type = 0;
+    DevBuf<int> vq;
+    std::vector<int> h_vq;         // host copy: index validation (pg_validate_priors)
+    DevBuf<double> pr_meas;
+    double pr_offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

@@ -2081,6 +2081,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
   for (int i = 0; i < 12; ++i) T[i] = out[i];
 }
 #include "pg_landmark.inc"
+#include "pg_prior.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -2334,7 +2335,8 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     es.J0 = es.J1 = es.omega = es.err = nullptr;
     es.external = false;
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
-    // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then
+    // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
+    // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again)
     if (set == pg_.set || set == pg_.lm_set) pg_ = PgFrontEnd();
     if (set == ba_.set) ba_.set = -1;
     // per-edge robust kernels cover the old edge count: the new edges get "none" (kind 0) until set_robust_kernel_per_edge is
@@ -3030,7 +3032,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set;
+  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5086,6 +5088,21 @@ void BlockSolver::pg_validate(const EdgeSet& es, const int* vi, const int* vj, s
   }
 }
 
+// the prior set: hidx[vq[k]] == v0[k] of the unary set (nv == 0: no pose table yet)
+void BlockSolver::pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const {
+  for (size_t k = 0; k < n; ++k) {
+    const int a = vq[k];
+    if (a < 0) throw ArgFailure("pg: negative vertex index in prior edge " + std::to_string(k));
+    if (nv > 0) {
+      if (a >= nv) throw ArgFailure("pg: pose index of prior edge " + std::to_string(k) + " outside the estimate table");
+      const int ha = hidx[a];
+      if (ha >= nP_) throw ArgFailure("pg: hessian index of an estimate outside the structure");
+      if (es.v0[k] != (ha < 0 ? -1 : ha))
+        throw ArgFailure("pg: prior edge " + std::to_string(k) + ": the pose's hessian index differs from the edge set's");
+    }
+  }
+}
+
 // the landmark half: hidx[vp[k]] == v0[k] and pt_hidx[vl[k]] == v1[k] of the observation set (whatever of the tables has been
 // handed over so far: nv == 0 / np == 0 = not yet)
 void BlockSolver::pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv,
@@ -5351,6 +5368,7 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
     if (pg_.lm_set >= 0)
       pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
                             pg_.points.n);
+    if (pg_.pr_set >= 0) pg_validate_priors(*sets_[pg_.pr_set], pg_.h_vq.data(), pg_.h_vq.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -5400,6 +5418,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
                                          const double* meas, const double* info, const double* offset, const double* kcam) {
   const std::string w(who);
   if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
+  if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
   EdgeSet& es = *sets_[set];
   const int d = type == 3 ? 2 : 3, dp = type == 3 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != d || p_ != dp || l_ != d)
@@ -5424,6 +5443,48 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   es.own_J1.alloc(n * d * d);
   es.own_err.alloc(n * d);
   es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ---- ... its unary pose priors (EdgeSE2Prior / EdgeSE2XYPrior / EdgeSE3Prior) -----------------------------------------------
+void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info,
+                                     const double* offset) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_prior_edges: call pg_set_edges first (the pose-pose set the prior set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 7 && type != 8 && type != 9) throw ArgFailure("pg_set_prior_edges: type must be 7 (EdgeSE2Prior), 8 (EdgeSE2XYPrior) or 9 (EdgeSE3Prior)");
+  if ((type == 9) != (pg_.type == 2)) throw ArgFailure("pg_set_prior_edges: EdgeSE2Prior (7) and EdgeSE2XYPrior (8) go with an EdgeSE2 pose set (1), EdgeSE3Prior (9) with EdgeSE3 (2)");
+  if (offset && type != 9) throw ArgFailure("pg_set_prior_edges: an offset belongs to EdgeSE3Prior (type 9) only");
+  if (offset)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(offset[i])) throw ArgFailure("pg_set_prior_edges: non-finite offset");
+  if (set == pg_.set) throw ArgFailure("pg_set_prior_edges: the set is bound as the pose-pose set");
+  if (set == pg_.lm_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the landmark set");
+  EdgeSet& es = *sets_[set];
+  const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
+  const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
+  if (!es.unary || es.d != d || es.dim0 != dp || p_ != dp)
+    throw ArgFailure("pg_set_prior_edges: the set must be a unary set on poses with (error, pose) dimensions (3, 3), (2, 3) or (6, 6)");
+  if (!pose_vertex || !meas || !info) throw ArgFailure("pg_set_prior_edges: null array");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const size_t n = (size_t)es.n;
+  pg_validate_priors(es, pose_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_.pr_set = set;
+  pg_.pr_type = type;
+  pg_.h_vq.assign(pose_vertex, pose_vertex + n);
+  for (int i = 0; i < 12; ++i) pg_.pr_offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.vq.upload(pose_vertex, n, st_);
+  pg_.pr_meas.upload(meas, n * ms, st_);
+  es.own_omega.upload(info, n * d * d, st_);
+  es.own_J0.alloc(n * d * dp);
+  es.own_err.alloc(n * d);
+  es.J0 = es.own_J0.p; es.J1 = nullptr; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
   es.has_data = false;
   es.has_err = false;
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
@@ -5466,9 +5527,13 @@ void BlockSolver::pg_linearize(bool jacobians) {
     if (pg_.points.n <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
     if ((int)pg_.h_vp.size() != el->n) throw StateFailure("pg_linearize: the landmark edge set has changed since pg_set_landmark_edges: call it again");
   }
+  EdgeSet* ep = pg_.pr_set >= 0 ? sets_[pg_.pr_set].get() : nullptr;
+  if (ep && (int)pg_.h_vq.size() != ep->n)
+    throw StateFailure("pg_linearize: the prior edge set has grown since pg_set_prior_edges (g2ohip_update_structure): call pg_set_prior_edges again");
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     if (jacobians) es.has_data = true;
     if (jacobians && el) el->has_data = true;
+    if (jacobians && ep) ep->has_data = true;
     return;
   }
   pg_.err_valid = true;
@@ -5480,10 +5545,11 @@ void BlockSolver::pg_linearize(bool jacobians) {
   else
     hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  if (el && el->n > 0) {
-    prof.begin(KernelProf::kPgLandmark, st_);
+  const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0;
+  const int jac = jacobians ? 1 : 0;
+  if (lm_launch || pr_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch) {
     const dim3 grid(grid_for(el->n)), block(kThreads);
-    const int jac = jacobians ? 1 : 0;
     PgIso off;
     for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
     const PgKcam kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3]};
@@ -5499,14 +5565,35 @@ void BlockSolver::pg_linearize(bool jacobians) {
                              pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, off, kc, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
         });
     });
-    prof.end(KernelProf::kPgLandmark, st_);
   }
+  if (pr_launch) {
+    const dim3 grid(grid_for(ep->n)), block(kThreads);
+    PgIso off;
+    for (int i = 0; i < 12; ++i) off.v[i] = pg_.pr_offset[i];
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      if (pg_.pr_type == 9)
+        hipLaunchKernelGGL(pg_se3_prior_linearize_kernel<STAGED>, grid, block, 0, st_, ep->n, pg_.poses.val.p, pg_.vq.p, pg_.pr_meas.p, off,
+                           ep->own_J0.p, ep->own_err.p, jac);
+      else
+        dispatch_value<7, 8>(pg_.pr_type, [&](auto type) {
+          constexpr int TYPE = type;
+          hipLaunchKernelGGL((pg_se2_prior_linearize_kernel<TYPE, STAGED>), grid, block, 0, st_, ep->n, pg_.poses.val.p, pg_.vq.p,
+                             pg_.pr_meas.p, ep->own_J0.p, ep->own_err.p, jac);
+        });
+    });
+  }
+  if (lm_launch || pr_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
   if (el) {
     el->has_err = true;
     if (jacobians) el->has_data = true;
+  }
+  if (ep) {
+    ep->has_err = true;
+    if (jacobians) ep->has_data = true;
   }
 }
 

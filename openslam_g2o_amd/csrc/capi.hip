@@ -673,6 +673,10 @@ int g2ohip_pg_set_landmark_camera_edges(g2ohip_solver* s, int set, int type, con
                                         const double* meas, const double* info, const double* offset, const double* kcam) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_landmark_camera_edges(set, type, pose_vertex, point_vertex, meas, info, offset, kcam); });
 }
+int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const double* meas, const double* info,
+                              const double* offset) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_prior_edges(set, type, pose_vertex, meas, info, offset); });
+}
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_landmark_estimates(n_points, points, hidx); });
 }

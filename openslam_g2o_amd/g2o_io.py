@@ -7,7 +7,9 @@ the information matrix is given as its upper triangle, row-major (edge_se2.cpp:4
 Landmark SLAM files add `VERTEX_XY` / `EDGE_SE2_XY` (g2o/types/slam2d/{vertex_point_xy,edge_se2_pointxy}.cpp read()) and
 `VERTEX_TRACKXYZ` / `EDGE_SE3_TRACKXYZ` / `PARAMS_SE3OFFSET` (g2o/types/slam3d/{vertex_pointxyz,edge_se3_pointxyz,
 parameter_se3_offset}.cpp read()); RGB-D / stereo files `EDGE_PROJECT_DEPTH` / `EDGE_PROJECT_DISPARITY` / `PARAMS_CAMERACALIB`
-(g2o/types/slam3d/{edge_se3_pointxyz_depth,edge_se3_pointxyz_disparity,parameter_camera}.cpp read()).
+(g2o/types/slam3d/{edge_se3_pointxyz_depth,edge_se3_pointxyz_disparity,parameter_camera}.cpp read()); unary pose priors
+`EDGE_PRIOR_SE2` / `EDGE_PRIOR_SE2_XY` (g2o/types/slam2d/{edge_se2_prior,edge_se2_xyprior}.cpp read()) and `EDGE_SE3_PRIOR`
+(g2o/types/slam3d/edge_se3_prior.cpp read(): vertex, PARAMS_SE3OFFSET id, measurement, upper triangle).
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -31,10 +33,15 @@ def read_g2o(path):
     offsets {id: (x y z qx qy qz qw), quaternion normalised as ParameterSE3Offset::read does}, fixed_points.
     A file with EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY (pose point paramId u v d + upper triangle) or PARAMS_CAMERACALIB
     (id x y z qx qy qz qw fx fy cx cy) also gives lm_kind (per observation: "xyz" | "depth" | "disparity") and cameras
-    {id: (x y z qx qy qz qw fx fy cx cy)}; files without these tags return exactly the keys above."""
+    {id: (x y z qx qy qz qw fx fy cx cy)}; files without these tags return exactly the keys above.
+    A file with EDGE_PRIOR_SE2 (v x y th + 6), EDGE_PRIOR_SE2_XY (v x y + 3) or EDGE_SE3_PRIOR (v paramId x y z qx qy qz qw + 21)
+    lines also gives pr_v (pose-table index of every prior), pr_kind (per prior: "se2" | "xy" | "se3"), pr_meas and pr_info
+    (lists: the kinds differ in size), pr_param (PARAMS_SE3OFFSET id, -1 for the 2-D kinds) and `offsets`; a file without
+    them gives none of these keys."""
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
+    qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
     kind = None
     with open(path) as f:
         for line in f:
@@ -85,6 +92,19 @@ def read_g2o(path):
                 lmeas.append([float(x) for x in t[4:7]])
                 linfo.append(_upper_to_full([float(x) for x in t[7:13]], 3))
                 lkind.append("depth" if tag == "EDGE_PROJECT_DEPTH" else "disparity")
+            elif tag in ("EDGE_PRIOR_SE2", "EDGE_PRIOR_SE2_XY"):
+                m = 3 if tag == "EDGE_PRIOR_SE2" else 2
+                qv.append(int(t[1]))
+                qkind.append("se2" if m == 3 else "xy")
+                qmeas.append(np.asarray([float(x) for x in t[2:2 + m]]))
+                qinfo.append(_upper_to_full([float(x) for x in t[2 + m:2 + m + m * (m + 1) // 2]], m))
+                qparam.append(-1)
+            elif tag == "EDGE_SE3_PRIOR":
+                qv.append(int(t[1]))
+                qkind.append("se3")
+                qparam.append(int(t[2]))
+                qmeas.append(np.asarray([float(x) for x in t[3:10]]))
+                qinfo.append(_upper_to_full([float(x) for x in t[10:31]], 6))
             elif tag == "PARAMS_CAMERACALIB":
                 o = np.asarray([float(x) for x in t[2:13]])
                 o[3:7] /= np.linalg.norm(o[3:7])
@@ -115,6 +135,9 @@ def read_g2o(path):
                    lm_param=np.asarray(lparam, np.int32), offsets=offsets, fixed_points=[plut[f] for f in fixed if f in plut])
         if cameras or any(k != "xyz" for k in lkind):
             out.update(lm_kind=lkind, cameras=cameras)
+    if qv:
+        out.update(pr_v=np.asarray([lut[a] for a in qv], np.int32), pr_kind=qkind, pr_meas=qmeas, pr_info=qinfo,
+                   pr_param=np.asarray(qparam, np.int32), offsets=offsets)
     return out
 
 
@@ -150,13 +173,16 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
     lm.setup_device_landmark_slam takes).  fixed_*: indices into the pose / point tables (default: the file's FIX lines; a file
     without any gets pose 0 fixed as the gauge).  All 3-D observations must name the same PARAMS_SE3OFFSET.  A file of
     EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY observations gives observation = "depth" | "disparity", kcam = (fx, fy, cx, cy)
-    and the offset of its PARAMS_CAMERACALIB; observations of different kinds or naming several camera parameters are refused."""
+    and the offset of its PARAMS_CAMERACALIB; observations of different kinds or naming several camera parameters are refused.
+    Pose priors (EDGE_PRIOR_SE2 / EDGE_PRIOR_SE2_XY / EDGE_SE3_PRIOR) become prior = "pose" | "xy", vq, zq, omega_q and -- 3-D --
+    prior_offset; priors of different kinds or naming several PARAMS_SE3OFFSET are refused.  A file with priors and no FIX
+    line keeps every pose free: the priors hold the gauge."""
     if "points" not in rd:
         raise ValueError("the file has no point landmarks")
     se2 = rd["kind"] == "se2"
     fp = list(rd["fixed"]) if fixed_poses is None else list(fixed_poses)
     fl = list(rd["fixed_points"]) if fixed_points is None else list(fixed_points)
-    if fixed_poses is None and not fp:
+    if fixed_poses is None and not fp and "pr_v" not in rd:
         fp = [0]
     n, L = len(rd["estimates"]), len(rd["points"])
     hidx, pt_hidx, nP, nL = landmark_hessian_index(n, L, fp, fl)
@@ -189,6 +215,30 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
             if ids:
                 offset = _iso_from_qt(rd["offsets"][ids.pop()])[0]
     E, M = len(rd["vi"]), len(rd["lm_vp"])
+    if "pr_v" in rd:
+        kinds = set(rd["pr_kind"])
+        if len(kinds) > 1:
+            raise ValueError("priors of different kinds (%s) are not one set" % ", ".join(sorted(kinds)))
+        pk = kinds.pop()
+        if (pk == "se3") == se2:
+            raise ValueError("%s priors do not belong to a %s graph" % (pk, rd["kind"]))
+        Q = len(rd["pr_v"])
+        zq = np.asarray(rd["pr_meas"], np.float64).reshape(Q, -1)
+        dq = {"se2": 3, "xy": 2, "se3": 6}[pk]
+        camera.update(prior="xy" if pk == "xy" else "pose", vq=rd["pr_v"],
+                      omega_q=np.asarray(rd["pr_info"]).transpose(0, 2, 1).reshape(Q, dq * dq).copy())
+        if pk == "se3":
+            ids = set(int(v) for v in rd["pr_param"])
+            if len(ids) > 1:
+                raise ValueError("priors with different PARAMS_SE3OFFSET are not one set")
+            po = rd["offsets"].get(ids.pop())
+            if po is None:
+                raise ValueError("the priors name a PARAMS_SE3OFFSET the file does not define")
+            qt = zq.copy()
+            qt[:, 3:] /= np.linalg.norm(qt[:, 3:], axis=1)[:, None]
+            zq = _iso_from_qt(qt)
+            camera.update(prior_offset=_iso_from_qt(po)[0])
+        camera.update(zq=zq)
     return dict(camera, kind=rd["kind"], n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=rd["vi"], vj=rd["vj"], Z=Z,
                 omega=np.asarray(rd["info"]).transpose(0, 2, 1).reshape(E, dp * dp).copy(), vp=rd["lm_vp"], vl=rd["lm_vl"],
                 zl=rd["lm_meas"], omega_l=np.asarray(rd["lm_info"]).transpose(0, 2, 1).reshape(M, dl * dl).copy(), offset=offset,
@@ -198,7 +248,8 @@ def landmark_problem(rd, fixed_poses=None, fixed_points=None):
 def write_g2o_landmarks(path, prob):
     """make_landmark_slam-style problem -> `.g2o` text with the reference's tags (poses get the ids 0..n-1, landmarks
     n..n+L-1, the sensor offset parameter id 0); fixed vertices (hessian index -1) go into a FIX line.  A problem with
-    observation = "depth" | "disparity" writes PARAMS_CAMERACALIB and EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY."""
+    observation = "depth" | "disparity" writes PARAMS_CAMERACALIB and EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY.  A problem with
+    `prior` writes EDGE_PRIOR_SE2 / EDGE_PRIOR_SE2_XY / EDGE_SE3_PRIOR (the latter's PARAMS_SE3OFFSET gets the id 1)."""
     se2 = prob["kind"] == "se2"
     obs = prob.get("observation", "xyz")
     obs_tag = {"xyz": "EDGE_SE3_TRACKXYZ", "depth": "EDGE_PROJECT_DEPTH", "disparity": "EDGE_PROJECT_DISPARITY"}[obs]
@@ -222,6 +273,10 @@ def write_g2o_landmarks(path, prob):
                 f.write("PARAMS_SE3OFFSET 0 %s\n" % fmt(qt(off)[0]))
             else:
                 f.write("PARAMS_CAMERACALIB 0 %s %s\n" % (fmt(qt(off)[0]), fmt(prob["kcam"])))
+            if prob.get("prior") is not None:
+                po = prob.get("prior_offset")
+                po = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]) if po is None else po
+                f.write("PARAMS_SE3OFFSET 1 %s\n" % fmt(qt(po)[0]))
             for i, v in enumerate(qt(prob["poses"])):
                 f.write("VERTEX_SE3:QUAT %d %s\n" % (i, fmt(v)))
             for j, pt in enumerate(prob["points"]):
@@ -237,6 +292,12 @@ def write_g2o_landmarks(path, prob):
         for e in range(len(prob["vp"])):
             f.write("%s %d %d %s%s %s\n" % ("EDGE_SE2_XY" if se2 else obs_tag, prob["vp"][e], n + prob["vl"][e],
                                             "" if se2 else "0 ", fmt(prob["zl"][e]), upper(np.asarray(prob["omega_l"][e]), dl)))
+        if prob.get("prior") is not None:
+            xy = prob["prior"] == "xy"
+            tag, dq = ("EDGE_PRIOR_SE2_XY", 2) if xy else ("EDGE_PRIOR_SE2", 3) if se2 else ("EDGE_SE3_PRIOR", 6)
+            zq = prob["zq"] if se2 else qt(prob["zq"])
+            for e in range(len(prob["vq"])):
+                f.write("%s %d %s%s %s\n" % (tag, prob["vq"][e], "" if se2 else "1 ", fmt(zq[e]), upper(np.asarray(prob["omega_q"][e]), dq)))
 
 
 # ---- bundle-adjustment tags --------------------------------------------------------------

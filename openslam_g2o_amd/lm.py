@@ -335,20 +335,31 @@ class DevicePoseGraph:
         self.s.pgDiscardTop()
 
 
-def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0):
+PRIOR_ERROR_DIM = {7: 3, 8: 2, 9: 6}   # EdgeSE2Prior, EdgeSE2XYPrior, EdgeSE3Prior (g2ohip_pg_set_prior_edges)
+
+
+def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0, priors=None):
     """HipBlockSolver for a pose graph with estimates, errors and Jacobians on the device.
     edge_type 1: EdgeSE2 (estimates / measurements (x, y, theta), information [n][9]);
     edge_type 2: EdgeSE3 (isometries [12] = R column-major | t, information [n][36]).
-    hidx[v] = hessian index of vertex v or -1 (fixed); BlockSolver_3_2 / BlockSolver_6_3 semantics, no Schur."""
+    hidx[v] = hessian index of vertex v or -1 (fixed); BlockSolver_3_2 / BlockSolver_6_3 semantics, no Schur.
+    priors: (type, vq, zq, omega_q, offset) -- unary priors on the poses vq, type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior
+    (edge_type 1), 9 = EdgeSE3Prior with its ParameterSE3Offset or None (edge_type 2); solver.prior_set = their set id."""
     import numpy as np
     from . import capi
     d = 3 if edge_type == 1 else 6
     s = capi.HipBlockSolver(d, landmark_dim or (2 if edge_type == 1 else 3), device)
     hidx = np.asarray(hidx, np.int32)
     k = s.addEdgeSet(d, hidx[np.asarray(vi)], hidx[np.asarray(vj)])
+    if priors is not None:
+        ptype, vq, zq, omega_q, offset = priors
+        kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[np.asarray(vq)], None)
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
     s.pgSetEstimates(estimates, hidx)
+    if priors is not None:
+        s.pgSetPriorEdges(kq, ptype, vq, zq, omega_q, offset)
+        s.prior_set = kq
     return s, DevicePoseGraph(s)
 
 
@@ -358,7 +369,9 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     carries observation = "depth" | "disparity" and kcam -- EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity), pose and
     landmark estimates, errors and Jacobians on the device; BlockSolver_3_2 / BlockSolver_6_3 semantics, landmarks
     marginalised (schur=True).  huber_delta > 0: Huber kernel on the observation set.  Returns (solver, DevicePoseGraph);
-    solver.landmark_sets = (odometry set id, observation set id)."""
+    solver.landmark_sets = (odometry set id, observation set id).  A prob that carries `prior` ("pose" | "xy", with vq, zq,
+    omega_q and -- 3-D -- prior_offset) also gets its unary prior set bound (EdgeSE2Prior / EdgeSE2XYPrior / EdgeSE3Prior):
+    solver.prior_set = its set id."""
     import numpy as np
     from . import capi
     se2 = prob["kind"] == "se2"
@@ -372,6 +385,10 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
     k0 = s.addEdgeSet(p, hidx[prob["vi"]], hidx[prob["vj"]])
     k1 = s.addEdgeSet(l, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    prior = prob.get("prior")
+    if prior is not None:
+        ptype = 9 if not se2 else (8 if prior == "xy" else 7)
+        kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[prob["vq"]], None)
     s.buildStructure(prob["nP"], prob["nL"], schur)
     s.pgSetEdges(k0, 1 if se2 else 2, prob["vi"], prob["vj"], prob["Z"], prob["omega"])
     s.pgSetEstimates(prob["poses"], hidx)
@@ -381,6 +398,9 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     else:
         s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
     s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
+    if prior is not None:
+        s.pgSetPriorEdges(kq, ptype, prob["vq"], prob["zq"], prob["omega_q"], prob.get("prior_offset"))
+        s.prior_set = kq
     if huber_delta > 0:
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
     s.landmark_sets = (k0, k1)

@@ -376,7 +376,8 @@ def _wrap(theta):
 
 def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, window=2, max_obs=None, seed=42,
                        noise_odometry=(0.02, 0.01), noise_landmark=0.05, outlier_frac=0.0, perturb=(0.1, 0.02, 0.2),
-                       closure_stride=5, fixed_landmarks=0, observation="xyz", kcam=(525.0, 515.0, 319.5, 239.5), z_min=1.0):
+                       closure_stride=5, fixed_landmarks=0, observation="xyz", kcam=(525.0, 515.0, 319.5, 239.5), z_min=1.0, *,
+                       priors=None, prior_stride=10, noise_prior=(0.3, 0.05), gauge="fixed"):
     """Landmark SLAM graph: odometry between poses plus point landmarks observed from them.
     kind "se2": VertexSE2 / VertexPointXY with EdgeSE2 + EdgeSE2PointXY; "se3": VertexSE3 / VertexPointXYZ with EdgeSE3 +
     EdgeSE3PointXYZ and one non-identity sensor offset (ParameterSE3Offset).
@@ -398,9 +399,27 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
     truth and at the initial estimates (the reference has no guard for a point behind the image plane); a landmark left with
     no observation is an error.  Information: the reference's defaults diag(1, 1, 100) (depth) / diag(1, 1, 1000) (disparity);
     the noise matches them: sigma 1 pixel, 0.1 m, 1000^-1/2 m^-1.  Outliers: up to 50 pixels and half the depth / disparity
-    range.  The dict then also carries `observation` and `kcam`."""
+    range.  The dict then also carries `observation` and `kcam`.
+    priors = "pose" | "xy": unary priors on poses (GPS-like fixes) -- EdgeSE2Prior / EdgeSE3Prior on the whole pose, or
+    EdgeSE2XYPrior on the position alone ("xy": kind "se2" only) -- on every `prior_stride`-th pose (0, stride, 2 stride, ...)
+    PLUS a second, independently measured one on pose `prior_stride`, so that one vertex carries two priors.  Measurements:
+    the ground truth with noise_prior = (translation, rotation) sigma, matching information matrices; the 3-D prior is taken
+    through a lever arm `prior_offset` (ParameterSE3Offset, distinct from the sensor `offset`): Z = X prior_offset noise.  The
+    dict then also carries prior (= priors), vq (pose of every prior), zq ([n][3 | 2 | 12]), omega_q and, 3-D, prior_offset.
+    gauge = "free" (needs priors): no pose is fixed, every hidx >= 0 and nP = n; the priors alone hold the gauge.  With
+    priors=None and gauge="fixed" the dict is what it was before these options existed."""
     if kind not in ("se2", "se3"):
         raise ValueError("kind must be 'se2' or 'se3'")
+    if priors not in (None, "pose", "xy"):
+        raise ValueError("priors must be None, 'pose' or 'xy'")
+    if priors == "xy" and kind != "se2":
+        raise ValueError("priors = 'xy' (EdgeSE2XYPrior) belongs to kind 'se2'")
+    if gauge not in ("fixed", "free"):
+        raise ValueError("gauge must be 'fixed' or 'free'")
+    if gauge == "free" and priors is None:
+        raise ValueError("gauge = 'free' needs priors: nothing else holds the gauge")
+    if priors is not None and int(prior_stride) < 1:
+        raise ValueError("prior_stride must be at least 1")
     if observation not in ("xyz", "depth", "disparity"):
         raise ValueError("observation must be 'xyz', 'depth' or 'disparity'")
     se2 = kind == "se2"
@@ -530,6 +549,8 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
     points[:fixed_landmarks] = points_true[:fixed_landmarks]
     hidx = np.arange(n, dtype=np.int32) - 1                         # pose 0 fixed
     nP, nL = n - 1, L - int(fixed_landmarks)
+    if gauge == "free":
+        hidx, nP = np.arange(n, dtype=np.int32), n
     pt_hidx = np.where(np.arange(L) < fixed_landmarks, -1, nP + np.arange(L) - int(fixed_landmarks)).astype(np.int32)
     dp = 3 if se2 else 6
     out = dict(kind=kind, n=n, L=L, nP=nP, nL=nL, E=E, M=M, vi=vi, vj=vj, Z=Z, omega=np.tile(info.T.reshape(1, dp * dp), (E, 1)),
@@ -538,4 +559,27 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
                pt_hidx=pt_hidx)
     if camera:
         out.update(observation=observation, kcam=np.array([float(v) for v in kcam]))
+    if priors is not None:
+        stride = int(prior_stride)
+        vq = np.concatenate([np.arange(0, n, stride), [stride] if stride < n else []]).astype(np.int32)
+        Q = len(vq)
+        pt, pr = noise_prior
+        if se2:
+            xy = poses_true[vq, :2] + pt * np.stack([rng.normal(260, Q), rng.normal(261, Q)], axis=1)
+            if priors == "xy":
+                zq, info_q = xy, np.eye(2) / pt ** 2
+            else:
+                zq = np.concatenate([xy, _wrap(poses_true[vq, 2] + pr * rng.normal(262, Q))[:, None]], axis=1)
+                info_q = np.diag([1 / pt ** 2, 1 / pt ** 2, 1 / pr ** 2])
+        else:
+            Rq = _exp_so3(np.array([[-0.2, 0.15, 0.1]]))[0][0]       # the lever arm of the prior's sensor (a GPS antenna)
+            tq = np.array([-0.3, 0.2, 0.1])
+            out.update(prior_offset=_iso_pack(Rq[None], tq[None])[0])
+            Rz = R[vq] @ Rq @ _exp_so3(np.stack([rng.normal(263 + q, Q) for q in range(3)], axis=1) * pr)[0]
+            tz = np.einsum("nij,j->ni", R[vq], tq) + pos[vq] + pt * np.stack([rng.normal(260 + q, Q) for q in range(3)], axis=1)
+            zq = _iso_pack(Rz, tz)
+            info_q = np.zeros((6, 6))
+            info_q[:3, :3] = np.eye(3) / pt ** 2
+            info_q[3:, 3:] = np.eye(3) / (0.5 * pr) ** 2              # (quaternion vector: half the angle)
+        out.update(prior=priors, vq=vq, zq=zq, omega_q=np.tile(info_q.reshape(1, -1), (Q, 1)))
     return out
