@@ -216,7 +216,8 @@ int g2ohip_kernel_time(g2ohip_solver* s, int slot, double* total_seconds, long* 
  * Krylov loop, e.g. sharded over GPUs with one all-reduce of the product per iteration, use these directly):
  * prepare: Dinv = (Hll + lambda_l I)^-1, bschur = b_p - Hpl Dinv b_l (g2ohip_device_array 100) and the diagonal blocks
  * Hpp_ii + lambda_p I - sum B Dinv B' (g2ohip_device_array 107, [nP][p*p]); apply: out = (Hpp + lambda_p I - Hpl Dinv Hpl') in
- * on device vectors of nP*p doubles.  With landmarks sharded over ranks both are this rank's summands. */
+ * on device vectors of nP*p doubles (in and out must not be the same vector: that is refused as a bad argument).  With
+ * landmarks sharded over ranks both are this rank's summands. */
 int g2ohip_schur_operator_prepare(g2ohip_solver* s);
 int g2ohip_schur_operator_apply(g2ohip_solver* s, const double* in_device, double* out_device);
 int g2ohip_solve_async(g2ohip_solver* s);

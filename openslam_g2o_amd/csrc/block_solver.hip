@@ -2265,6 +2265,9 @@ void BlockSolver::init() {
   invalidate_graphs();
   // block_solver.hpp:606-620: numeric + symbolic state is rebuilt on the next buildStructure/solve
   if (chol_) chol_->reset();
+  // LinearSolverPCG::init() (linear_solver_pcg.h:64-70): the residual carried into the next solve's stopping level is forgotten
+  if (pcg_) pcg_->reset_residual();
+  if (pcg_mf_) pcg_mf_->reset_residual();
   system_built_ = false;
 }
 
@@ -4421,9 +4424,11 @@ void BlockSolver::schur_operator_prepare() {
   G2OHIP_HIP_CHECK(hipGetLastError());
 }
 
-// dout = (Hpp + lam_p I - Hpl Dinv Hpl') din on device vectors of nP * p doubles (after schur_operator_prepare)
+// dout = (Hpp + lam_p I - Hpl Dinv Hpl') din on device vectors of nP * p doubles (after schur_operator_prepare).  Not in
+// place: the Hpp product gathers din of the neighbouring block rows while other workgroups already write dout.
 void BlockSolver::schur_operator_apply(const double* din, double* dout) {
   if (!mf_ready_) throw StateFailure("schur_operator_apply before schur_operator_prepare");
+  if (din == dout) throw ArgFailure("schur_operator_apply: in and out must be different vectors");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t sizeP = (size_t)nP_ * p_;
   const int gl = grid_for(nL_), gp = grid_for(sizeP);
