@@ -138,7 +138,8 @@ int g2ohip_set_robust_kernel(g2ohip_solver* s, int set, int kind, double delta);
 /* The same per EDGE: in g2o the robust kernel is a member of the edge (optimizable_graph.h:436-443, asked per edge by
  * base_binary_edge.hpp:92-112), so a pose graph with kernels on its loop closures only is still ONE set of EdgeSE2 / EdgeSE3.
  * kind [n], delta [n] (kind 0 = none for that edge); kind == NULL returns to the set-level kernel.  Not for a set bound to the
- * BA front end (g2ohip_ba_set_edges_classes carries the kernels there: G2OHIP_ERR_STATE).  Edges appended later by
+ * BA front end by g2ohip_ba_set_edges* (g2ohip_ba_set_edges_classes carries the kernels there: G2OHIP_ERR_STATE; a set bound by
+ * g2ohip_ba_set_stereo_edges takes them).  Edges appended later by
  * g2ohip_update_structure start with no kernel until this is called again for the grown set. */
 int g2ohip_set_robust_kernel_per_edge(g2ohip_solver* s, int set, const int32_t* kind, const double* delta);
 
@@ -243,7 +244,8 @@ int g2ohip_trial_stats(g2ohip_solver* s, double lambda, int* solve_ok, double* c
  * one GPU folds the Schur reduction into the factorisation; Hschur is then written only when it is asked for),
  * "ba_fused" (1: the BA edge set's errors and Jacobians evaluated inside the assembly kernels), "ba_fuse_landmarks" (1: the
  * landmark side of the fused BA path assembled by the Schur tiles of the solve), "pg_landmark_staged" (1: the landmark linearize
- * kernels of the pose-graph front end store through LDS; 0: one lane per edge, for the comparison), "use_graph" (0), "mask_solution" (1),
+ * kernels of the pose-graph front end store through LDS; 0: one lane per edge, for the comparison), "ba_stereo_staged" (1: the
+ * same choice for the linearize kernel of g2ohip_ba_set_stereo_edges), "use_graph" (0), "mask_solution" (1),
  * "marginals_reduced" (0) / "marginals_recursion" (1) (see g2ohip_compute_marginals), "setup_overlap" (1: the symbolic
  * analysis next to the Schur tiles' set-up), "pcg_check_every" (16: PCG iterations between looks at the convergence flag),
  * "sharded_graph" (1: g2ohip_solve_sharded as one hipGraph where nothing crosses the host; 2: with RCCL too),
@@ -415,6 +417,21 @@ int g2ohip_ba_set_edges(g2ohip_solver* s, int set, const int32_t* cam_vertex, co
  * g2ohip_set_robust_kernel on the set is refused (G2OHIP_ERR_STATE) while the classes are bound. */
 int g2ohip_ba_set_edges_classes(g2ohip_solver* s, int set, const int32_t* cam_vertex, const int32_t* point_vertex, const double* meas,
                                 const double* info, int n_classes, const double* class_params, const int32_t* edge_class);
+/* The same slot bound to STEREO observations: EdgeProjectXYZ2UVU (g2o/types/sba/types_six_dof_expmap.h:181-200; error
+ * (u_left, v_left, u_right) = obs - CameraParameters::stereocam_uvu_map(T.map(X)), types_six_dof_expmap.cpp:40, 77-82, with the fourth
+ * field of CameraParameters, `baseline`, types_six_dof_expmap.h:53-80: u_right = f (x - baseline) / z + cx).  Edge set `set` was added
+ * with error_dim 3, vertex 0 = 3-dof point, vertex 1 = 6-dof pose, on a (6, 3) solver (anything else: G2OHIP_ERR_ARG);
+ * measurements [n][3], information [n][3x3] column-major (NULL = identity).  After g2ohip_build_structure.  The front end has ONE
+ * slot: a later g2ohip_ba_set_edges* or g2ohip_ba_set_stereo_edges replaces the binding; one that is rejected (null array,
+ * non-finite parameter or focal_length == 0, index outside the estimate tables, hessian indices that differ from the set's:
+ * G2OHIP_ERR_ARG; a set that carries per-edge robust kernels: G2OHIP_ERR_STATE) leaves the previous binding usable.
+ * The reference leaves linearizeOplus of this edge commented out (types_six_dof_expmap.h:199) and differentiates numerically;
+ * the device writes the exact derivative.  A stereo set always takes the generic assembly (option "ba_fused" is ignored for
+ * it, edge classes are not offered): fixed cameras and points, several observations of one (pose, landmark) pair,
+ * g2ohip_set_robust_kernel and -- on the bound set -- g2ohip_set_robust_kernel_per_edge, do_schur 0 / 1, every linear_solver
+ * and use_graph work as for any generic set.  Everything below (set_estimates ... discard_top) acts on it unchanged. */
+int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_vertex, const int32_t* point_vertex, const double* meas,
+                               const double* info, double focal_length, double cx, double cy, double baseline);
 /* setEstimate for every vertex + the index mapping: cam_hidx[v] = hessianIndex (-1 fixed),
  * point_hidx[v] = landmark index (0-based, i.e. hessianIndex - num_poses) or -1. */
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,

@@ -85,6 +85,13 @@ class HipBlockSolver {
     return ok(g2ohip_set_option(h_, "linear_solver", on ? 1.0 : 0.0), "set_option") &&
            ok(g2ohip_set_option(h_, "pcg_tolerance", tolerance), "set_option");
   }
+  // EdgeProjectXYZ2UVU observations (stereo bundle adjustment) in the slot of the device-resident BA front end
+  // (g2ohip_ba_set_stereo_edges; the estimates and the trial loop through handle()): `set` was added with errorDim 3, vertex 0 =
+  // point, vertex 1 = pose; meas [n][3] = (u_left, v_left, u_right), info [n][3x3] or nullptr (identity)
+  bool baSetStereoEdges(int set, const int32_t* camVertex, const int32_t* pointVertex, const double* meas, const double* info,
+                        double focalLength, double cx, double cy, double baseline) {
+    return ok(g2ohip_ba_set_stereo_edges(h_, set, camVertex, pointVertex, meas, info, focalLength, cx, cy, baseline), "baSetStereoEdges");
+  }
   // EdgeSE3PointXYZDepth (type 5) / EdgeSE3PointXYZDisparity (type 6) observations with one ParameterCamera, kept on the device
   // beside an EdgeSE3 pose set of g2ohip_pg_set_edges (handle()): offset isometry [12] or nullptr, kcam = fx, fy, cx, cy
   bool pgSetLandmarkCameraEdges(int set, int type, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas,

@@ -132,6 +132,9 @@ class BlockSolver {
                     double cx, double cy);
   void ba_set_edges_classes(int set, const int* cam_vertex, const int* point_vertex, const double* meas, const double* info, double f,
                             double cx, double cy, int n_classes, const double* class_params, const int* edge_class);
+  // the same slot bound to a set of stereo observations (EdgeProjectXYZ2UVU, error (u_left, v_left, u_right)): ba_stereo.inc
+  void ba_set_stereo_edges(int set, const int* cam_vertex, const int* point_vertex, const double* meas, const double* info, double f,
+                           double cx, double cy, double baseline);
   void ba_set_estimates(int n_cams, const double* cams, const int* cam_hidx, int n_points, const double* points, const int* point_hidx);
   void ba_get_estimates(double* cams, double* points);
   void ba_get_estimates_of(int n_cams, const int* cam_idx, double* cams, int n_points, const int* point_idx, double* points);   // selected vertices
@@ -281,6 +284,7 @@ class BlockSolver {
                                       // assembled by the Schur tiles of the solve, which write only b_l and Dinv, what the solve reads
   bool marginals_recursion = true;  // compute_marginals: all entries on the pattern of L in one top-down pass (sparse inverse) instead of one pair of sweeps per column
   bool pg_landmark_staged = true;   // landmark linearize kernels: results leave through LDS, contiguous per wave (pg_landmark.inc)
+  bool ba_stereo_staged = true;     // the stereo BA linearize kernel likewise (ba_stereo.inc)
   bool marginals_reduced = false;   // compute_marginals: invert the reduced pose system instead of Hpp alone (the reference inverts Hpp)
  private:
   hipStream_t fetch_st_ = nullptr;                         // ba_fetch_begin: the copy stream of the asynchronous estimate read-back
@@ -383,6 +387,8 @@ class BlockSolver {
     int set = -1, n_edges = 0;
     EstimateTable cams, pts;    // T[12] per camera, (x, y, z) per point
     double f = 0, cx = 0, cy = 0;
+    bool stereo = false;        // the set holds EdgeProjectXYZ2UVU observations (ba_set_stereo_edges): meas [n][3], always the generic
+    double baseline = 0;        // assembly (fused_ok = false, none of the fused tables below), per-edge robust kernels allowed
     int n_classes = 1;          // edge classes (ba_set_edges_classes): > 1 = the class of an observation rides in the top byte of its
     DevBuf<double> ctab;        // camera index, ctab[5 c] = (f, cx, cy, robust kernel kind, delta)
     std::vector<double> h_ctab;

@@ -2082,6 +2082,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 }
 #include "pg_landmark.inc"
 #include "pg_prior.inc"
+#include "ba_stereo.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -3079,7 +3080,7 @@ void BlockSolver::set_robust_kernel_per_edge(int set, const int* kind, const dou
     return;
   }
   if (!delta) throw ArgFailure("set_robust_kernel_per_edge: null delta array");
-  if (set == ba_.set && ba_.set >= 0)
+  if (set == ba_.set && ba_.set >= 0 && !ba_.stereo)   // (a stereo set is assembled by the generic kernels, which read es.rk, and so does its producer)
     throw StateFailure("set_robust_kernel_per_edge: the set is bound to the BA front end; per-edge kernels go through ba_set_edges_classes there");
   std::vector<double> h((size_t)es.n * 2);
   for (int k = 0; k < es.n; ++k) {
@@ -4863,6 +4864,8 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
   ba_.set = set;
   ba_.n_edges = es.n;
   ba_.f = f; ba_.cx = cx; ba_.cy = cy;
+  ba_.stereo = false;
+  ba_.baseline = 0;
   ba_.n_classes = n_classes;
   if (n_classes > 1) {
     ba_.h_ctab.assign(class_params, class_params + 5 * (size_t)n_classes);
@@ -5043,6 +5046,72 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
   prepare_ba_tile_kernels();
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
   lap("buffers, kernel attributes, sync");
+}
+
+// ---- ... bound to stereo observations: EdgeProjectXYZ2UVU (ba_stereo.inc) -------------------------------------------------
+// The front end's one slot with meas [n][3] = (u_left, v_left, u_right) and the fourth field of CameraParameters.  Such a set always
+// takes the generic path: ba_linearize writes J0 / J1 / err with ba_stereo_linearize_kernel and the generic assembly, Schur tiles,
+// factorisation and back-substitution take over (fused_ok = false whatever ba_fused says; none of the fused tables is built, and
+// those of an earlier mono binding are dropped).  Fixed cameras and points, several observations of one (pose, landmark) pair,
+// set-level and -- after the binding -- per-edge robust kernels are what that path allows anyway.  Validate, then commit.
+void BlockSolver::ba_set_stereo_edges(int set, const int* cam_vertex, const int* point_vertex, const double* meas, const double* info,
+                                      double f, double cx, double cy, double baseline) {
+  invalidate_graphs();
+  require_structure();
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  EdgeSet& es = *sets_[set];
+  if (es.d != 3 || es.unary || es.dim0 != 3 || es.dim1 != 6 || p_ != 6 || l_ != 3)
+    throw ArgFailure("ba_set_stereo_edges: the set must be EdgeProjectXYZ2UVU-shaped (d=3, vertex0 = 3-dof point, vertex1 = 6-dof pose)");
+  if (!cam_vertex || !point_vertex || !meas) throw ArgFailure("ba_set_stereo_edges: null array");
+  if (!std::isfinite(f) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
+    throw ArgFailure("ba_set_stereo_edges: non-finite camera parameters");
+  if (f == 0.0) throw ArgFailure("ba_set_stereo_edges: the focal length must not be zero");
+  if (es.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel; per-edge ones are set on the bound set)
+    throw StateFailure("ba_set_stereo_edges: the set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound set");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const size_t n = (size_t)es.n;
+  ba_validate_edges(es, cam_vertex, point_vertex, n, ba_.cams.h_hidx.data(), ba_.cams.n, ba_.pts.h_hidx.data(), ba_.pts.n);
+  ba_.set = set;
+  ba_.n_edges = es.n;
+  ba_.f = f; ba_.cx = cx; ba_.cy = cy;
+  ba_.stereo = true;
+  ba_.baseline = baseline;
+  ba_.n_classes = 1;
+  ba_.h_ctab.clear();
+  ba_.ctab.release();
+  ba_.h_cam_v.assign(cam_vertex, cam_vertex + n);
+  ba_.h_pt_v.assign(point_vertex, point_vertex + n);
+  ba_.err_valid = ba_.jac_valid = false;
+  chi2_valid_ = false;
+  ba_.sys_version = -1;
+  ba_.fused_ok = false;
+  ba_.ll_slots_ok = false;
+  for (DevBuf<int>* b : {&ba_.edge_hpl, &ba_.pt_pm, &ba_.cam_pm, &ba_.cam_q, &ba_.pt_q, &ba_.cam_lm, &ba_.pt_lm, &ba_.hpl_lm, &ba_.row_lm,
+                         &ba_.ll_edge, &ba_.ll_row})
+    b->release();
+  for (DevBuf<double>* b : {&ba_.meas_pm, &ba_.omega_pm, &ba_.meas_lm, &ba_.omega_lm, &ba_.meas_q, &ba_.omega_q, &ba_.ll_meas, &ba_.ll_omega})
+    b->release();
+  ba_.ll_rec.release();
+  ba_.tile_ll.release();
+  ba_.cam_v.upload(cam_vertex, n, st_);
+  ba_.pt_v.upload(point_vertex, n, st_);
+  ba_.meas.upload(meas, n * 3, st_);
+  ba_.omega_identity = info == nullptr;
+  if (!info) {   // information().setIdentity(): written on the device, not read per edge by the producer
+    es.own_omega.alloc(n * 9);
+    if (n) hipLaunchKernelGGL(identity3_kernel, dim3(grid_for(n * 9)), dim3(kThreads), 0, st_, n, es.own_omega.p);
+  } else {
+    es.own_omega.upload(info, n * 9, st_);
+  }
+  es.own_J0.alloc(n * 9);
+  es.own_J1.alloc(n * 18);
+  es.own_err.alloc(n * 3);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;   // becomes valid with the first ba_linearize
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipGetLastError());
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 // Edge -> estimate indices against the estimate tables and against the edge set's hessian indices: a wrong index would be
@@ -5258,9 +5327,9 @@ void BlockSolver::ba_linearize(bool jacobians) {
     if (jacobians) es.has_data = true;
     return;
   }
-  if (need_jac && (es.own_J0.n < (size_t)es.n * 6 || es.own_J1.n < (size_t)es.n * 12)) {   // (left out by ba_set_edges on the fused path)
-    es.own_J0.alloc((size_t)es.n * 6);
-    es.own_J1.alloc((size_t)es.n * 12);
+  if (need_jac && (es.own_J0.n < (size_t)es.n * es.d * 3 || es.own_J1.n < (size_t)es.n * es.d * 6)) {   // (left out by ba_set_edges on the fused path)
+    es.own_J0.alloc((size_t)es.n * es.d * 3);
+    es.own_J1.alloc((size_t)es.n * es.d * 6);
     es.J0 = es.own_J0.p;
     es.J1 = es.own_J1.p;
     invalidate_graphs();   // (clears err_valid / jac_valid: before they are set for the evaluation below)
@@ -5274,10 +5343,20 @@ void BlockSolver::ba_linearize(bool jacobians) {
   const int lgrid = grid_for(es.n);
   if (d_red_multi.n < (sets_.size() + 1) * kMaxBlocks) d_red_multi.alloc((sets_.size() + 1) * kMaxBlocks);
   if (ba_.chi_part.n < (size_t)lgrid) ba_.chi_part.alloc(lgrid);
-  hipLaunchKernelGGL(ba_linearize_kernel, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.val.p, ba_.pts.val.p, ba_.cam_v.p,
-                     ba_.pt_v.p, ba_.meas.p, ba_.f, ba_.cx, ba_.cy, es.own_J0.p, es.own_J1.p, es.own_err.p, (jacobians && !fused) ? 1 : 0,
-                     es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, ba_.chi_part.p,
-                     ba_.n_classes > 1 ? ba_.ctab.p : (const double*)nullptr);
+  if (ba_.stereo) {
+    if (es.n > 0)   // (the kernel clamps its edge index to n - 1)
+      with_bool(ba_stereo_staged, [&](auto staged) {
+        constexpr bool STAGED = staged;
+        hipLaunchKernelGGL(ba_stereo_linearize_kernel<STAGED>, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.val.p, ba_.pts.val.p,
+                           ba_.cam_v.p, ba_.pt_v.p, ba_.meas.p, ba_.f, ba_.cx, ba_.cy, ba_.baseline, es.own_J0.p, es.own_J1.p, es.own_err.p,
+                           need_jac ? 1 : 0, es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, es.rk.p, ba_.chi_part.p);
+      });
+  } else {
+    hipLaunchKernelGGL(ba_linearize_kernel, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.val.p, ba_.pts.val.p, ba_.cam_v.p,
+                       ba_.pt_v.p, ba_.meas.p, ba_.f, ba_.cx, ba_.cy, es.own_J0.p, es.own_J1.p, es.own_err.p, (jacobians && !fused) ? 1 : 0,
+                       es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, ba_.chi_part.p,
+                       ba_.n_classes > 1 ? ba_.ctab.p : (const double*)nullptr);
+  }
   hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(1024), 0, st_, ba_.chi_part.p, lgrid, d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks);
   if (profiling) {
     tfe_.stop(st_);

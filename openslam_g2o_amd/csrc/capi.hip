@@ -128,6 +128,7 @@ bool set_solver_option(BlockSolver& solver, const char* name, double value) {
       {"marginals_reduced", [](BlockSolver& b, double v) { b.marginals_reduced = v != 0; }},
       // (the next pg_linearize evaluates again, in the chosen form)
       {"pg_landmark_staged", [](BlockSolver& b, double v) { b.pg_landmark_staged = v != 0; }},
+      {"ba_stereo_staged", [](BlockSolver& b, double v) { b.ba_stereo_staged = v != 0; }},   // (likewise the next ba_linearize)
       {"marginals_recursion", [](BlockSolver& b, double v) { b.marginals_recursion = v != 0; }},
       {"use_graph", [](BlockSolver& b, double v) { b.use_graph = v != 0; }},
       {"sharded_graph", [](BlockSolver& b, double v) { b.sharded_graph = (int)v; }},
@@ -533,6 +534,10 @@ int g2ohip_ba_set_edges_classes(g2ohip_solver* s, int set, const int32_t* cam_ve
                            edge_class);
     if (n_classes == 1) b.set_robust_kernel(set, (int)class_params[3], class_params[4]);
   });
+}
+int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_vertex, const int32_t* point_vertex, const double* meas,
+                               const double* info, double focal_length, double cx, double cy, double baseline) {
+  return entry(s, [&](BlockSolver& b) { b.ba_set_stereo_edges(set, cam_vertex, point_vertex, meas, info, focal_length, cx, cy, baseline); });
 }
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,
                             const double* points, const int32_t* point_hidx) {

@@ -307,6 +307,8 @@ def write_g2o_landmarks(path, prob):
 # VERTEX_XYZ id x y z                                  types_sba.cpp:40 (VertexSBAPointXYZ)
 # EDGE_PROJECT_XYZ2UV:EXPMAP point pose param u v i00 i01 i11   (types_six_dof_expmap.cpp:241-270; the point is
 #                                                      vertex 0, types_six_dof_expmap.h:133)
+# EDGE_PROJECT_XYZ2UVU:EXPMAP point pose u v u_r i00 i01 i02 i11 i12 i22   (stereo; types_six_dof_expmap.cpp:328-351: no
+#                                                      parameter id on the line)
 # FIX id ...                                           optimizable_graph.cpp:407-420
 def _quat_to_R(q):
     """(x, y, z, w) -> rotation matrices [n][3][3] (Eigen's toRotationMatrix, no normalisation)."""
@@ -348,7 +350,9 @@ def _R_to_quat(R):
 
 
 def write_g2o_ba(path, prob):
-    """openslam_g2o_amd.synthetic-style BA problem -> `.g2o` text (cameras get ids 0..P-1, points P..P+L-1)."""
+    """openslam_g2o_amd.synthetic-style BA problem -> `.g2o` text (cameras get ids 0..P-1, points P..P+L-1).  A problem with
+    observation = "stereo" writes EDGE_PROJECT_XYZ2UVU:EXPMAP lines and its baseline in the parameter line."""
+    stereo = prob.get("observation") == "stereo"
     cams, pts = np.asarray(prob["cams"]), np.asarray(prob["pts"])
     P = len(cams)
     Rwc = cams[:, 0:9].reshape(-1, 3, 3).transpose(0, 2, 1)            # world -> camera, stored column-major
@@ -357,7 +361,10 @@ def write_g2o_ba(path, prob):
     tcw = -(Rcw @ twc[:, :, None])[:, :, 0]
     q = _R_to_quat(Rcw)
     with open(path, "w") as f:
-        f.write("PARAMS_CAMERAPARAMETERS 0 %.17g %.17g %.17g 0\n" % (prob["f"], prob["cx"], prob["cy"]))
+        if stereo:
+            f.write("PARAMS_CAMERAPARAMETERS 0 %.17g %.17g %.17g %.17g\n" % (prob["f"], prob["cx"], prob["cy"], prob["baseline"]))
+        else:
+            f.write("PARAMS_CAMERAPARAMETERS 0 %.17g %.17g %.17g 0\n" % (prob["f"], prob["cx"], prob["cy"]))
         for i in range(P):
             f.write("VERTEX_SE3:EXPMAP %d %s\n" % (i, " ".join("%.17g" % v for v in (*tcw[i], *q[i]))))
         for j in range(len(pts)):
@@ -366,7 +373,11 @@ def write_g2o_ba(path, prob):
         if fixed:
             f.write("FIX %s\n" % " ".join(str(i) for i in fixed))
         info = prob.get("omega")
-        for e in range(len(prob["meas"])):
+        for e in range(len(prob["meas"]) if stereo else 0):
+            io = (1.0, 0.0, 0.0, 1.0, 0.0, 1.0) if info is None else [info[e][i + 3 * j] for i in range(3) for j in range(i, 3)]   # column-major 3x3 -> upper
+            f.write("EDGE_PROJECT_XYZ2UVU:EXPMAP %d %d %s\n" % (
+                P + prob["pt_idx"][e], prob["cam_idx"][e], " ".join("%.17g" % v for v in (*prob["meas"][e], *io))))
+        for e in range(0 if stereo else len(prob["meas"])):
             io = (1.0, 0.0, 1.0) if info is None else (info[e][0], info[e][2], info[e][3])   # column-major 2x2 -> upper
             f.write("EDGE_PROJECT_XYZ2UV:EXPMAP %d %d 0 %.17g %.17g %.17g %.17g %.17g\n" % (
                 P + prob["pt_idx"][e], prob["cam_idx"][e], prob["meas"][e][0], prob["meas"][e][1], *io))
@@ -374,7 +385,10 @@ def write_g2o_ba(path, prob):
 
 def read_g2o_ba(path):
     """`.g2o` BA file -> problem dict in the layout of openslam_g2o_amd.synthetic.make_ba_problem (index mapping:
-    free poses by vertex id, then points by vertex id, sparse_optimizer.cpp:174-187; FIX or no FIX: gauge left to the caller)."""
+    free poses by vertex id, then points by vertex id, sparse_optimizer.cpp:174-187; FIX or no FIX: gauge left to the caller).
+    A file of EDGE_PROJECT_XYZ2UVU:EXPMAP lines gives observation = "stereo", baseline (the fourth field of
+    PARAMS_CAMERAPARAMETERS), meas [E][3] and omega [E][9]; one that mixes the two edge tags raises ValueError."""
+    stereo, baseline = None, None
     cam_id, cam_v, pt_id, pt_v, e_pt, e_cam, meas, info, fixed = [], [], [], [], [], [], [], [], []
     f_, cx, cy = None, None, None
     with open(path) as fh:
@@ -385,13 +399,25 @@ def read_g2o_ba(path):
             tag = t[0]
             if tag == "PARAMS_CAMERAPARAMETERS":
                 f_, cx, cy = float(t[2]), float(t[3]), float(t[4])
+                baseline = float(t[5]) if len(t) > 5 else None
             elif tag == "VERTEX_SE3:EXPMAP":
                 cam_id.append(int(t[1]))
                 cam_v.append([float(x) for x in t[2:9]])
             elif tag in ("VERTEX_XYZ", "VERTEX_TRACKXYZ"):
                 pt_id.append(int(t[1]))
                 pt_v.append([float(x) for x in t[2:5]])
+            elif tag == "EDGE_PROJECT_XYZ2UVU:EXPMAP":
+                if stereo is False:
+                    raise ValueError("%s mixes EDGE_PROJECT_XYZ2UV:EXPMAP and EDGE_PROJECT_XYZ2UVU:EXPMAP: one observation set is one edge type" % path)
+                stereo = True
+                e_pt.append(int(t[1]))
+                e_cam.append(int(t[2]))
+                meas.append([float(x) for x in t[3:6]])
+                info.append(_upper_to_full([float(x) for x in t[6:12]], 3).T.reshape(9))      # column-major 3x3
             elif tag == "EDGE_PROJECT_XYZ2UV:EXPMAP":
+                if stereo:
+                    raise ValueError("%s mixes EDGE_PROJECT_XYZ2UV:EXPMAP and EDGE_PROJECT_XYZ2UVU:EXPMAP: one observation set is one edge type" % path)
+                stereo = False
                 e_pt.append(int(t[1]))
                 e_cam.append(int(t[2]))
                 meas.append([float(t[4]), float(t[5])])
@@ -424,6 +450,11 @@ def read_g2o_ba(path):
             cam_hidx[i] = k
             k += 1
     nP, L = k, len(pts)
-    return dict(P=len(cams), L=L, E=len(meas), nP=nP, nL=L, f=f_, cx=cx, cy=cy, cams=cams, pts=pts,
-                meas=np.asarray(meas, np.float64), omega=np.asarray(info, np.float64), cam_idx=cam_idx, pt_idx=pt_idx,
-                cam_hidx=cam_hidx, v0=(nP + pt_idx).astype(np.int32), v1=cam_hidx[cam_idx].astype(np.int32))
+    out = dict(P=len(cams), L=L, E=len(meas), nP=nP, nL=L, f=f_, cx=cx, cy=cy, cams=cams, pts=pts,
+               meas=np.asarray(meas, np.float64), omega=np.asarray(info, np.float64), cam_idx=cam_idx, pt_idx=pt_idx,
+               cam_hidx=cam_hidx, v0=(nP + pt_idx).astype(np.int32), v1=cam_hidx[cam_idx].astype(np.int32))
+    if stereo:
+        if baseline is None:
+            raise ValueError("PARAMS_CAMERAPARAMETERS of %s has no baseline field" % path)
+        out.update(observation="stereo", baseline=baseline)
+    return out

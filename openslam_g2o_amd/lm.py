@@ -289,15 +289,20 @@ class DeviceBAGraph:
 def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
     """Build a HipBlockSolver for an openslam_g2o_amd.synthetic BA problem with the estimates, errors
     and Jacobians produced on the device.  Returns (solver, graph).  options: g2ohip_set_option pairs that have to be
-    in place before buildStructure (ordering / kernel selection knobs)."""
+    in place before buildStructure (ordering / kernel selection knobs).  A problem with observation = "stereo"
+    (make_ba_problem(..., stereo_baseline=b)) is a set of EdgeProjectXYZ2UVU: error_dim 3, bound through baSetStereoEdges."""
     import numpy as np
     from . import capi
+    stereo = prob.get("observation") == "stereo"
     s = capi.HipBlockSolver(6, 3, device)
     for name, value in (options or {}).items():
         s.setOption(name, value)
-    k = s.addEdgeSet(2, prob["v0"], prob["v1"])
+    k = s.addEdgeSet(3 if stereo else 2, prob["v0"], prob["v1"])
     s.buildStructure(prob["nP"], prob["nL"], True)
-    s.baSetEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"])
+    if stereo:
+        s.baSetStereoEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"], prob["baseline"])
+    else:
+        s.baSetEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"])
     s.baSetEstimates(prob["cams"], prob["cam_hidx"], prob["pts"], np.arange(prob["L"], dtype=np.int32))
     if huber_delta > 0:
         s.setRobustKernel(k, capi.KERNEL_HUBER, huber_delta)

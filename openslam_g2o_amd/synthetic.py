@@ -72,7 +72,12 @@ def _exp_so3(w):
 
 
 def make_ba_problem(P, L, seed=42, spacing=0.5, obs_per_landmark=5, outlier_frac=0.0,
-                    f=1000.0, cx=320.0, cy=240.0):
+                    f=1000.0, cx=320.0, cy=240.0, stereo_baseline=None):
+    """stereo_baseline = b: the observations are those of EdgeProjectXYZ2UVU (types_six_dof_expmap.h:181-200) -- the dictionary
+    gains observation = "stereo", baseline = b and meas [E][3] with u_right = f (x - b) / z + cx in its third column (noise:
+    normal stream 15 = uniform streams 30 / 31, outliers uniform over the image width from uniform stream 32; none of them used
+    otherwise).  Everything else, and
+    the whole dictionary without the argument, is as before."""
     rng = CounterRng(seed)
     K = obs_per_landmark
     assert P >= K
@@ -108,10 +113,16 @@ def make_ba_problem(P, L, seed=42, spacing=0.5, obs_per_landmark=5, outlier_frac
     cam_hidx = np.arange(P, dtype=np.int32) - 2
     cam_hidx[:2] = -1
     nP = P - 2
-    return dict(P=P, L=L, E=E, nP=nP, nL=L, f=f, cx=cx, cy=cy, cams=cams, pts=pts, meas=meas,
+    prob = dict(P=P, L=L, E=E, nP=nP, nL=L, f=f, cx=cx, cy=cy, cams=cams, pts=pts, meas=meas,
                 cam_idx=cam_idx, pt_idx=pt_idx, cam_hidx=cam_hidx,
                 v0=(nP + pt_idx).astype(np.int32),        # EdgeProjectXYZ2UV: vertex 0 = point
                 v1=cam_hidx[cam_idx].astype(np.int32))    # vertex 1 = pose (types_six_dof_expmap.h:133)
+    if stereo_baseline is not None:
+        ur = (Xc[:, 0] - stereo_baseline) / Xc[:, 2] * f + cx + rng.normal(15, E)
+        if outlier_frac > 0:
+            ur[is_out] = rng.uniform(32, E)[is_out] * 640.0
+        prob.update(observation="stereo", baseline=float(stereo_baseline), meas=np.concatenate([meas, ur[:, None]], axis=1))
+    return prob
 
 
 def make_ba_loops(P, L, laps=4, hubs=3, drop=0.2, seed=7, spacing=0.5, f=1000.0, cx=320.0, cy=240.0, hub_stride=3):
