@@ -467,7 +467,18 @@ int g2ohip_ba_discard_top(g2ohip_solver* s);
  * vertex_se2.h:55-59), estimates and measurements (x, y, theta), information [n][3x3];
  * type 2 = EdgeSE3 / VertexSE3 (g2o/types/slam3d/edge_se3.cpp:48-75, isometry3d_gradients.h:39-126,
  * vertex_se3.h:107-116), estimates and measurements as isometries [12] = R (column-major) | t,
- * information [n][6x6].  Edge set `set` was added with error_dim 3 / 6 and hessian indices of its two
+ * information [n][6x6];
+ * type 10 = EdgeSim3 / VertexSim3Expmap, the 7-dof pose graph of monocular SLAM (g2o/types/sim3/types_seven_dof_expmap.h:44-65
+ * oplusImpl, :94-102 computeError e = log(C Si Sj^-1); g2o/types/sim3/sim3.h:70-142 exp, :148-230 log, :233-236 inverse,
+ * :266-272 operator*): estimates and measurements are the members of the reference's Sim3, 8 doubles (qx, qy, qz, qw, tx, ty,
+ * tz, s), information [n][7x7], on a handle of pose dimension 7 and a set of error_dim 7.  The reference defines no Jacobian
+ * for this edge; the device evaluates what g2o then uses, the central differences of BaseBinaryEdge::linearizeOplus
+ * (g2o/core/base_binary_edge.hpp:132-201, delta = 1e-9) through oplusImpl, and writes zeros for the block of a fixed vertex.
+ * G2OHIP_ERR_ARG for a quaternion of norm 0, a scale <= 0 or a non-finite value in the measurements or estimates, for another
+ * pose or error dimension, and for any landmark, camera or prior set beside a type-10 set (either order).  Not covered:
+ * EdgeSim3ProjectXYZ, landmarks or priors beside a Sim3 set, sharded solves, the g2o plugin adapter (it keeps this edge on its
+ * host path).
+ * Edge set `set` was added with error_dim 3 / 6 / 7 and hessian indices of its two
  * vertices; vi/vj index the estimate array (all vertices, fixed ones included), hidx[v] = hessianIndex or -1.
  * The calls mirror the g2ohip_ba_* ones (set_edges after g2ohip_build_structure).
  * The set_edges / set_estimates entries of both front ends (g2ohip_ba_*, g2ohip_pg_*, the landmark half below) validate what
@@ -477,6 +488,10 @@ int g2ohip_ba_discard_top(g2ohip_solver* s);
 int g2ohip_pg_set_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const double* meas,
                         const double* info);
 int g2ohip_pg_set_estimates(g2ohip_solver* s, int n_vertices, const double* poses, const int32_t* hidx);
+/* VertexSim3Expmap::_fix_scale (types_seven_dof_expmap.h:60-61, 78) for every vertex of a type-10 binding: the sigma entry of a
+ * step is taken as zero in g2ohip_pg_update and in the perturbations of the numeric Jacobian, whose column 6 is then exactly
+ * zero.  Default 0; kept when g2ohip_update_structure drops the binding, back to 0 after g2ohip_clear_edge_sets. */
+int g2ohip_pg_set_sim3_fix_scale(g2ohip_solver* s, int fix_scale);
 int g2ohip_pg_get_estimates(g2ohip_solver* s, double* poses);
 int g2ohip_pg_linearize(g2ohip_solver* s, int jacobians);
 int g2ohip_pg_update(g2ohip_solver* s);

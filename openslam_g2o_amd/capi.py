@@ -60,7 +60,7 @@ EXPORTS = [
     "g2ohip_pg_set_edges", "g2ohip_pg_set_estimates", "g2ohip_pg_get_estimates", "g2ohip_pg_linearize", "g2ohip_pg_update",
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
-    "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges",
+    "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -162,6 +162,7 @@ def load():
     L.g2ohip_pg_set_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_pg_linearize.argtypes = [vp, C.c_int]
+    L.g2ohip_pg_set_sim3_fix_scale.argtypes = [vp, C.c_int]
     L.g2ohip_pg_set_landmark_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_camera_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -692,14 +693,22 @@ class HipBlockSolver:
         _check(self.L.g2ohip_copy_edge_data(self.h, set_id, _dp(J0), _dp(J1), _dp(err)), "edgeData")
         return J0, J1, err
 
-    # ---- device-resident pose-graph front end (EdgeSE2 = 1, EdgeSE3 = 2) ------------------------------
+    # ---- device-resident pose-graph front end (EdgeSE2 = 1, EdgeSE3 = 2, EdgeSim3 = 10) ---------------
+    PG_POSE_STRIDE = {1: 3, 2: 12, 10: 8}    # doubles per estimate / measurement; EdgeSim3: (qx, qy, qz, qw, tx, ty, tz, s)
+    PG_POSE_DIM = {1: 3, 2: 6, 10: 7}
+
     def pgSetEdges(self, set_id, edge_type, vi, vj, meas, info):
         vi, vj, meas, info = _i32(vi), _i32(vj), _f64(meas), _f64(info)
-        self._pg = (edge_type, 3 if edge_type == 1 else 12)
-        n, d = self._set_sizes[set_id], (3 if edge_type == 1 else 6)
-        if len(vi) != n or len(vj) != n or meas.size != n * self._pg[1] or info.size != n * d * d:
+        stride, d = self.PG_POSE_STRIDE.get(edge_type, 12), self.PG_POSE_DIM.get(edge_type, 6)
+        n = self._set_sizes[set_id]
+        if len(vi) != n or len(vj) != n or meas.size != n * stride or info.size != n * d * d:
             raise ValueError("pgSetEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
         _check(self.L.g2ohip_pg_set_edges(self.h, set_id, edge_type, _ip(vi), _ip(vj), _dp(meas), _dp(info)), "pgSetEdges")
+        self._pg = (edge_type, stride)      # (a refused call leaves the previous binding, here as in the library)
+
+    def pgSetSim3FixScale(self, fix_scale):
+        """VertexSim3Expmap::_fix_scale for every vertex of an EdgeSim3 binding (default off)."""
+        _check(self.L.g2ohip_pg_set_sim3_fix_scale(self.h, int(bool(fix_scale))), "pgSetSim3FixScale")
 
     def pgSetEstimates(self, poses, hidx):
         poses, hidx = _f64(poses), _i32(hidx)

@@ -103,6 +103,12 @@ class HipBlockSolver {
   bool pgSetPriorEdges(int set, int type, const int32_t* poseVertex, const double* meas, const double* info, const double* offset) {
     return ok(g2ohip_pg_set_prior_edges(h_, set, type, poseVertex, meas, info, offset), "pgSetPriorEdges");
   }
+  // EdgeSim3 over VertexSim3Expmap (g2ohip_pg_set_edges type 10): estimates / measurements (qx, qy, qz, qw, tx, ty, tz, s),
+  // information [n][49], on a solver of pose dimension 7; fixScale = VertexSim3Expmap::_fix_scale of every vertex
+  bool pgSetEdges(int set, int type, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
+    return ok(g2ohip_pg_set_edges(h_, set, type, vi, vj, meas, info), "pgSetEdges");
+  }
+  bool pgSetSim3FixScale(bool fixScale) { return ok(g2ohip_pg_set_sim3_fix_scale(h_, fixScale ? 1 : 0), "pgSetSim3FixScale"); }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -90,6 +90,7 @@ class BlockSolver {
   void copy_diagonal(double* host);
   void copy_edge_data(int set, double* J0, double* J1, double* err);
   void pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
+  void pg_set_sim3_fix_scale(bool fix_scale);
   void pg_set_estimates(int nv, const double* poses, const int* hidx);
   void pg_get_estimates(double* poses);
   void pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
@@ -440,7 +441,9 @@ class BlockSolver {
     DevBuf<int> vi, vj;
     std::vector<int> h_vi, h_vj;   // host copies: index validation (pg_validate)
     DevBuf<double> meas;
-    EstimateTable poses;           // (x, y, theta) or T[12] per pose
+    EstimateTable poses;           // (x, y, theta), T[12] or -- type 10 = EdgeSim3 over VertexSim3Expmap, which stands alone: no
+                                   // landmark or prior set beside it -- (qx, qy, qz, qw, tx, ty, tz, s) per pose
+    bool fix_scale = false;        // VertexSim3Expmap::_fix_scale of the whole table (pg_set_sim3_fix_scale)
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
     int lm_set = -1, lm_type = 0;

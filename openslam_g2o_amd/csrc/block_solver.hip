@@ -2082,6 +2082,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 }
 #include "pg_landmark.inc"
 #include "pg_prior.inc"
+#include "pg_sim3.inc"
 #include "ba_stereo.inc"
 #undef PG_R
 
@@ -2341,7 +2342,11 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
     // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again)
-    if (set == pg_.set || set == pg_.lm_set) pg_ = PgFrontEnd();
+    if (set == pg_.set || set == pg_.lm_set) {
+      const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
+      pg_ = PgFrontEnd();
+      pg_.fix_scale = fix_scale;
+    }
     if (set == ba_.set) ba_.set = -1;
     // per-edge robust kernels cover the old edge count: the new edges get "none" (kind 0) until set_robust_kernel_per_edge is
     // called again -- the array is extended on the device so that no kernel reads past its end
@@ -5411,21 +5416,49 @@ void BlockSolver::ba_discard_top() {
 }
 
 
-// ---- pose-graph front end (EdgeSE2 / EdgeSE3) ---------------------------------------------------------
+// ---- pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3) ----------------------------------------------
+// doubles per estimate / measurement, error (= vertex) dimension of a pose-pose type
+static int pg_pose_stride(int type) { return type == 1 ? 3 : type == 2 ? 12 : 8; }
+static int pg_pose_dim(int type) { return type == 1 ? 3 : type == 2 ? 6 : 7; }
+// Sim3 values (qx, qy, qz, qw, tx, ty, tz, s): a quaternion of norm 0 is no rotation, a scale <= 0 has no logarithm
+static void pg_validate_sim3(const char* who, const double* v, size_t n) {
+  for (size_t k = 0; k < n; ++k) {
+    const double* s = v + 8 * k;
+    for (int i = 0; i < 8; ++i)
+      if (!std::isfinite(s[i])) throw ArgFailure(std::string(who) + ": non-finite Sim3 value in entry " + std::to_string(k));
+    if (s[0] == 0.0 && s[1] == 0.0 && s[2] == 0.0 && s[3] == 0.0)
+      throw ArgFailure(std::string(who) + ": quaternion of norm 0 in entry " + std::to_string(k));
+    if (!(s[7] > 0.0)) throw ArgFailure(std::string(who) + ": scale <= 0 in entry " + std::to_string(k));
+  }
+}
+
 void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
   invalidate_graphs();
   require_structure();
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (type != 1 && type != 2) throw ArgFailure("pg_set_edges: type must be 1 (EdgeSE2) or 2 (EdgeSE3)");
+  if (type != 1 && type != 2 && type != 10) throw ArgFailure("pg_set_edges: type must be 1 (EdgeSE2), 2 (EdgeSE3) or 10 (EdgeSim3)");
   EdgeSet& es = *sets_[set];
-  const int d = type == 1 ? 3 : 6;
+  const int d = pg_pose_dim(type);
+  if (type == 10 && p_ != 7) throw ArgFailure("pg_set_edges: EdgeSim3 (10) needs a solver of pose dimension 7");
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d) throw ArgFailure("pg_set_edges: the set must be a binary pose-pose set of matching dimension");
   if (!vi || !vj || !meas || !info) throw ArgFailure("pg_set_edges: null array");
+  const size_t n = (size_t)es.n, ms = (size_t)pg_pose_stride(type);
+  if (type == 10) {
+    // one Sim3 set stands alone (no landmark, camera or prior set beside it), and a binding of another type takes its tables along
+    if (pg_.lm_set >= 0 || pg_.pr_set >= 0) throw ArgFailure("pg_set_edges: EdgeSim3 (10) cannot be bound beside a landmark or prior set");
+    pg_validate_sim3("pg_set_edges", meas, n);
+  }
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const size_t n = (size_t)es.n, ms = type == 1 ? 3 : 12;
-  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  // the committed pose table belongs to the committed type: a binding of another stride starts without estimates
+  const bool keep_table = pg_.poses.n > 0 && pg_.poses.stride == (int)ms;
+  if (keep_table) pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  if (!keep_table) {
+    pg_.poses.n = 0;
+    pg_.has_backup = false;
+  }
   pg_.set = set;
   pg_.type = type;
+  pg_.err_valid = pg_.jac_valid = false;
   pg_.h_vi.assign(vi, vi + n);
   pg_.h_vj.assign(vj, vj + n);
   pg_.vi.upload(vi, n, st_);
@@ -5441,11 +5474,21 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
+// VertexSim3Expmap::_fix_scale for the whole pose table (types_seven_dof_expmap.h:60-61, 78): the sigma entry of every step is
+// taken as zero, in pg_update and in the perturbations of the numeric Jacobian
+void BlockSolver::pg_set_sim3_fix_scale(bool fix_scale) {
+  if (fix_scale == pg_.fix_scale) return;
+  invalidate_graphs();
+  pg_.fix_scale = fix_scale;
+  pg_.jac_valid = false;   // (the errors do not depend on it)
+}
+
 void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx) {
   if (pg_.type == 0) throw StateFailure("pg_set_estimates: call pg_set_edges first");
   if (nv <= 0 || !poses || !hidx) throw ArgFailure("pg_set_estimates: bad arguments");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const int ps = pg_.type == 1 ? 3 : 12;
+  const int ps = pg_pose_stride(pg_.type);
+  if (pg_.type == 10) pg_validate_sim3("pg_set_estimates", poses, (size_t)nv);
   const bool same = pg_.poses.same(nv, ps, hidx);   // (same tables, new values: see ba_set_estimates)
   if (!same) {
     pg_validate(*sets_[pg_.set], pg_.h_vi.data(), pg_.h_vj.data(), pg_.h_vi.size(), hidx, nv);
@@ -5475,6 +5518,7 @@ void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_verte
   require_structure();
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type == 10) throw ArgFailure("pg_set_landmark_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
   if (type != 3 && type != 4) throw ArgFailure("pg_set_landmark_edges: type must be 3 (EdgeSE2PointXY) or 4 (EdgeSE3PointXYZ)");
   if (type != pg_.type + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
   if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
@@ -5488,6 +5532,7 @@ void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pos
   require_structure();
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_camera_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type == 10) throw ArgFailure("pg_set_landmark_camera_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
   if (type != 5 && type != 6) throw ArgFailure("pg_set_landmark_camera_edges: type must be 5 (EdgeSE3PointXYZDepth) or 6 (EdgeSE3PointXYZDisparity)");
   if (pg_.type != 2) throw ArgFailure("pg_set_landmark_camera_edges: the camera edges go with an EdgeSE3 pose set (2)");
   if (!kcam) throw ArgFailure("pg_set_landmark_camera_edges: null kcam (fx, fy, cx, cy)");
@@ -5539,6 +5584,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   require_structure();
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_prior_edges: call pg_set_edges first (the pose-pose set the prior set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type == 10) throw ArgFailure("pg_set_prior_edges: no prior set stands beside an EdgeSim3 pose set (10)");
   if (type != 7 && type != 8 && type != 9) throw ArgFailure("pg_set_prior_edges: type must be 7 (EdgeSE2Prior), 8 (EdgeSE2XYPrior) or 9 (EdgeSE3Prior)");
   if ((type == 9) != (pg_.type == 2)) throw ArgFailure("pg_set_prior_edges: EdgeSE2Prior (7) and EdgeSE2XYPrior (8) go with an EdgeSE2 pose set (1), EdgeSE3Prior (9) with EdgeSE3 (2)");
   if (offset && type != 9) throw ArgFailure("pg_set_prior_edges: an offset belongs to EdgeSE3Prior (type 9) only");
@@ -5626,9 +5672,21 @@ void BlockSolver::pg_linearize(bool jacobians) {
   if (pg_.type == 1)
     hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  else
+  else if (pg_.type == 2)
     hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
+  else if (es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
+    prof.begin(KernelProf::kPgSim3Error, st_);
+    hipLaunchKernelGGL(pg_sim3_error_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
+                       pg_.meas.p, es.own_err.p);
+    prof.end(KernelProf::kPgSim3Error, st_);
+    if (jacobians) {
+      prof.begin(KernelProf::kPgSim3Jacobian, st_);
+      hipLaunchKernelGGL(pg_sim3_jacobian_kernel, dim3(grid_for(14 * (size_t)es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p,
+                         pg_.poses.hidx.p, pg_.vi.p, pg_.vj.p, pg_.meas.p, pg_.fix_scale ? 1 : 0, es.own_J0.p, es.own_J1.p);
+      prof.end(KernelProf::kPgSim3Jacobian, st_);
+    }
+  }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0;
   const int jac = jacobians ? 1 : 0;
   if (lm_launch || pr_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
@@ -5689,9 +5747,12 @@ void BlockSolver::pg_update() {
   if (pg_.type == 1)
     hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
-  else
+  else if (pg_.type == 2)
     hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
+  else
+    hipLaunchKernelGGL(pg_sim3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, d_x.p, pg_.fix_scale ? 1 : 0);
   if (pg_.points.n > 0) {
     const size_t ns = (size_t)pg_.points.n * l_;
     hipLaunchKernelGGL(pg_points_update_kernel, dim3(grid_for(ns)), dim3(kThreads), 0, st_, ns, l_, pg_.points.val.p, pg_.points.hidx.p, d_x.p,

@@ -646,6 +646,9 @@ int g2ohip_pg_set_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, 
                         const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_edges(set, type, vi, vj, meas, info); });
 }
+int g2ohip_pg_set_sim3_fix_scale(g2ohip_solver* s, int fix_scale) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_sim3_fix_scale(fix_scale != 0); });
+}
 int g2ohip_pg_set_estimates(g2ohip_solver* s, int n_vertices, const double* poses, const int32_t* hidx) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_estimates(n_vertices, poses, hidx); });
 }

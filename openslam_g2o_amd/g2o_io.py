@@ -10,6 +10,8 @@ parameter_se3_offset}.cpp read()); RGB-D / stereo files `EDGE_PROJECT_DEPTH` / `
 (g2o/types/slam3d/{edge_se3_pointxyz_depth,edge_se3_pointxyz_disparity,parameter_camera}.cpp read()); unary pose priors
 `EDGE_PRIOR_SE2` / `EDGE_PRIOR_SE2_XY` (g2o/types/slam2d/{edge_se2_prior,edge_se2_xyprior}.cpp read()) and `EDGE_SE3_PRIOR`
 (g2o/types/slam3d/edge_se3_prior.cpp read(): vertex, PARAMS_SE3OFFSET id, measurement, upper triangle).
+Monocular 7-dof graphs: `VERTEX_SIM3:EXPMAP` / `EDGE_SIM3:EXPMAP` (g2o/types/sim3/types_seven_dof_expmap.cpp:59-136 read() /
+write(); read_g2o and write_g2o_sim3).
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -37,7 +39,13 @@ def read_g2o(path):
     A file with EDGE_PRIOR_SE2 (v x y th + 6), EDGE_PRIOR_SE2_XY (v x y + 3) or EDGE_SE3_PRIOR (v paramId x y z qx qy qz qw + 21)
     lines also gives pr_v (pose-table index of every prior), pr_kind (per prior: "se2" | "xy" | "se3"), pr_meas and pr_info
     (lists: the kinds differ in size), pr_param (PARAMS_SE3OFFSET id, -1 for the 2-D kinds) and `offsets`; a file without
-    them gives none of these keys."""
+    them gives none of these keys.
+    A file of VERTEX_SIM3:EXPMAP (id, 7 values of a minimal vector, fx fy cx cy) / EDGE_SIM3:EXPMAP (i j, 7 values, upper
+    triangle of the 7x7 information) gives kind = 'sim3', estimates and meas [..][8] = (qx, qy, qz, qw, tx, ty, tz, s) and
+    sim3_extras [n][4] (focal length, principal point: carried, not used).  Both reads invert: the file holds the minimal
+    vector of camera -> world, the estimate / measurement is Sim3(vector).inverse() (types_seven_dof_expmap.cpp:81, 110-111)."""
+    from . import sim3 as S3
+    sim3_extras = []
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
@@ -67,6 +75,16 @@ def read_g2o(path):
                 ej.append(int(t[2]))
                 meas.append([float(x) for x in t[3:10]])
                 info.append(_upper_to_full([float(x) for x in t[10:31]], 6))
+            elif tag == "VERTEX_SIM3:EXPMAP":
+                kind = kind or "sim3"
+                vid.append(int(t[1]))
+                vest.append(S3.sim3_inverse(S3.FP64, S3.sim3_exp(S3.FP64, [float(x) for x in t[2:9]])))
+                sim3_extras.append([float(x) for x in t[9:13]])
+            elif tag == "EDGE_SIM3:EXPMAP":
+                ei.append(int(t[1]))
+                ej.append(int(t[2]))
+                meas.append(S3.sim3_inverse(S3.FP64, S3.sim3_exp(S3.FP64, [float(x) for x in t[3:10]])))
+                info.append(_upper_to_full([float(x) for x in t[10:38]], 7))
             elif tag == "VERTEX_XY":
                 pid.append(int(t[1]))
                 pest.append([float(x) for x in t[2:4]])
@@ -124,6 +142,8 @@ def read_g2o(path):
     vj = np.asarray([lut[a] for a in ej], np.int32)
     out = dict(kind=kind, ids=vid, estimates=vest, vi=vi, vj=vj, meas=np.asarray(meas, np.float64),
                info=np.asarray(info, np.float64), fixed=[lut[f] for f in fixed if f in lut])
+    if sim3_extras:
+        out["sim3_extras"] = np.asarray(sim3_extras, np.float64)[order]
     if pid or lp or offsets or cameras:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
@@ -139,6 +159,31 @@ def read_g2o(path):
         out.update(pr_v=np.asarray([lut[a] for a in qv], np.int32), pr_kind=qkind, pr_meas=qmeas, pr_info=qinfo,
                    pr_param=np.asarray(qparam, np.int32), offsets=offsets)
     return out
+
+
+def write_g2o_sim3(path, estimates, vi, vj, meas, info, extras=None, fixed=(), ids=None):
+    """VERTEX_SIM3:EXPMAP / EDGE_SIM3:EXPMAP lines as VertexSim3Expmap::write / EdgeSim3::write state them
+    (types_seven_dof_expmap.cpp:85-101, 123-136): both writes invert -- the line holds log() of the INVERSE of the estimate /
+    measurement (camera -> world) -- the vertex line ends with focal length and principal point (extras [n][4], default
+    1 1 0 0: the constructor's values), the edge line with the upper triangle of the information.  %.17g: a read gives the
+    written doubles back."""
+    from . import sim3 as S3
+    estimates, meas = np.asarray(estimates, np.float64).reshape(-1, 8), np.asarray(meas, np.float64).reshape(-1, 8)
+    info = np.asarray(info, np.float64).reshape(-1, 7, 7)
+    n = len(estimates)
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    extras = np.tile([1.0, 1.0, 0.0, 0.0], (n, 1)) if extras is None else np.asarray(extras, np.float64).reshape(n, 4)
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    with open(path, "w") as f:
+        for k in range(n):
+            lv = S3.sim3_log(S3.FP64, S3.sim3_inverse(S3.FP64, estimates[k]))
+            f.write("VERTEX_SIM3:EXPMAP %d %s %s\n" % (ids[k], fmt(lv), fmt(extras[k])))
+        for k in fixed:
+            f.write("FIX %d\n" % ids[k])
+        for e in range(len(meas)):
+            v7 = S3.sim3_log(S3.FP64, S3.sim3_inverse(S3.FP64, meas[e]))
+            up = [info[e, i, j] for i in range(7) for j in range(i, 7)]
+            f.write("EDGE_SIM3:EXPMAP %d %d %s %s\n" % (ids[vi[e]], ids[vj[e]], fmt(v7), fmt(up)))
 
 
 def hessian_index(n_vertices, fixed):

@@ -343,17 +343,26 @@ class DevicePoseGraph:
 PRIOR_ERROR_DIM = {7: 3, 8: 2, 9: 6}   # EdgeSE2Prior, EdgeSE2XYPrior, EdgeSE3Prior (g2ohip_pg_set_prior_edges)
 
 
-def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0, priors=None):
+PG_POSE_DIM = {1: 3, 2: 6, 10: 7}       # EdgeSE2, EdgeSE3, EdgeSim3 (g2ohip_pg_set_edges)
+
+
+def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0, priors=None,
+                            fix_scale=False, options=None):
     """HipBlockSolver for a pose graph with estimates, errors and Jacobians on the device.
     edge_type 1: EdgeSE2 (estimates / measurements (x, y, theta), information [n][9]);
     edge_type 2: EdgeSE3 (isometries [12] = R column-major | t, information [n][36]).
+    edge_type 10: EdgeSim3 over VertexSim3Expmap (estimates / measurements (qx, qy, qz, qw, tx, ty, tz, s), information
+    [n][49]; BlockSolver_7_3); fix_scale: VertexSim3Expmap::_fix_scale of every vertex.  No priors beside this type.
     hidx[v] = hessian index of vertex v or -1 (fixed); BlockSolver_3_2 / BlockSolver_6_3 semantics, no Schur.
+    options: g2ohip_set_option pairs that have to be in place before buildStructure.
     priors: (type, vq, zq, omega_q, offset) -- unary priors on the poses vq, type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior
     (edge_type 1), 9 = EdgeSE3Prior with its ParameterSE3Offset or None (edge_type 2); solver.prior_set = their set id."""
     import numpy as np
     from . import capi
-    d = 3 if edge_type == 1 else 6
+    d = PG_POSE_DIM[edge_type]
     s = capi.HipBlockSolver(d, landmark_dim or (2 if edge_type == 1 else 3), device)
+    for name, value in (options or {}).items():
+        s.setOption(name, value)
     hidx = np.asarray(hidx, np.int32)
     k = s.addEdgeSet(d, hidx[np.asarray(vi)], hidx[np.asarray(vj)])
     if priors is not None:
@@ -361,7 +370,10 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
         kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[np.asarray(vq)], None)
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
+    if edge_type == 10:
+        s.pgSetSim3FixScale(fix_scale)
     s.pgSetEstimates(estimates, hidx)
+    s.pose_set = k
     if priors is not None:
         s.pgSetPriorEdges(kq, ptype, vq, zq, omega_q, offset)
         s.prior_set = kq

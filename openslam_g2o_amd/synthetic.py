@@ -594,3 +594,49 @@ def make_landmark_slam(kind, n_poses, n_landmarks, laps=3, sensor_range=4.0, win
             info_q[3:, 3:] = np.eye(3) / (0.5 * pr) ** 2              # (quaternion vector: half the angle)
         out.update(prior=priors, vq=vq, zq=zq, omega_q=np.tile(info_q.reshape(1, -1), (Q, 1)))
     return out
+
+
+def make_sim3_graph(n, loop_every, scale_drift, seed, fix_scale=False, noise=1.0):
+    """A closed monocular trajectory as a 7-dof pose graph (VertexSim3Expmap / EdgeSim3, g2o/types/sim3): n poses on two laps
+    of a circle, looking at its centre; the estimate of a pose is the world -> camera Sim3 (qx, qy, qz, qw, tx, ty, tz, s)
+    with s = 1.  Odometry edges (k, k + 1), the closing edge (n - 1, 0) and, every loop_every poses of the first lap, a loop
+    closure to the pose one lap later.  The measurement of (i, j) is exp(noise) Sj Si^-1 of the ground truth, so that
+    EdgeSim3::computeError = log(C Si Sj^-1) vanishes there without noise (noise = 0; the standard deviations 0.01 rotation,
+    0.02 translation, 0.01 log-scale are multiplied by it).  The initial estimate chains the odometry from pose 0 and
+    multiplies the scale by (1 + scale_drift) at every step -- the drift monocular odometry accumulates and a loop closure has to
+    take out again; with fix_scale (VertexSim3Expmap::_fix_scale for every vertex: the optimisation cannot move s) the drift
+    is left out and the scales stay 1.  Vertex 0 is fixed.  Deterministic from seed.
+    Returns est, est_true [n][8], hidx, num_free, vi, vj, meas [m][8], info [m][49], fix_scale."""
+    from . import sim3 as S3
+    F = S3.FP64
+    rng = CounterRng(seed)
+    lap = max(2, n // 2)
+    ang = 2.0 * np.pi * np.arange(n) / lap
+    radius = 0.25 * lap
+    wob = 0.05 * rng.normal(1, n)
+    true = np.zeros((n, 8))
+    for k in range(n):
+        c = np.array([radius * np.cos(ang[k]), radius * np.sin(ang[k]), 0.3 * np.sin(3 * ang[k]) + wob[k]])
+        z = -c / np.linalg.norm(c)                                   # optical axis towards the centre
+        x = np.cross([0.0, 0.0, 1.0], z)
+        x /= np.linalg.norm(x)
+        Rcw = np.stack([x, np.cross(z, x), z])                       # rows: camera axes in the world
+        q = S3.R_to_q(F, Rcw.tolist())
+        true[k] = q + list(-Rcw @ c) + [1.0]
+    vi = list(range(n - 1)) + [n - 1] + [k for k in range(0, n - lap, max(1, loop_every))]
+    vj = list(range(1, n)) + [0] + [k + lap for k in range(0, n - lap, max(1, loop_every))]
+    m = len(vi)
+    sd = noise * np.array([0.01] * 3 + [0.02] * 3 + [0.01])
+    nz = np.stack([rng.normal(10 + c, m) for c in range(7)], axis=1) * sd
+    meas = np.zeros((m, 8))
+    for e in range(m):
+        rel = S3.sim3_mul(F, true[vj[e]], S3.sim3_inverse(F, true[vi[e]]))
+        meas[e] = S3.to_f64(S3.sim3_mul(F, S3.sim3_exp(F, nz[e]), rel) if noise else rel)
+    info = np.tile(np.diag([1e4] * 3 + [2500.0] * 3 + [1e4]).reshape(49), (m, 1))
+    est = true.copy()
+    drift = [0.0] * 6 + [0.0 if fix_scale else float(np.log1p(scale_drift))]
+    for k in range(n - 1):                                           # Sj = C Si along the odometry
+        est[k + 1] = S3.to_f64(S3.sim3_mul(F, S3.sim3_exp(F, drift), S3.sim3_mul(F, meas[k], est[k])))
+    hidx = np.arange(n, dtype=np.int32) - 1
+    return dict(est=est, est_true=true, hidx=hidx, num_free=n - 1, vi=np.asarray(vi, np.int32), vj=np.asarray(vj, np.int32),
+                meas=meas, info=info, fix_scale=bool(fix_scale))
