@@ -475,9 +475,11 @@ int g2ohip_ba_discard_top(g2ohip_solver* s);
  * for this edge; the device evaluates what g2o then uses, the central differences of BaseBinaryEdge::linearizeOplus
  * (g2o/core/base_binary_edge.hpp:132-201, delta = 1e-9) through oplusImpl, and writes zeros for the block of a fixed vertex.
  * G2OHIP_ERR_ARG for a quaternion of norm 0, a scale <= 0 or a non-finite value in the measurements or estimates, for another
- * pose or error dimension, and for any landmark, camera or prior set beside a type-10 set (either order).  Not covered:
- * EdgeSim3ProjectXYZ, landmarks or priors beside a Sim3 set, sharded solves, the g2o plugin adapter (it keeps this edge on its
- * host path).
+ * pose or error dimension, and for any prior set or landmark set of types 3-6 beside a type-10 set (either order); the one
+ * landmark set that stands beside it is EdgeSim3ProjectXYZ (g2ohip_pg_set_sim3_project_edges below), and for a map of keyframes
+ * and points without Sim3 constraints the type-10 set may hold zero edges (its arrays may then be NULL).  Not covered: priors
+ * beside a Sim3 set, more than one landmark set per handle, sharded solves, the g2o plugin adapter (it keeps these edges on
+ * its host path).
  * Edge set `set` was added with error_dim 3 / 6 / 7 and hessian indices of its two
  * vertices; vi/vj index the estimate array (all vertices, fixed ones included), hidx[v] = hessianIndex or -1.
  * The calls mirror the g2ohip_ba_* ones (set_edges after g2ohip_build_structure).
@@ -538,6 +540,28 @@ int g2ohip_pg_set_landmark_edges(g2ohip_solver* s, int set, int type, const int3
  * push / pop / discard_top, robust kernels, g2ohip_clear_edge_sets -- acts on it unchanged. */
 int g2ohip_pg_set_landmark_camera_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
                                         const double* meas, const double* info, const double* offset, const double* kcam);
+/* Sim3 bundle adjustment, the other half of the reference's sim3 type group: type 11 = EdgeSim3ProjectXYZ
+ * (g2o/types/sim3/types_seven_dof_expmap.h:118-137, tag EDGE_PROJECT_SIM3_XYZ:EXPMAP; computeError :126-133), the reprojection of
+ * a VertexSBAPointXYZ through the similarity camera of a VertexSim3Expmap, bound to the SAME single landmark slot beside a
+ * type-10 (EdgeSim3) pose set only, on a handle of (pose, landmark) dimensions (7, 3) and a set of error_dim 2:
+ *   e = z - cam_map(project(S.map(X))), Sim3::map(X) = s (r X) + t (sim3.h:144-146), project = (x / z, y / z)
+ *   (slam3d/se3_ops.hpp:49-55), cam_map(v)[i] = v[i] focal_length[i] + principle_point[i] (:70-76) with the intrinsics of the
+ *   OBSERVING vertex: intrinsics [n_cams][4] = (fx, fy, cx, cy), one row per entry of the pose table of g2ohip_pg_set_estimates
+ *   (finite, fx and fy not zero; n_cams must equal that table's size whenever one is bound, checked here and again when
+ *   g2ohip_pg_set_estimates changes the table).  meas [n][2], info [n][2x2], landmarks (x, y, z).
+ * As in the whole landmark slot vertex 0 of the set is the POSE and vertex 1 the landmark -- the reference's edge has the point
+ * as vertex 0 and the pose as vertex 1: J0 is [n][2x7] (the reference's _jacobianOplusXj), J1 [n][2x3] (_jacobianOplusXi).
+ * The reference defines no Jacobian for this edge (linearizeOplus is commented out, :135); the device evaluates what g2o then
+ * uses, the central differences of BaseBinaryEdge::linearizeOplus (g2o/core/base_binary_edge.hpp:132-201, delta = 1e-9): the
+ * pose through oplusImpl (g2ohip_pg_set_sim3_fix_scale makes column 6 exactly zero), the point by plain addition
+ * (g2o/types/sba/types_sba.h:151-155); the block of a fixed vertex is written as zeros.  Like the reference there is no guard
+ * for a point on or behind the image plane.  Preconditions, validation (validate-then-commit) and error codes are those of
+ * g2ohip_pg_set_landmark_edges; that entry and g2ohip_pg_set_landmark_camera_edges keep rejecting type 11 and any set beside a
+ * type-10 pose set, and g2ohip_pg_set_edges rejects types 1 and 2 while a type-11 set is bound.  Everything after the binding
+ * -- g2ohip_pg_set_landmark_estimates, g2ohip_pg_linearize / update / push / pop / discard_top, robust kernels,
+ * g2ohip_clear_edge_sets -- acts on it unchanged; its kernels are timed in the pg_landmark_linearize slot. */
+int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                     const double* meas, const double* info, int n_cams, const double* intrinsics);
 /* ---- ... its unary pose priors: GPS fixes, an anchor on the first pose, surveyed checkpoints ------------------------
  * One UNARY edge set of the same handle beside the pose-pose set of g2ohip_pg_set_edges, in a slot of its own (independent of
  * the landmark slot: with or without a landmark set, do_schur 0 or 1; a later call replaces the binding):

@@ -61,6 +61,7 @@ EXPORTS = [
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
+    "g2ohip_pg_set_sim3_project_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -165,6 +166,7 @@ def load():
     L.g2ohip_pg_set_sim3_fix_scale.argtypes = [vp, C.c_int]
     L.g2ohip_pg_set_landmark_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_camera_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_sim3_project_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -770,6 +772,20 @@ class HipBlockSolver:
             raise ValueError("pgSetLandmarkCameraEdges: kcam is (fx, fy, cx, cy)")
         _check(self.L.g2ohip_pg_set_landmark_camera_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
                                                           None if off is None else _dp(off), _dp(kc)), "pgSetLandmarkCameraEdges")
+
+    def pgSetSim3ProjectEdges(self, set_id, pose_vertex, point_vertex, meas, info, intrinsics):
+        """EdgeSim3ProjectXYZ (type 11) beside an EdgeSim3 pose set (type 10, possibly with zero edges): meas [n][2], info
+        [n][2x2], intrinsics [n_poses][4] = (fx, fy, cx, cy) per entry of the table of pgSetEstimates.  Vertex 0 of the set is
+        the pose, vertex 1 the point (the reference's edge has them the other way round).  After pgSetEdges."""
+        pv, lv, meas, info = _i32(pose_vertex), _i32(point_vertex), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        if len(pv) != n or len(lv) != n or meas.size != n * 2 or info.size != n * 4:
+            raise ValueError("pgSetSim3ProjectEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        kc = _f64(intrinsics)
+        if kc.ndim != 2 or kc.shape[1] != 4:
+            raise ValueError("pgSetSim3ProjectEdges: intrinsics is [n_poses][4] = (fx, fy, cx, cy)")
+        _check(self.L.g2ohip_pg_set_sim3_project_edges(self.h, set_id, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
+               "pgSetSim3ProjectEdges")
 
     def pgSetPriorEdges(self, set_id, edge_type, pose_vertex, meas, info, offset=None):
         """Unary priors on poses: edge_type 7 = EdgeSE2Prior (meas [n][3]), 8 = EdgeSE2XYPrior ([n][2]) beside EdgeSE2,

@@ -98,6 +98,12 @@ class HipBlockSolver {
                                 const double* info, const double* offset, const double* kcam) {
     return ok(g2ohip_pg_set_landmark_camera_edges(h_, set, type, poseVertex, pointVertex, meas, info, offset, kcam), "pgSetLandmarkCameraEdges");
   }
+  // EdgeSim3ProjectXYZ observations (type 11) beside an EdgeSim3 pose set (type 10) of g2ohip_pg_set_edges (handle()): vertex 0 of
+  // the set is the pose, vertex 1 the point; intrinsics [nCams][4] = fx, fy, cx, cy per entry of the pose table
+  bool pgSetSim3ProjectEdges(int set, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas, const double* info,
+                             int nCams, const double* intrinsics) {
+    return ok(g2ohip_pg_set_sim3_project_edges(h_, set, poseVertex, pointVertex, meas, info, nCams, intrinsics), "pgSetSim3ProjectEdges");
+  }
   // unary pose priors (g2ohip_pg_set_prior_edges): type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior beside an EdgeSE2 pose set, 9 =
   // EdgeSE3Prior beside an EdgeSE3 one; `set` is a unary set (addEdgeSet with v1 == nullptr), offset isometry [12] or nullptr (type 9)
   bool pgSetPriorEdges(int set, int type, const int32_t* poseVertex, const double* meas, const double* info, const double* offset) {

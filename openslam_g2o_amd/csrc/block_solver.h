@@ -97,6 +97,8 @@ class BlockSolver {
                              const double* offset);
   void pg_set_landmark_camera_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                     const double* info, const double* offset, const double* kcam);
+  void pg_set_sim3_project_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
+                                 int n_cams, const double* intrinsics);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -353,7 +355,7 @@ class BlockSolver {
                              int np) const;
   void pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const;
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
-                              const double* info, const double* offset, const double* kcam);
+                              const double* info, const double* offset, const double* kcam, int n_cams = 0);
   // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
   // values, their backup (an estimate stack of depth one) and every vertex's index in the system (-1: fixed).
   // Validate, then commit: every committed (edge binding, table) pair has been validated against each other when the later of
@@ -427,7 +429,8 @@ class BlockSolver {
   // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
   // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one ParameterCamera
-  // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges).  Vertex 0 of an observation
+  // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges), 11 = EdgeSim3ProjectXYZ (beside type 10, landmarks (x, y, z),
+  // one (fx, fy, cx, cy) per entry of the pose table; bound by pg_set_sim3_project_edges).  Vertex 0 of an observation
   // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); points.hidx[v] is the landmark's index in
   // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
   // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
@@ -441,8 +444,8 @@ class BlockSolver {
     DevBuf<int> vi, vj;
     std::vector<int> h_vi, h_vj;   // host copies: index validation (pg_validate)
     DevBuf<double> meas;
-    EstimateTable poses;           // (x, y, theta), T[12] or -- type 10 = EdgeSim3 over VertexSim3Expmap, which stands alone: no
-                                   // landmark or prior set beside it -- (qx, qy, qz, qw, tx, ty, tz, s) per pose
+    EstimateTable poses;           // (x, y, theta), T[12] or -- type 10 = EdgeSim3 over VertexSim3Expmap: no prior set and no
+                                   // landmark set other than type 11 beside it -- (qx, qy, qz, qw, tx, ty, tz, s) per pose
     bool fix_scale = false;        // VertexSim3Expmap::_fix_scale of the whole table (pg_set_sim3_fix_scale)
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
@@ -453,6 +456,8 @@ class BlockSolver {
     EstimateTable points;          // (x, y) or (x, y, z) per landmark
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
     double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
+    DevBuf<double> cam_k;          // type 11: (fx, fy, cx, cy) of every entry of `poses` (VertexSim3Expmap::_focal_length,
+    int n_cams = 0;                // _principle_point), n_cams entries: == poses.n whenever both are bound
     // ONE unary set of pose priors `pr_set`, independent of the landmark slot: pr_type 7 = EdgeSE2Prior (measurement (x, y, theta)),
     // 8 = EdgeSE2XYPrior ((x, y)) beside type 1, 9 = EdgeSE3Prior (isometry [12], one ParameterSE3Offset pr_offset) beside type 2.
     // vq indexes `poses`.  Priors own no vertices: pg_linearize fills the set's own_J0 / own_err, nothing else knows of them.

@@ -2083,6 +2083,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_landmark.inc"
 #include "pg_prior.inc"
 #include "pg_sim3.inc"
+#include "pg_sim3_project.inc"
 #include "ba_stereo.inc"
 #undef PG_R
 
@@ -5441,12 +5442,16 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   const int d = pg_pose_dim(type);
   if (type == 10 && p_ != 7) throw ArgFailure("pg_set_edges: EdgeSim3 (10) needs a solver of pose dimension 7");
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d) throw ArgFailure("pg_set_edges: the set must be a binary pose-pose set of matching dimension");
-  if (!vi || !vj || !meas || !info) throw ArgFailure("pg_set_edges: null array");
   const size_t n = (size_t)es.n, ms = (size_t)pg_pose_stride(type);
+  // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays)
+  if ((n > 0 || type != 10) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
   if (type == 10) {
-    // one Sim3 set stands alone (no landmark, camera or prior set beside it), and a binding of another type takes its tables along
-    if (pg_.lm_set >= 0 || pg_.pr_set >= 0) throw ArgFailure("pg_set_edges: EdgeSim3 (10) cannot be bound beside a landmark or prior set");
+    // beside a Sim3 set stands an EdgeSim3ProjectXYZ landmark set (11) or nothing: no other landmark, camera or prior set
+    if ((pg_.lm_set >= 0 && pg_.lm_type != 11) || pg_.pr_set >= 0)
+      throw ArgFailure("pg_set_edges: EdgeSim3 (10) cannot be bound beside a prior set or a landmark set other than EdgeSim3ProjectXYZ (11)");
     pg_validate_sim3("pg_set_edges", meas, n);
+  } else if (pg_.lm_set >= 0 && pg_.lm_type == 11) {
+    throw ArgFailure("pg_set_edges: an EdgeSim3ProjectXYZ landmark set (11) is bound: it stands beside EdgeSim3 (10) only");
   }
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   // the committed pose table belongs to the committed type: a binding of another stride starts without estimates
@@ -5475,7 +5480,8 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
 }
 
 // VertexSim3Expmap::_fix_scale for the whole pose table (types_seven_dof_expmap.h:60-61, 78): the sigma entry of every step is
-// taken as zero, in pg_update and in the perturbations of the numeric Jacobian
+// taken as zero, in pg_update and in the perturbations of the numeric Jacobians -- those of an EdgeSim3ProjectXYZ set beside it
+// included: jac_valid covers both sets
 void BlockSolver::pg_set_sim3_fix_scale(bool fix_scale) {
   if (fix_scale == pg_.fix_scale) return;
   invalidate_graphs();
@@ -5492,6 +5498,9 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
   const bool same = pg_.poses.same(nv, ps, hidx);   // (same tables, new values: see ba_set_estimates)
   if (!same) {
     pg_validate(*sets_[pg_.set], pg_.h_vi.data(), pg_.h_vj.data(), pg_.h_vi.size(), hidx, nv);
+    if (pg_.lm_set >= 0 && pg_.lm_type == 11 && nv != pg_.n_cams)
+      throw ArgFailure("pg_set_estimates: " + std::to_string(nv) + " poses, but the EdgeSim3ProjectXYZ set was bound with intrinsics of " +
+                       std::to_string(pg_.n_cams) + " cameras");
     if (pg_.lm_set >= 0)
       pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
                             pg_.points.n);
@@ -5542,26 +5551,54 @@ void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pos
   pg_bind_landmark_edges("pg_set_landmark_camera_edges", set, type, pose_vertex, point_vertex, meas, info, offset, kcam);
 }
 
-// what both entries share: the set's dimensions, index validation, the uploads
+// EdgeSim3ProjectXYZ (11) beside an EdgeSim3 pose set (10): the reprojection of a VertexSBAPointXYZ through the similarity
+// camera of the observing VertexSim3Expmap, whose focal length and principal point are row pose_vertex[k] of `intrinsics`
+// [n_cams][4] = (fx, fy, cx, cy) -- one row per entry of the pose table (pg_sim3_project.inc)
+void BlockSolver::pg_set_sim3_project_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                            const double* info, int n_cams, const double* intrinsics) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_sim3_project_edges: call pg_set_edges first (the EdgeSim3 set the landmark set stands beside; it may be empty)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type != 10) throw ArgFailure("pg_set_sim3_project_edges: EdgeSim3ProjectXYZ (11) goes with an EdgeSim3 pose set (10)");
+  if (n_cams <= 0 || !intrinsics) throw ArgFailure("pg_set_sim3_project_edges: no intrinsics (fx, fy, cx, cy per pose)");
+  for (size_t i = 0; i < 4 * (size_t)n_cams; ++i)
+    if (!std::isfinite(intrinsics[i])) throw ArgFailure("pg_set_sim3_project_edges: non-finite intrinsics of camera " + std::to_string(i / 4));
+  for (int c = 0; c < n_cams; ++c)
+    if (intrinsics[4 * (size_t)c] == 0.0 || intrinsics[4 * (size_t)c + 1] == 0.0)
+      throw ArgFailure("pg_set_sim3_project_edges: fx and fy must not be zero (camera " + std::to_string(c) + ")");
+  if (pg_.poses.n > 0 && n_cams != pg_.poses.n)
+    throw ArgFailure("pg_set_sim3_project_edges: intrinsics of " + std::to_string(n_cams) + " cameras, but the pose table holds " +
+                     std::to_string(pg_.poses.n) + " poses");
+  pg_bind_landmark_edges("pg_set_sim3_project_edges", set, 11, pose_vertex, point_vertex, meas, info, nullptr, intrinsics, n_cams);
+}
+
+// what the three entries share: the set's dimensions, index validation, the uploads (type 11: kcam is the table [n_cams][4])
 void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
-                                         const double* meas, const double* info, const double* offset, const double* kcam) {
+                                         const double* meas, const double* info, const double* offset, const double* kcam, int n_cams) {
   const std::string w(who);
   if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
   if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
   EdgeSet& es = *sets_[set];
-  const int d = type == 3 ? 2 : 3, dp = type == 3 ? 3 : 6;
-  if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != d || p_ != dp || l_ != d)
-    throw ArgFailure(w + ": the set must be a binary pose-landmark set with (error, pose, landmark) dimensions (2, 3, 2) or (3, 6, 3)");
+  const int d = (type == 3 || type == 11) ? 2 : 3, dp = type == 3 ? 3 : type == 11 ? 7 : 6, dl = type == 3 ? 2 : 3;
+  if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != dl || p_ != dp || l_ != dl)
+    throw ArgFailure(w + ": the set must be a binary pose-landmark set with (error, pose, landmark) dimensions " +
+                     (type == 11 ? "(2, 7, 3)" : "(2, 3, 2) or (3, 6, 3)"));
   if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure(w + ": null array");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
+  if (type == 11)   // (the kernels index the intrinsics by pose_vertex: in range also while no pose table is bound)
+    for (size_t k = 0; k < n; ++k)
+      if (pose_vertex[k] >= n_cams) throw ArgFailure(w + ": pose index of landmark edge " + std::to_string(k) + " outside the intrinsics table");
   pg_.lm_set = set;
   pg_.lm_type = type;
   pg_.h_vp.assign(pose_vertex, pose_vertex + n);
   pg_.h_vl.assign(point_vertex, point_vertex + n);
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
-  for (int i = 0; i < 4; ++i) pg_.kcam[i] = kcam ? kcam[i] : (i < 2 ? 1.0 : 0.0);
+  for (int i = 0; i < 4; ++i) pg_.kcam[i] = (kcam && type != 11) ? kcam[i] : (i < 2 ? 1.0 : 0.0);
+  pg_.n_cams = type == 11 ? n_cams : 0;
+  if (type == 11) pg_.cam_k.upload(kcam, 4 * (size_t)n_cams, st_);
   pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
   chi2_valid_ = false;
   pg_.vp.upload(pose_vertex, n, st_);
@@ -5569,7 +5606,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   pg_.lm_meas.upload(meas, n * d, st_);
   es.own_omega.upload(info, n * d * d, st_);
   es.own_J0.alloc(n * d * dp);
-  es.own_J1.alloc(n * d * d);
+  es.own_J1.alloc(n * d * dl);
   es.own_err.alloc(n * d);
   es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
   es.has_data = false;
@@ -5690,7 +5727,14 @@ void BlockSolver::pg_linearize(bool jacobians) {
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0;
   const int jac = jacobians ? 1 : 0;
   if (lm_launch || pr_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
-  if (lm_launch) {
+  if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
+    hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
+                       pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
+    if (jacobians)
+      hipLaunchKernelGGL(pg_sim3_project_jacobian_kernel, dim3(grid_for(10 * (size_t)el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p,
+                         pg_.points.val.p, pg_.poses.hidx.p, pg_.points.hidx.p, pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p,
+                         pg_.fix_scale ? 1 : 0, el->own_J0.p, el->own_J1.p);
+  } else if (lm_launch) {
     const dim3 grid(grid_for(el->n)), block(kThreads);
     PgIso off;
     for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];

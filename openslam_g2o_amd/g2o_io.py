@@ -11,7 +11,8 @@ parameter_se3_offset}.cpp read()); RGB-D / stereo files `EDGE_PROJECT_DEPTH` / `
 `EDGE_PRIOR_SE2` / `EDGE_PRIOR_SE2_XY` (g2o/types/slam2d/{edge_se2_prior,edge_se2_xyprior}.cpp read()) and `EDGE_SE3_PRIOR`
 (g2o/types/slam3d/edge_se3_prior.cpp read(): vertex, PARAMS_SE3OFFSET id, measurement, upper triangle).
 Monocular 7-dof graphs: `VERTEX_SIM3:EXPMAP` / `EDGE_SIM3:EXPMAP` (g2o/types/sim3/types_seven_dof_expmap.cpp:59-136 read() /
-write(); read_g2o and write_g2o_sim3).
+write(); read_g2o and write_g2o_sim3), with map points `VERTEX_XYZ` (g2o/types/sba/types_sba.cpp, VertexSBAPointXYZ) observed
+through `EDGE_PROJECT_SIM3_XYZ:EXPMAP` (types_seven_dof_expmap.cpp:145-172: id_point id_pose u v i00 i01 i11).
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -42,10 +43,15 @@ def read_g2o(path):
     them gives none of these keys.
     A file of VERTEX_SIM3:EXPMAP (id, 7 values of a minimal vector, fx fy cx cy) / EDGE_SIM3:EXPMAP (i j, 7 values, upper
     triangle of the 7x7 information) gives kind = 'sim3', estimates and meas [..][8] = (qx, qy, qz, qw, tx, ty, tz, s) and
-    sim3_extras [n][4] (focal length, principal point: carried, not used).  Both reads invert: the file holds the minimal
-    vector of camera -> world, the estimate / measurement is Sim3(vector).inverse() (types_seven_dof_expmap.cpp:81, 110-111)."""
+    sim3_extras [n][4] (fx, fy, cx, cy of every vertex: the intrinsics table of EdgeSim3ProjectXYZ).  Both reads invert: the
+    file holds the minimal vector of camera -> world, the estimate / measurement is Sim3(vector).inverse()
+    (types_seven_dof_expmap.cpp:81, 110-111).  A sim3 file with VERTEX_XYZ (id x y z) or EDGE_PROJECT_SIM3_XYZ:EXPMAP (id_point
+    id_pose u v + upper triangle of the 2x2 information) lines also gives sim3_point_ids, sim3_points [L][3] (sorted by id),
+    sim3_vp / sim3_vl (pose-table and point-table index of every observation), sim3_zl [m][2], sim3_omega_l [m][4] and
+    sim3_fixed_points; a file without them gives none of these keys (sim3_ba_problem turns them into a problem dict)."""
     from . import sim3 as S3
     sim3_extras = []
+    spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
@@ -85,6 +91,15 @@ def read_g2o(path):
                 ej.append(int(t[2]))
                 meas.append(S3.sim3_inverse(S3.FP64, S3.sim3_exp(S3.FP64, [float(x) for x in t[3:10]])))
                 info.append(_upper_to_full([float(x) for x in t[10:38]], 7))
+            elif tag == "VERTEX_XYZ":
+                spid.append(int(t[1]))
+                spest.append([float(x) for x in t[2:5]])
+            elif tag == "EDGE_PROJECT_SIM3_XYZ:EXPMAP":
+                sp_pt.append(int(t[1]))
+                sp_pose.append(int(t[2]))
+                sp_meas.append([float(x) for x in t[3:5]])
+                i00, i01, i11 = (float(x) for x in t[5:8])
+                sp_info.append([i00, i01, i01, i11])
             elif tag == "VERTEX_XY":
                 pid.append(int(t[1]))
                 pest.append([float(x) for x in t[2:4]])
@@ -144,6 +159,15 @@ def read_g2o(path):
                info=np.asarray(info, np.float64), fixed=[lut[f] for f in fixed if f in lut])
     if sim3_extras:
         out["sim3_extras"] = np.asarray(sim3_extras, np.float64)[order]
+    if kind == "sim3" and (spid or sp_pt):
+        spid = np.asarray(spid, np.int64)
+        so = np.argsort(spid, kind="stable")
+        spid = spid[so]
+        splut = {int(v): k for k, v in enumerate(spid)}
+        out.update(sim3_point_ids=spid, sim3_points=np.asarray(spest, np.float64).reshape(-1, 3)[so],
+                   sim3_vp=np.asarray([lut[a] for a in sp_pose], np.int32), sim3_vl=np.asarray([splut[a] for a in sp_pt], np.int32),
+                   sim3_zl=np.asarray(sp_meas, np.float64).reshape(-1, 2), sim3_omega_l=np.asarray(sp_info, np.float64).reshape(-1, 4),
+                   sim3_fixed_points=[splut[f] for f in fixed if f in splut])
     if pid or lp or offsets or cameras:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
@@ -161,12 +185,14 @@ def read_g2o(path):
     return out
 
 
-def write_g2o_sim3(path, estimates, vi, vj, meas, info, extras=None, fixed=(), ids=None):
+def write_g2o_sim3(path, estimates, vi, vj, meas, info, extras=None, fixed=(), ids=None, points=None, vp=None, vl=None, zl=None,
+                   omega_l=None, fixed_points=(), point_ids=None):
     """VERTEX_SIM3:EXPMAP / EDGE_SIM3:EXPMAP lines as VertexSim3Expmap::write / EdgeSim3::write state them
     (types_seven_dof_expmap.cpp:85-101, 123-136): both writes invert -- the line holds log() of the INVERSE of the estimate /
     measurement (camera -> world) -- the vertex line ends with focal length and principal point (extras [n][4], default
     1 1 0 0: the constructor's values), the edge line with the upper triangle of the information.  %.17g: a read gives the
-    written doubles back."""
+    written doubles back.  points [L][3] (+ vp, vl, zl [m][2], omega_l [m][4]): VERTEX_XYZ lines (ids point_ids, default n ..) and
+    EDGE_PROJECT_SIM3_XYZ:EXPMAP lines "id_point id_pose u v i00 i01 i11" (EdgeSim3ProjectXYZ::write, :161-172)."""
     from . import sim3 as S3
     estimates, meas = np.asarray(estimates, np.float64).reshape(-1, 8), np.asarray(meas, np.float64).reshape(-1, 8)
     info = np.asarray(info, np.float64).reshape(-1, 7, 7)
@@ -178,12 +204,44 @@ def write_g2o_sim3(path, estimates, vi, vj, meas, info, extras=None, fixed=(), i
         for k in range(n):
             lv = S3.sim3_log(S3.FP64, S3.sim3_inverse(S3.FP64, estimates[k]))
             f.write("VERTEX_SIM3:EXPMAP %d %s %s\n" % (ids[k], fmt(lv), fmt(extras[k])))
+        if points is not None:
+            points = np.asarray(points, np.float64).reshape(-1, 3)
+            point_ids = n + np.arange(len(points)) if point_ids is None else np.asarray(point_ids)
+            for j in range(len(points)):
+                f.write("VERTEX_XYZ %d %s\n" % (point_ids[j], fmt(points[j])))
+            for j in fixed_points:
+                f.write("FIX %d\n" % point_ids[j])
         for k in fixed:
             f.write("FIX %d\n" % ids[k])
         for e in range(len(meas)):
             v7 = S3.sim3_log(S3.FP64, S3.sim3_inverse(S3.FP64, meas[e]))
             up = [info[e, i, j] for i in range(7) for j in range(i, 7)]
             f.write("EDGE_SIM3:EXPMAP %d %d %s %s\n" % (ids[vi[e]], ids[vj[e]], fmt(v7), fmt(up)))
+        if points is not None and vp is not None:
+            zl, omega_l = np.asarray(zl, np.float64).reshape(-1, 2), np.asarray(omega_l, np.float64).reshape(-1, 4)
+            for e in range(len(zl)):
+                f.write("EDGE_PROJECT_SIM3_XYZ:EXPMAP %d %d %s %s\n" % (point_ids[vl[e]], ids[vp[e]], fmt(zl[e]),
+                                                                        fmt((omega_l[e][0], omega_l[e][1], omega_l[e][3]))))
+
+
+def sim3_ba_problem(rd, fixed_poses=None, fixed_points=None):
+    """read_g2o result of a sim3 file with points -> the problem dict of lm.setup_device_sim3_ba (the layout of
+    synthetic.make_sim3_ba): free poses by vertex id, then free points by vertex id (sparse_optimizer.cpp:174-187); fixed
+    vertices from the file's FIX lines unless given."""
+    if rd.get("kind") != "sim3" or "sim3_points" not in rd:
+        raise ValueError("sim3_ba_problem: not a VERTEX_SIM3:EXPMAP file with VERTEX_XYZ points")
+    n, L = len(rd["estimates"]), len(rd["sim3_points"])
+    hidx, nP = hessian_index(n, rd["fixed"] if fixed_poses is None else fixed_poses)
+    fp = set(rd["sim3_fixed_points"] if fixed_points is None else fixed_points)
+    pt_hidx = np.full(L, -1, np.int32)
+    k = nP
+    for j in range(L):
+        if j not in fp:
+            pt_hidx[j] = k
+            k += 1
+    return dict(est=rd["estimates"], hidx=hidx, num_free=nP, nP=nP, nL=k - nP, vi=rd["vi"], vj=rd["vj"], meas=rd["meas"],
+                info=rd["info"].reshape(-1, 49), points=rd["sim3_points"], pt_hidx=pt_hidx, vp=rd["sim3_vp"], vl=rd["sim3_vl"],
+                zl=rd["sim3_zl"], omega_l=rd["sim3_omega_l"], intrinsics=rd["sim3_extras"], fix_scale=False)
 
 
 def hessian_index(n_vertices, fixed):

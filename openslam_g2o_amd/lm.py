@@ -310,8 +310,8 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
 
 
 class DevicePoseGraph:
-    """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3, and the
-    landmark observations bound beside them: setup_device_landmark_slam)."""
+    """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3, and the
+    landmark observations bound beside them: setup_device_landmark_slam, setup_device_sim3_ba)."""
 
     device_resident = True
 
@@ -421,4 +421,31 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     if huber_delta > 0:
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
     s.landmark_sets = (k0, k1)
+    return s, DevicePoseGraph(s)
+
+
+def setup_device_sim3_ba(prob, huber_delta=0.0, schur=True, device=0, options=None):
+    """HipBlockSolver for an openslam_g2o_amd.synthetic.make_sim3_ba (or g2o_io.sim3_ba_problem) graph: Sim3 keyframes
+    (VertexSim3Expmap, EdgeSim3 between them -- possibly none) observing map points through EdgeSim3ProjectXYZ with per-camera
+    intrinsics; pose and point estimates, errors and the numeric Jacobians on the device; BlockSolver_7_3 semantics, points
+    marginalised (schur=True).  huber_delta > 0: Huber kernel on the observation set.  Returns (solver, DevicePoseGraph);
+    solver.landmark_sets = (EdgeSim3 set id, observation set id), solver.pose_set = the former."""
+    import numpy as np
+    from . import capi
+    s = capi.HipBlockSolver(7, 3, device)
+    for name, value in (options or {}).items():
+        s.setOption(name, value)
+    hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
+    k0 = s.addEdgeSet(7, hidx[prob["vi"]], hidx[prob["vj"]])
+    k1 = s.addEdgeSet(2, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    s.buildStructure(prob["nP"], prob["nL"], schur)
+    s.pgSetEdges(k0, 10, prob["vi"], prob["vj"], prob["meas"], prob["info"])
+    s.pgSetSim3FixScale(prob.get("fix_scale", False))
+    s.pgSetEstimates(prob["est"], hidx)
+    s.pgSetSim3ProjectEdges(k1, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob["intrinsics"])
+    s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
+    if huber_delta > 0:
+        s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    s.landmark_sets = (k0, k1)
+    s.pose_set = k0
     return s, DevicePoseGraph(s)

@@ -3,6 +3,7 @@
   Sim3(Vector7d) (exp), log(), inverse(), operator*      g2o/types/sim3/sim3.h:70-142, 148-230, 233-236, 266-272
   VertexSim3Expmap::oplusImpl                            g2o/types/sim3/types_seven_dof_expmap.h:56-65
   EdgeSim3::computeError                                 g2o/types/sim3/types_seven_dof_expmap.h:94-102
+  EdgeSim3ProjectXYZ::computeError, Sim3::map, cam_map   g2o/types/sim3/types_seven_dof_expmap.h:126-133, :70-76, sim3.h:144-146
   BaseBinaryEdge::linearizeOplus (numeric branch)        g2o/core/base_binary_edge.hpp:132-201 (delta = 1e-9, central)
   Eigen: Quaternion(Matrix3), toRotationMatrix, quaternion product, quaternion * vector, 3x3 partial-pivot LU solve
 
@@ -11,8 +12,8 @@ ONE body of formulas, written operation for operation in the reference's order a
 cos, exp, log, acos, sqrt.  Constants the reference writes as fp64 literals (eps = 0.00001, delta = 1e-9, 1./6.) enter every
 arithmetic as those fp64 values.  Every data-dependent choice -- the exp branch, the log branch, the case of the rotation ->
 quaternion conversion, the pivot rows of the LU -- is appended to `trace` (when given), so that a test can assert that two
-arithmetics took the same path.  The device kernels (csrc/pg_sim3.inc) state the same operations in HIP and share no code with
-this file.
+arithmetics took the same path.  The device kernels (csrc/pg_sim3.inc, csrc/pg_sim3_project.inc) state the same operations in
+HIP and share no code with this file.
 
 Layouts as in the C ABI: a Sim3 is 8 doubles (qx, qy, qz, qw, tx, ty, tz, s); a minimal vector is (omega[3], upsilon[3],
 sigma); Jacobian blocks are 7x7 column-major."""
@@ -277,6 +278,69 @@ def sim3_jacobians(F, si, sj, z, fixed=(False, False), fix_scale=False, trace=No
                     J[r][c] = scalar * (e1[r] - e2[r])
         out.append(J)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ EdgeSim3ProjectXYZ
+def sim3_map(F, S, X):
+    """Sim3::map (sim3.h:144-146): s * (r * X) + t."""
+    S, X = _vec(F, S), _vec(F, X)
+    rX = q_rot(S[0:4], X)
+    return [S[7] * rX[i] + S[4 + i] for i in range(3)]
+
+
+def project_error(F, S, X, kc, z):
+    """EdgeSim3ProjectXYZ::computeError (types_seven_dof_expmap.h:126-133): z - cam_map(project(S.map(X))), project = (x / z,
+    y / z), cam_map(v)[i] = v[i] * focal_length[i] + principle_point[i]; kc = (fx, fy, cx, cy) of the observing vertex."""
+    m = sim3_map(F, S, X)
+    kc, z = _vec(F, kc), _vec(F, z)
+    u, v = m[0] / m[2], m[1] / m[2]
+    return [z[0] - (u * kc[0] + kc[2]), z[1] - (v * kc[1] + kc[3])]
+
+
+def project_jacobians(F, S, X, kc, z, fixed=(False, False), fix_scale=False, trace=None):
+    """The numeric branch of BaseBinaryEdge::linearizeOplus for EdgeSim3ProjectXYZ (which defines no Jacobian): the pose
+    perturbed through oplusImpl, the point by plain addition (VertexSBAPointXYZ::oplusImpl).  Returns (Jpose 2x7, Jpoint 2x3) as
+    row lists J[row][col] -- the pose first, as in the landmark slot of the C ABI (the reference's edge has the point as vertex 0);
+    fixed = (pose fixed, point fixed): the block of a fixed vertex is zero."""
+    delta = F.num(DELTA64)
+    scalar = F.num(1.0) / (F.num(2.0) * delta)
+    zero = F.num(0.0)
+    X = _vec(F, X)
+    Jp = [[zero] * 7 for _ in range(2)]
+    Jx = [[zero] * 3 for _ in range(2)]
+    if not fixed[0]:
+        for c in range(7):
+            add = [zero] * 7
+            add[c] = delta
+            e1 = project_error(F, sim3_oplus(F, S, add, fix_scale, trace), X, kc, z)
+            add[c] = -delta
+            e2 = project_error(F, sim3_oplus(F, S, add, fix_scale, trace), X, kc, z)
+            for r in range(2):
+                Jp[r][c] = (e1[r] - e2[r]) * scalar
+    if not fixed[1]:
+        for c in range(3):
+            e1 = project_error(F, S, [X[i] + (delta if i == c else zero) for i in range(3)], kc, z)
+            e2 = project_error(F, S, [X[i] + (-delta if i == c else zero) for i in range(3)], kc, z)
+            for r in range(2):
+                Jx[r][c] = (e1[r] - e2[r]) * scalar
+    return Jp, Jx
+
+
+def project_edges(F, poses, points, vp, vl, meas, intrinsics, pose_hidx=None, pt_hidx=None, fix_scale=False, jac=True, trace=None):
+    """err [n][2] and (jac) J0 [n][14] (pose, 2x7), J1 [n][6] (point, 2x3) column-major of a whole EdgeSim3ProjectXYZ list, rounded
+    to fp64; intrinsics [n_poses][4] = (fx, fy, cx, cy) indexed by vp; hidx < 0 = fixed vertex."""
+    n = len(vp)
+    err = np.zeros((n, 2))
+    J0, J1 = np.zeros((n, 14)), np.zeros((n, 6))
+    for k in range(n):
+        a, b = int(vp[k]), int(vl[k])
+        err[k] = to_f64(project_error(F, poses[a], points[b], intrinsics[a], meas[k]))
+        if jac:
+            fixed = (pose_hidx is not None and pose_hidx[a] < 0, pt_hidx is not None and pt_hidx[b] < 0)
+            Jp, Jx = project_jacobians(F, poses[a], points[b], intrinsics[a], meas[k], fixed, fix_scale, trace)
+            J0[k] = to_f64([Jp[r][c] for c in range(7) for r in range(2)])
+            J1[k] = to_f64([Jx[r][c] for c in range(3) for r in range(2)])
+    return (J0, J1, err) if jac else err
 
 
 # ------------------------------------------------------------------------------------------------ whole edge lists

@@ -640,3 +640,52 @@ def make_sim3_graph(n, loop_every, scale_drift, seed, fix_scale=False, noise=1.0
     hidx = np.arange(n, dtype=np.int32) - 1
     return dict(est=est, est_true=true, hidx=hidx, num_free=n - 1, vi=np.asarray(vi, np.int32), vj=np.asarray(vj, np.int32),
                 meas=meas, info=info, fix_scale=bool(fix_scale))
+
+
+def make_sim3_ba(n_cams, n_points, obs_per_point, seed, sim3_edges=True, fix_scale=False, pixel_noise=0.5, scale_drift=0.01):
+    """Monocular loop closing with map points (BlockSolver_7_3): the cameras of make_sim3_graph(n_cams, ...) -- a drifting
+    closed trajectory of VertexSim3Expmap, initial estimates chained along the noisy odometry -- observing VertexSBAPointXYZ
+    points through EdgeSim3ProjectXYZ.  Every camera has intrinsics of its own (fx != fy, non-zero cx, cy, all different between
+    cameras: VertexSim3Expmap::_focal_length / _principle_point).  The points lie in a ball around the centre the cameras look
+    at, 0.2 of the trajectory's radius wide, so that every point is in front of every camera with a depth >= 1 in camera units
+    (checked for the true and for the initial poses; n_cams >= 12); point j is observed by obs_per_point cameras spread over the
+    trajectory, measurement = its projection through the TRUE camera + pixel_noise * N(0, 1), information = identity.  The
+    initial points are the true ones + 0.02 * N(0, 1).  The first two cameras are fixed (the gauge of a similarity
+    reconstruction).  sim3_edges=False leaves the EdgeSim3 set empty (keyframes and points, no constraints between keyframes);
+    the initial poses are the same.  Deterministic from seed.
+    Returns the keys of make_sim3_graph (hidx / num_free for two fixed cameras) plus nP, nL, points, points_true [L][3], pt_hidx,
+    vp, vl, zl [m][2], omega_l [m][4], intrinsics [n_cams][4] = (fx, fy, cx, cy)."""
+    from . import sim3 as S3
+    F = S3.FP64
+    if obs_per_point < 1 or obs_per_point > n_cams:
+        raise ValueError("make_sim3_ba: 1 <= obs_per_point <= n_cams")
+    g = make_sim3_graph(n_cams, max(1, n_cams // 4), scale_drift, seed, fix_scale)
+    rng = CounterRng(seed + 1)
+    radius = 0.25 * max(2, n_cams // 2)
+    d = np.stack([rng.normal(40 + c, n_points) for c in range(3)], axis=1)
+    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
+    pts_true = d * (0.2 * radius * rng.uniform(43, n_points) ** (1.0 / 3.0))[:, None]
+    pts = pts_true + 0.02 * np.stack([rng.normal(44 + c, n_points) for c in range(3)], axis=1)
+    k = np.arange(n_cams)
+    intr = np.stack([480.0 + 7.0 * k, 510.0 + 5.0 * k, 320.0 + 3.0 * k, 240.0 - 2.0 * k], axis=1)
+    stride = max(1, n_cams // obs_per_point)
+    start = np.minimum((rng.uniform(47, n_points) * n_cams).astype(np.int64), n_cams - 1)
+    vp = ((start[:, None] + stride * np.arange(obs_per_point)[None, :]) % n_cams).reshape(-1).astype(np.int32)
+    vl = np.repeat(np.arange(n_points, dtype=np.int32), obs_per_point)
+    m = len(vp)
+    zero2 = np.zeros((m, 2))
+    zl = -S3.project_edges(F, g["est_true"], pts_true, vp, vl, zero2, intr, jac=False)        # e = z - proj: z = 0 gives -proj
+    zl = zl + pixel_noise * np.stack([rng.normal(48 + c, m) for c in range(2)], axis=1)
+    for poses, X in ((g["est_true"], pts_true), (g["est"], pts)):
+        depth = np.array([S3.sim3_map(F, poses[vp[e]], X[vl[e]])[2] for e in range(m)])
+        if not (depth >= 1.0).all():
+            raise ValueError("make_sim3_ba: an observed depth below 1 camera unit (%g): use n_cams >= 12" % depth.min())
+    hidx = np.maximum(np.arange(n_cams, dtype=np.int32) - 2, -1)
+    nP = n_cams - 2
+    out = dict(g)
+    if not sim3_edges:
+        out.update(vi=np.zeros(0, np.int32), vj=np.zeros(0, np.int32), meas=np.zeros((0, 8)), info=np.zeros((0, 49)))
+    out.update(hidx=hidx, num_free=nP, nP=nP, nL=n_points, points=pts, points_true=pts_true,
+               pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
+               omega_l=np.tile(np.eye(2).reshape(1, 4), (m, 1)), intrinsics=intr)
+    return out
