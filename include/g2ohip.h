@@ -562,6 +562,39 @@ int g2ohip_pg_set_landmark_camera_edges(g2ohip_solver* s, int set, int type, con
  * g2ohip_clear_edge_sets -- acts on it unchanged; its kernels are timed in the pg_landmark_linearize slot. */
 int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex,
                                      const double* meas, const double* info, int n_cams, const double* intrinsics);
+/* SBA-format bundle adjustment, the reference's own format in g2o/types/sba/types_sba.{h,cpp} (tags VERTEX_CAM, VERTEX_XYZ,
+ * EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC): pose type 12 of g2ohip_pg_set_edges = the VertexCam table, on a handle of (pose,
+ * landmark) dimensions (6, 3).  A row of g2ohip_pg_set_estimates is then 7 doubles (tx, ty, tz, qx, qy, qz, qw), camera-to-world,
+ * the order of SE3Quat::toVector (g2o/types/slam3d/se3quat.h:138-148) and of VertexCam::write (types_sba.cpp:114-131); a
+ * non-finite value or a quaternion of norm 0 is G2OHIP_ERR_ARG, otherwise the row is stored as given.  The type-12 pose-pose set
+ * is the anchor the landmark slot needs and holds ZERO edges (added with error_dim 6 and n = 0; its arrays may be NULL): n > 0
+ * is G2OHIP_ERR_ARG -- EdgeSBACam and EdgeSBAScale have no analytic Jacobian in the reference and are not on the device yet.
+ * g2ohip_pg_update applies SBACam::update (g2o/types/sba/sbacam.h:101-117): t += x[0:3], qr = (x[3:6], sqrt(1 - |x[3:6]|^2)),
+ * q <- q qr, then q / |q|; no sign flip.  A step with |x[3:6]| > 1 gives NaN, as in the reference.
+ * Beside it, in the single landmark slot, type 13 = EdgeProjectP2MC (types_sba.h:161-196; error_dim 2, meas [n][2], info
+ * [n][2x2]) or type 14 = EdgeProjectP2SC (types_sba.h:200-252; error_dim 3, meas [n][3] = (u, v, u_right), info [n][3x3]) over
+ * landmarks (x, y, z).  With R = toRotationMatrix(q), w2n = [R' | -R' t] (sbacam.h:120-130), pc = w2n (X, 1) = (px, py, pz):
+ *   mono   (types_sba.h:170-192)  e = ((fx px + cx pz) / pz, (fy py + cy pz) / pz) - z
+ *   stereo (types_sba.h:209-247)  the same two rows and (fx (px - baseline) + cx pz) / pz - z[2]
+ * intrinsics [n_cams][5] = (fx, fy, cx, cy, baseline), one row per entry of the pose table (finite, fx and fy not zero; n_cams
+ * must equal that table's size whenever one is bound, checked here and again when g2ohip_pg_set_estimates changes the table).
+ * The Jacobians are the reference's analytic ones (types_sba.cpp:249-328 stereo, :334-403 mono; dRdx/y/z of sbacam.h:162-181).
+ * As in the whole landmark slot vertex 0 of the set is the CAMERA and vertex 1 the point -- the reference's edges have the point
+ * as vertex 0 and the camera as vertex 1: J0 is [n][d x 6] (the reference's _jacobianOplusXj; columns t, then the quaternion's
+ * x, y, z), J1 [n][d x 3] (_jacobianOplusXi), column-major; blocks of fixed vertices are written like the others.  There is no
+ * guard for a point on or behind the image plane (pz <= 0): the reference aborts on the NaN there (types_sba.cpp:270-273,
+ * :355-358), the device returns the NaN or infinity.  In the .g2o format these edges carry no information matrix: the reference
+ * sets the identity (types_sba.cpp:204-244); here `info` is whatever the caller passes.
+ * Preconditions, validation (validate-then-commit) and error codes are those of g2ohip_pg_set_landmark_edges.  Refused with
+ * G2OHIP_ERR_ARG, in either order: landmark types 3-6 and 11 and any prior set beside a type-12 set; types 13 / 14 beside pose
+ * types 1, 2 and 10.  Everything after the binding -- g2ohip_pg_set_landmark_estimates, g2ohip_pg_linearize / update / push /
+ * pop / discard_top, robust kernels, do_schur 0 / 1, every linear_solver, g2ohip_clear_edge_sets -- acts on it unchanged; the
+ * kernel is timed in the pg_landmark_linearize slot and has the staged and direct store forms of option pg_landmark_staged.
+ * Not covered: EdgeSBACam, EdgeSBAScale, VertexIntrinsics / EdgeProjectP2MC_Intrinsics (a three-vertex edge), priors beside a
+ * type-12 set, more than one landmark set per handle (mono and stereo at once), sharded solves, the g2o plugin adapter (it keeps
+ * these edges on its host path). */
+int g2ohip_pg_set_cam_project_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                    const double* meas, const double* info, int n_cams, const double* intrinsics);
 /* ---- ... its unary pose priors: GPS fixes, an anchor on the first pose, surveyed checkpoints ------------------------
  * One UNARY edge set of the same handle beside the pose-pose set of g2ohip_pg_set_edges, in a slot of its own (independent of
  * the landmark slot: with or without a landmark set, do_schur 0 or 1; a later call replaces the binding):

@@ -61,7 +61,7 @@ EXPORTS = [
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
-    "g2ohip_pg_set_sim3_project_edges",
+    "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -167,6 +167,7 @@ def load():
     L.g2ohip_pg_set_landmark_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_camera_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_sim3_project_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
+    L.g2ohip_pg_set_cam_project_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -695,9 +696,10 @@ class HipBlockSolver:
         _check(self.L.g2ohip_copy_edge_data(self.h, set_id, _dp(J0), _dp(J1), _dp(err)), "edgeData")
         return J0, J1, err
 
-    # ---- device-resident pose-graph front end (EdgeSE2 = 1, EdgeSE3 = 2, EdgeSim3 = 10) ---------------
-    PG_POSE_STRIDE = {1: 3, 2: 12, 10: 8}    # doubles per estimate / measurement; EdgeSim3: (qx, qy, qz, qw, tx, ty, tz, s)
-    PG_POSE_DIM = {1: 3, 2: 6, 10: 7}
+    # ---- device-resident pose-graph front end (EdgeSE2 = 1, EdgeSE3 = 2, EdgeSim3 = 10, the VertexCam table = 12) ---------------
+    # doubles per estimate / measurement; EdgeSim3: (qx, qy, qz, qw, tx, ty, tz, s), VertexCam: (tx, ty, tz, qx, qy, qz, qw)
+    PG_POSE_STRIDE = {1: 3, 2: 12, 10: 8, 12: 7}
+    PG_POSE_DIM = {1: 3, 2: 6, 10: 7, 12: 6}
 
     def pgSetEdges(self, set_id, edge_type, vi, vj, meas, info):
         vi, vj, meas, info = _i32(vi), _i32(vj), _f64(meas), _f64(info)
@@ -786,6 +788,23 @@ class HipBlockSolver:
             raise ValueError("pgSetSim3ProjectEdges: intrinsics is [n_poses][4] = (fx, fy, cx, cy)")
         _check(self.L.g2ohip_pg_set_sim3_project_edges(self.h, set_id, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
                "pgSetSim3ProjectEdges")
+
+    def pgSetCamProjectEdges(self, set_id, edge_type, pose_vertex, point_vertex, meas, info, intrinsics):
+        """SBA-format observations beside a VertexCam set (type 12, which holds zero edges): edge_type 13 = EdgeProjectP2MC
+        (meas [n][2], info [n][2x2]), 14 = EdgeProjectP2SC (meas [n][3] = (u, v, u_right), info [n][3x3]); intrinsics
+        [n_cams][5] = (fx, fy, cx, cy, baseline) per entry of the table of pgSetEstimates.  Vertex 0 of the set is the camera,
+        vertex 1 the point (the reference's edges have them the other way round).  After pgSetEdges."""
+        if edge_type not in (13, 14):
+            raise ValueError("pgSetCamProjectEdges: edge_type is 13 (EdgeProjectP2MC) or 14 (EdgeProjectP2SC)")
+        pv, lv, meas, info = _i32(pose_vertex), _i32(point_vertex), _f64(meas), _f64(info)
+        n, d = self._set_sizes[set_id], edge_type - 11
+        if len(pv) != n or len(lv) != n or meas.size != n * d or info.size != n * d * d:
+            raise ValueError("pgSetCamProjectEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        kc = _f64(intrinsics)
+        if kc.ndim != 2 or kc.shape[1] != 5:
+            raise ValueError("pgSetCamProjectEdges: intrinsics is [n_cams][5] = (fx, fy, cx, cy, baseline)")
+        _check(self.L.g2ohip_pg_set_cam_project_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
+               "pgSetCamProjectEdges")
 
     def pgSetPriorEdges(self, set_id, edge_type, pose_vertex, meas, info, offset=None):
         """Unary priors on poses: edge_type 7 = EdgeSE2Prior (meas [n][3]), 8 = EdgeSE2XYPrior ([n][2]) beside EdgeSE2,

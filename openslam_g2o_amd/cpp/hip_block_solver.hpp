@@ -104,6 +104,13 @@ class HipBlockSolver {
                              int nCams, const double* intrinsics) {
     return ok(g2ohip_pg_set_sim3_project_edges(h_, set, poseVertex, pointVertex, meas, info, nCams, intrinsics), "pgSetSim3ProjectEdges");
   }
+  // SBA-format observations beside a VertexCam set (type 12, zero edges) of g2ohip_pg_set_edges (handle()): type 13 =
+  // EdgeProjectP2MC, 14 = EdgeProjectP2SC; vertex 0 of the set is the camera, vertex 1 the point; intrinsics [nCams][5] = fx, fy,
+  // cx, cy, baseline per entry of the pose table
+  bool pgSetCamProjectEdges(int set, int type, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas,
+                            const double* info, int nCams, const double* intrinsics) {
+    return ok(g2ohip_pg_set_cam_project_edges(h_, set, type, poseVertex, pointVertex, meas, info, nCams, intrinsics), "pgSetCamProjectEdges");
+  }
   // unary pose priors (g2ohip_pg_set_prior_edges): type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior beside an EdgeSE2 pose set, 9 =
   // EdgeSE3Prior beside an EdgeSE3 one; `set` is a unary set (addEdgeSet with v1 == nullptr), offset isometry [12] or nullptr (type 9)
   bool pgSetPriorEdges(int set, int type, const int32_t* poseVertex, const double* meas, const double* info, const double* offset) {

@@ -99,6 +99,8 @@ class BlockSolver {
                                     const double* info, const double* offset, const double* kcam);
   void pg_set_sim3_project_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
                                  int n_cams, const double* intrinsics);
+  void pg_set_cam_project_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                const double* info, int n_cams, const double* intrinsics);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -430,7 +432,9 @@ class BlockSolver {
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
   // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one ParameterCamera
   // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges), 11 = EdgeSim3ProjectXYZ (beside type 10, landmarks (x, y, z),
-  // one (fx, fy, cx, cy) per entry of the pose table; bound by pg_set_sim3_project_edges).  Vertex 0 of an observation
+  // one (fx, fy, cx, cy) per entry of the pose table; bound by pg_set_sim3_project_edges), 13 = EdgeProjectP2MC, 14 =
+  // EdgeProjectP2SC (beside type 12 = the VertexCam table, whose pose-pose set holds zero edges; landmarks (x, y, z), one (fx, fy,
+  // cx, cy, baseline) per entry of the pose table; bound by pg_set_cam_project_edges).  Vertex 0 of an observation
   // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); points.hidx[v] is the landmark's index in
   // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
   // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
@@ -446,6 +450,8 @@ class BlockSolver {
     DevBuf<double> meas;
     EstimateTable poses;           // (x, y, theta), T[12] or -- type 10 = EdgeSim3 over VertexSim3Expmap: no prior set and no
                                    // landmark set other than type 11 beside it -- (qx, qy, qz, qw, tx, ty, tz, s) per pose
+                                   // or -- type 12 = VertexCam: no prior set and no landmark set other than 13 / 14 beside it
+                                   // -- (tx, ty, tz, qx, qy, qz, qw) per camera
     bool fix_scale = false;        // VertexSim3Expmap::_fix_scale of the whole table (pg_set_sim3_fix_scale)
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
@@ -457,7 +463,8 @@ class BlockSolver {
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
     double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
     DevBuf<double> cam_k;          // type 11: (fx, fy, cx, cy) of every entry of `poses` (VertexSim3Expmap::_focal_length,
-    int n_cams = 0;                // _principle_point), n_cams entries: == poses.n whenever both are bound
+    int n_cams = 0;                // _principle_point), n_cams entries: == poses.n whenever both are bound; types 13 / 14: (fx,
+                                   // fy, cx, cy, baseline) (SBACam::Kcam, baseline)
     // ONE unary set of pose priors `pr_set`, independent of the landmark slot: pr_type 7 = EdgeSE2Prior (measurement (x, y, theta)),
     // 8 = EdgeSE2XYPrior ((x, y)) beside type 1, 9 = EdgeSE3Prior (isometry [12], one ParameterSE3Offset pr_offset) beside type 2.
     // vq indexes `poses`.  Priors own no vertices: pg_linearize fills the set's own_J0 / own_err, nothing else knows of them.

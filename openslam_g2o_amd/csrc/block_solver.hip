@@ -2084,6 +2084,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_prior.inc"
 #include "pg_sim3.inc"
 #include "pg_sim3_project.inc"
+#include "pg_cam_project.inc"
 #include "ba_stereo.inc"
 #undef PG_R
 
@@ -5417,10 +5418,11 @@ void BlockSolver::ba_discard_top() {
 }
 
 
-// ---- pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3) ----------------------------------------------
+// ---- pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3 / the VertexCam table) ------------------------
 // doubles per estimate / measurement, error (= vertex) dimension of a pose-pose type
-static int pg_pose_stride(int type) { return type == 1 ? 3 : type == 2 ? 12 : 8; }
-static int pg_pose_dim(int type) { return type == 1 ? 3 : type == 2 ? 6 : 7; }
+static int pg_pose_stride(int type) { return type == 1 ? 3 : type == 2 ? 12 : type == 12 ? 7 : 8; }
+static int pg_pose_dim(int type) { return type == 1 ? 3 : (type == 2 || type == 12) ? 6 : 7; }
+static bool pg_cam_landmark(int lm_type) { return lm_type == 13 || lm_type == 14; }
 // Sim3 values (qx, qy, qz, qw, tx, ty, tz, s): a quaternion of norm 0 is no rotation, a scale <= 0 has no logarithm
 static void pg_validate_sim3(const char* who, const double* v, size_t n) {
   for (size_t k = 0; k < n; ++k) {
@@ -5433,19 +5435,41 @@ static void pg_validate_sim3(const char* who, const double* v, size_t n) {
   }
 }
 
+// VertexCam rows (tx, ty, tz, qx, qy, qz, qw): a quaternion of norm 0 is no rotation; otherwise the row is kept as given
+static void pg_validate_cams(const char* who, const double* v, size_t n) {
+  for (size_t k = 0; k < n; ++k) {
+    const double* c = v + 7 * k;
+    for (int i = 0; i < 7; ++i)
+      if (!std::isfinite(c[i])) throw ArgFailure(std::string(who) + ": non-finite VertexCam value in entry " + std::to_string(k));
+    if (c[3] == 0.0 && c[4] == 0.0 && c[5] == 0.0 && c[6] == 0.0)
+      throw ArgFailure(std::string(who) + ": quaternion of norm 0 in entry " + std::to_string(k));
+  }
+}
+
 void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
   invalidate_graphs();
   require_structure();
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (type != 1 && type != 2 && type != 10) throw ArgFailure("pg_set_edges: type must be 1 (EdgeSE2), 2 (EdgeSE3) or 10 (EdgeSim3)");
+  if (type != 1 && type != 2 && type != 10 && type != 12)
+    throw ArgFailure("pg_set_edges: type must be 1 (EdgeSE2), 2 (EdgeSE3), 10 (EdgeSim3) or 12 (the VertexCam table)");
   EdgeSet& es = *sets_[set];
   const int d = pg_pose_dim(type);
   if (type == 10 && p_ != 7) throw ArgFailure("pg_set_edges: EdgeSim3 (10) needs a solver of pose dimension 7");
+  if (type == 12 && (p_ != 6 || l_ != 3)) throw ArgFailure("pg_set_edges: the VertexCam table (12) needs a solver of (pose, landmark) dimensions (6, 3)");
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d) throw ArgFailure("pg_set_edges: the set must be a binary pose-pose set of matching dimension");
   const size_t n = (size_t)es.n, ms = (size_t)pg_pose_stride(type);
-  // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays)
-  if ((n > 0 || type != 10) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
-  if (type == 10) {
+  if (type == 12 && n > 0)
+    throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam is not on the device yet (it has no analytic Jacobian in the reference)");
+  // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
+  // type-12 set is always empty: it is the anchor of the camera table that the landmark slot needs)
+  if ((n > 0 || (type != 10 && type != 12)) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
+  if (type == 12) {
+    // beside a VertexCam table stands an EdgeProjectP2MC (13) or EdgeProjectP2SC (14) landmark set or nothing
+    if ((pg_.lm_set >= 0 && !pg_cam_landmark(pg_.lm_type)) || pg_.pr_set >= 0)
+      throw ArgFailure("pg_set_edges: a VertexCam set (12) cannot be bound beside a prior set or a landmark set other than EdgeProjectP2MC (13) / EdgeProjectP2SC (14)");
+  } else if (pg_.lm_set >= 0 && pg_cam_landmark(pg_.lm_type)) {
+    throw ArgFailure("pg_set_edges: an EdgeProjectP2MC / EdgeProjectP2SC landmark set (13 / 14) is bound: it stands beside a VertexCam set (12) only");
+  } else if (type == 10) {
     // beside a Sim3 set stands an EdgeSim3ProjectXYZ landmark set (11) or nothing: no other landmark, camera or prior set
     if ((pg_.lm_set >= 0 && pg_.lm_type != 11) || pg_.pr_set >= 0)
       throw ArgFailure("pg_set_edges: EdgeSim3 (10) cannot be bound beside a prior set or a landmark set other than EdgeSim3ProjectXYZ (11)");
@@ -5495,11 +5519,12 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const int ps = pg_pose_stride(pg_.type);
   if (pg_.type == 10) pg_validate_sim3("pg_set_estimates", poses, (size_t)nv);
+  if (pg_.type == 12) pg_validate_cams("pg_set_estimates", poses, (size_t)nv);
   const bool same = pg_.poses.same(nv, ps, hidx);   // (same tables, new values: see ba_set_estimates)
   if (!same) {
     pg_validate(*sets_[pg_.set], pg_.h_vi.data(), pg_.h_vj.data(), pg_.h_vi.size(), hidx, nv);
-    if (pg_.lm_set >= 0 && pg_.lm_type == 11 && nv != pg_.n_cams)
-      throw ArgFailure("pg_set_estimates: " + std::to_string(nv) + " poses, but the EdgeSim3ProjectXYZ set was bound with intrinsics of " +
+    if (pg_.lm_set >= 0 && (pg_.lm_type == 11 || pg_cam_landmark(pg_.lm_type)) && nv != pg_.n_cams)
+      throw ArgFailure("pg_set_estimates: " + std::to_string(nv) + " poses, but the projection set was bound with intrinsics of " +
                        std::to_string(pg_.n_cams) + " cameras");
     if (pg_.lm_set >= 0)
       pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
@@ -5528,6 +5553,7 @@ void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_verte
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
   if (pg_.type == 10) throw ArgFailure("pg_set_landmark_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
+  if (pg_.type == 12) throw ArgFailure("pg_set_landmark_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
   if (type != 3 && type != 4) throw ArgFailure("pg_set_landmark_edges: type must be 3 (EdgeSE2PointXY) or 4 (EdgeSE3PointXYZ)");
   if (type != pg_.type + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
   if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
@@ -5542,6 +5568,7 @@ void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pos
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_camera_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
   if (pg_.type == 10) throw ArgFailure("pg_set_landmark_camera_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
+  if (pg_.type == 12) throw ArgFailure("pg_set_landmark_camera_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
   if (type != 5 && type != 6) throw ArgFailure("pg_set_landmark_camera_edges: type must be 5 (EdgeSE3PointXYZDepth) or 6 (EdgeSE3PointXYZDisparity)");
   if (pg_.type != 2) throw ArgFailure("pg_set_landmark_camera_edges: the camera edges go with an EdgeSE3 pose set (2)");
   if (!kcam) throw ArgFailure("pg_set_landmark_camera_edges: null kcam (fx, fy, cx, cy)");
@@ -5573,22 +5600,48 @@ void BlockSolver::pg_set_sim3_project_edges(int set, const int* pose_vertex, con
   pg_bind_landmark_edges("pg_set_sim3_project_edges", set, 11, pose_vertex, point_vertex, meas, info, nullptr, intrinsics, n_cams);
 }
 
-// what the three entries share: the set's dimensions, index validation, the uploads (type 11: kcam is the table [n_cams][4])
+// EdgeProjectP2MC (13, mono) / EdgeProjectP2SC (14, stereo) beside a VertexCam set (12): the projection of a VertexSBAPointXYZ
+// into the camera pose_vertex[k], whose Kcam and baseline are row pose_vertex[k] of `intrinsics` [n_cams][5] = (fx, fy, cx, cy,
+// baseline) -- one row per entry of the pose table (pg_cam_project.inc)
+void BlockSolver::pg_set_cam_project_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
+                                           const double* info, int n_cams, const double* intrinsics) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_cam_project_edges: call pg_set_edges first (the empty VertexCam set (12) the landmark set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 13 && type != 14) throw ArgFailure("pg_set_cam_project_edges: type must be 13 (EdgeProjectP2MC) or 14 (EdgeProjectP2SC)");
+  if (pg_.type != 12) throw ArgFailure("pg_set_cam_project_edges: EdgeProjectP2MC / EdgeProjectP2SC go with a VertexCam set (12)");
+  if (n_cams <= 0 || !intrinsics) throw ArgFailure("pg_set_cam_project_edges: no intrinsics (fx, fy, cx, cy, baseline per camera)");
+  for (size_t i = 0; i < 5 * (size_t)n_cams; ++i)
+    if (!std::isfinite(intrinsics[i])) throw ArgFailure("pg_set_cam_project_edges: non-finite intrinsics of camera " + std::to_string(i / 5));
+  for (int c = 0; c < n_cams; ++c)
+    if (intrinsics[5 * (size_t)c] == 0.0 || intrinsics[5 * (size_t)c + 1] == 0.0)
+      throw ArgFailure("pg_set_cam_project_edges: fx and fy must not be zero (camera " + std::to_string(c) + ")");
+  if (pg_.poses.n > 0 && n_cams != pg_.poses.n)
+    throw ArgFailure("pg_set_cam_project_edges: intrinsics of " + std::to_string(n_cams) + " cameras, but the pose table holds " +
+                     std::to_string(pg_.poses.n) + " cameras");
+  pg_bind_landmark_edges("pg_set_cam_project_edges", set, type, pose_vertex, point_vertex, meas, info, nullptr, intrinsics, n_cams);
+}
+
+// what the four entries share: the set's dimensions, index validation, the uploads (types 11 and 13 / 14: kcam is the table
+// [n_cams][4] and [n_cams][5])
 void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
                                          const double* meas, const double* info, const double* offset, const double* kcam, int n_cams) {
   const std::string w(who);
   if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
   if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
   EdgeSet& es = *sets_[set];
-  const int d = (type == 3 || type == 11) ? 2 : 3, dp = type == 3 ? 3 : type == 11 ? 7 : 6, dl = type == 3 ? 2 : 3;
+  const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
+  const int ks = type == 11 ? 4 : 5;
+  const int d = (type == 3 || type == 11 || type == 13) ? 2 : 3, dp = type == 3 ? 3 : type == 11 ? 7 : 6, dl = type == 3 ? 2 : 3;
   if (es.unary || es.d != d || es.dim0 != dp || es.dim1 != dl || p_ != dp || l_ != dl)
     throw ArgFailure(w + ": the set must be a binary pose-landmark set with (error, pose, landmark) dimensions " +
-                     (type == 11 ? "(2, 7, 3)" : "(2, 3, 2) or (3, 6, 3)"));
+                     (type == 11 ? "(2, 7, 3)" : type == 13 ? "(2, 6, 3)" : type == 14 ? "(3, 6, 3)" : "(2, 3, 2) or (3, 6, 3)"));
   if (!pose_vertex || !point_vertex || !meas || !info) throw ArgFailure(w + ": null array");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
-  if (type == 11)   // (the kernels index the intrinsics by pose_vertex: in range also while no pose table is bound)
+  if (table)   // (the kernels index the intrinsics by pose_vertex: in range also while no pose table is bound)
     for (size_t k = 0; k < n; ++k)
       if (pose_vertex[k] >= n_cams) throw ArgFailure(w + ": pose index of landmark edge " + std::to_string(k) + " outside the intrinsics table");
   pg_.lm_set = set;
@@ -5596,9 +5649,9 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   pg_.h_vp.assign(pose_vertex, pose_vertex + n);
   pg_.h_vl.assign(point_vertex, point_vertex + n);
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
-  for (int i = 0; i < 4; ++i) pg_.kcam[i] = (kcam && type != 11) ? kcam[i] : (i < 2 ? 1.0 : 0.0);
-  pg_.n_cams = type == 11 ? n_cams : 0;
-  if (type == 11) pg_.cam_k.upload(kcam, 4 * (size_t)n_cams, st_);
+  for (int i = 0; i < 4; ++i) pg_.kcam[i] = (kcam && !table) ? kcam[i] : (i < 2 ? 1.0 : 0.0);
+  pg_.n_cams = table ? n_cams : 0;
+  if (table) pg_.cam_k.upload(kcam, ks * (size_t)n_cams, st_);
   pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
   chi2_valid_ = false;
   pg_.vp.upload(pose_vertex, n, st_);
@@ -5622,6 +5675,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_prior_edges: call pg_set_edges first (the pose-pose set the prior set stands beside)");
   if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
   if (pg_.type == 10) throw ArgFailure("pg_set_prior_edges: no prior set stands beside an EdgeSim3 pose set (10)");
+  if (pg_.type == 12) throw ArgFailure("pg_set_prior_edges: no prior set stands beside a VertexCam set (12)");
   if (type != 7 && type != 8 && type != 9) throw ArgFailure("pg_set_prior_edges: type must be 7 (EdgeSE2Prior), 8 (EdgeSE2XYPrior) or 9 (EdgeSE3Prior)");
   if ((type == 9) != (pg_.type == 2)) throw ArgFailure("pg_set_prior_edges: EdgeSE2Prior (7) and EdgeSE2XYPrior (8) go with an EdgeSE2 pose set (1), EdgeSE3Prior (9) with EdgeSE3 (2)");
   if (offset && type != 9) throw ArgFailure("pg_set_prior_edges: an offset belongs to EdgeSE3Prior (type 9) only");
@@ -5712,7 +5766,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
   else if (pg_.type == 2)
     hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  else if (es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
+  else if (pg_.type == 10 && es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
     prof.begin(KernelProf::kPgSim3Error, st_);
     hipLaunchKernelGGL(pg_sim3_error_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_err.p);
@@ -5734,6 +5788,16 @@ void BlockSolver::pg_linearize(bool jacobians) {
       hipLaunchKernelGGL(pg_sim3_project_jacobian_kernel, dim3(grid_for(10 * (size_t)el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p,
                          pg_.points.val.p, pg_.poses.hidx.p, pg_.points.hidx.p, pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p,
                          pg_.fix_scale ? 1 : 0, el->own_J0.p, el->own_J1.p);
+  } else if (lm_launch && pg_cam_landmark(pg_.lm_type)) {   // EdgeProjectP2MC / EdgeProjectP2SC -- pg_cam_project.inc
+    const dim3 grid(grid_for(el->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      with_bool(pg_.lm_type == 14, [&](auto stereo) {
+        constexpr bool STEREO = stereo;
+        hipLaunchKernelGGL((pg_cam_project_linearize_kernel<STEREO, STAGED>), grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
+                           pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+      });
+    });
   } else if (lm_launch) {
     const dim3 grid(grid_for(el->n)), block(kThreads);
     PgIso off;
@@ -5793,6 +5857,9 @@ void BlockSolver::pg_update() {
                        pg_.poses.hidx.p, d_x.p);
   else if (pg_.type == 2)
     hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, d_x.p);
+  else if (pg_.type == 12)
+    hipLaunchKernelGGL(pg_cam_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
   else
     hipLaunchKernelGGL(pg_sim3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,

@@ -685,6 +685,10 @@ int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* p
                                      const double* info, int n_cams, const double* intrinsics) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_sim3_project_edges(set, pose_vertex, point_vertex, meas, info, n_cams, intrinsics); });
 }
+int g2ohip_pg_set_cam_project_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                    const double* meas, const double* info, int n_cams, const double* intrinsics) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_cam_project_edges(set, type, pose_vertex, point_vertex, meas, info, n_cams, intrinsics); });
+}
 int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const double* meas, const double* info,
                               const double* offset) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_prior_edges(set, type, pose_vertex, meas, info, offset); });

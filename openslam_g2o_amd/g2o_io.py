@@ -13,6 +13,14 @@ parameter_se3_offset}.cpp read()); RGB-D / stereo files `EDGE_PROJECT_DEPTH` / `
 Monocular 7-dof graphs: `VERTEX_SIM3:EXPMAP` / `EDGE_SIM3:EXPMAP` (g2o/types/sim3/types_seven_dof_expmap.cpp:59-136 read() /
 write(); read_g2o and write_g2o_sim3), with map points `VERTEX_XYZ` (g2o/types/sba/types_sba.cpp, VertexSBAPointXYZ) observed
 through `EDGE_PROJECT_SIM3_XYZ:EXPMAP` (types_seven_dof_expmap.cpp:145-172: id_point id_pose u v i00 i01 i11).
+SBA-format bundle adjustment, the format of the reference's sba_demo and of BA datasets in g2o form: `VERTEX_CAM` (id tx ty tz
+qx qy qz qw fx fy cx cy baseline, g2o/types/sba/types_sba.cpp:74-131 read() / write(); the quaternion is normalised on read, a
+line without intrinsics gets 300 300 320 320 0.1) with `EDGE_PROJECT_P2MC` (id_point id_cam u v) / `EDGE_PROJECT_P2SC` (id_point
+id_cam u v u_right), which store NO information matrix: it is the identity (types_sba.cpp:204-244); read_g2o, write_g2o_sbacam
+and sbacam_ba_problem.
+`VERTEX_XYZ` is ONE tag, VertexSBAPointXYZ (types_sba.cpp:40, 180-195: id x y z), whatever observes it: read_g2o hands its
+points to the sim3 keys in a VERTEX_SIM3:EXPMAP file and to the cam keys in a VERTEX_CAM file, read_g2o_ba reads it beside
+VERTEX_SE3:EXPMAP cameras; the value read is the same three doubles for all of them.
 Host-side bookkeeping only; nothing here is on the accelerated path.
 """
 import numpy as np
@@ -48,11 +56,17 @@ def read_g2o(path):
     (types_seven_dof_expmap.cpp:81, 110-111).  A sim3 file with VERTEX_XYZ (id x y z) or EDGE_PROJECT_SIM3_XYZ:EXPMAP (id_point
     id_pose u v + upper triangle of the 2x2 information) lines also gives sim3_point_ids, sim3_points [L][3] (sorted by id),
     sim3_vp / sim3_vl (pose-table and point-table index of every observation), sim3_zl [m][2], sim3_omega_l [m][4] and
-    sim3_fixed_points; a file without them gives none of these keys (sim3_ba_problem turns them into a problem dict)."""
+    sim3_fixed_points; a file without them gives none of these keys (sim3_ba_problem turns them into a problem dict).
+    A file of VERTEX_CAM lines gives kind = 'sbacam', estimates [n][7] = (tx, ty, tz, qx, qy, qz, qw) with the quaternion
+    normalised as VertexCam::read does, cam_intrinsics [n][5] = (fx, fy, cx, cy, baseline), cam_point_ids, cam_points [L][3]
+    (the VERTEX_XYZ lines, sorted by id), cam_vp / cam_vl (camera-table and point-table index of every EDGE_PROJECT_P2MC /
+    EDGE_PROJECT_P2SC line), cam_zl [m][2|3], cam_stereo and cam_fixed_points (sbacam_ba_problem turns them into a problem
+    dict); a file that mixes the two edge tags raises ValueError."""
     from . import sim3 as S3
     sim3_extras = []
     spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
+    cam_extras, cam_pt, cam_cam, cam_meas, cam_stereo = [], [], [], [], None
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
     qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
@@ -91,6 +105,21 @@ def read_g2o(path):
                 ej.append(int(t[2]))
                 meas.append(S3.sim3_inverse(S3.FP64, S3.sim3_exp(S3.FP64, [float(x) for x in t[3:10]])))
                 info.append(_upper_to_full([float(x) for x in t[10:38]], 7))
+            elif tag == "VERTEX_CAM":
+                kind = kind or "sbacam"
+                vid.append(int(t[1]))
+                v = [float(x) for x in t[2:9]]
+                norm = np.sqrt(v[3] * v[3] + v[4] * v[4] + v[5] * v[5] + v[6] * v[6])
+                vest.append(v[0:3] + [q / norm for q in v[3:7]])
+                cam_extras.append([float(x) for x in t[9:14]] if len(t) >= 14 else [300.0, 300.0, 320.0, 320.0, 0.1])
+            elif tag in ("EDGE_PROJECT_P2MC", "EDGE_PROJECT_P2SC"):
+                st = tag == "EDGE_PROJECT_P2SC"
+                if cam_stereo is not None and cam_stereo != st:
+                    raise ValueError("%s mixes EDGE_PROJECT_P2MC and EDGE_PROJECT_P2SC: one observation set is one edge type" % path)
+                cam_stereo = st
+                cam_pt.append(int(t[1]))
+                cam_cam.append(int(t[2]))
+                cam_meas.append([float(x) for x in t[3:(6 if st else 5)]])
             elif tag == "VERTEX_XYZ":
                 spid.append(int(t[1]))
                 spest.append([float(x) for x in t[2:5]])
@@ -168,6 +197,17 @@ def read_g2o(path):
                    sim3_vp=np.asarray([lut[a] for a in sp_pose], np.int32), sim3_vl=np.asarray([splut[a] for a in sp_pt], np.int32),
                    sim3_zl=np.asarray(sp_meas, np.float64).reshape(-1, 2), sim3_omega_l=np.asarray(sp_info, np.float64).reshape(-1, 4),
                    sim3_fixed_points=[splut[f] for f in fixed if f in splut])
+    if kind == "sbacam":
+        spid = np.asarray(spid, np.int64)
+        so = np.argsort(spid, kind="stable")
+        spid = spid[so]
+        splut = {int(v): k for k, v in enumerate(spid)}
+        d = 3 if cam_stereo else 2
+        out.update(cam_intrinsics=np.asarray(cam_extras, np.float64).reshape(-1, 5)[order], cam_point_ids=spid,
+                   cam_points=np.asarray(spest, np.float64).reshape(-1, 3)[so],
+                   cam_vp=np.asarray([lut[a] for a in cam_cam], np.int32), cam_vl=np.asarray([splut[a] for a in cam_pt], np.int32),
+                   cam_zl=np.asarray(cam_meas, np.float64).reshape(-1, d), cam_stereo=bool(cam_stereo),
+                   cam_fixed_points=[splut[f] for f in fixed if f in splut])
     if pid or lp or offsets or cameras:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
@@ -242,6 +282,54 @@ def sim3_ba_problem(rd, fixed_poses=None, fixed_points=None):
     return dict(est=rd["estimates"], hidx=hidx, num_free=nP, nP=nP, nL=k - nP, vi=rd["vi"], vj=rd["vj"], meas=rd["meas"],
                 info=rd["info"].reshape(-1, 49), points=rd["sim3_points"], pt_hidx=pt_hidx, vp=rd["sim3_vp"], vl=rd["sim3_vl"],
                 zl=rd["sim3_zl"], omega_l=rd["sim3_omega_l"], intrinsics=rd["sim3_extras"], fix_scale=False)
+
+
+def write_g2o_sbacam(path, prob, ids=None, point_ids=None):
+    """make_sbacam_ba-style problem -> `.g2o` text in the reference's SBA format: VERTEX_CAM lines as VertexCam::write states
+    them (types_sba.cpp:114-131: t, the quaternion's coefficients, fx fy cx cy baseline), VERTEX_XYZ lines (ids point_ids,
+    default n ..), FIX lines for the vertices of hessian index -1, and EDGE_PROJECT_P2MC / EDGE_PROJECT_P2SC lines "id_point
+    id_cam u v [u_right]" -- the reference writes no information matrix (types_sba.cpp:215-244) and reads the identity, so
+    omega_l must be the identity.  %.17g: a read gives the written doubles back."""
+    est = np.asarray(prob["est"], np.float64).reshape(-1, 7)
+    pts = np.asarray(prob["points"], np.float64).reshape(-1, 3)
+    intr = np.asarray(prob["intrinsics"], np.float64).reshape(len(est), 5)
+    n = len(est)
+    zl = np.asarray(prob["zl"], np.float64)
+    stereo = zl.shape[1] == 3
+    d = 3 if stereo else 2
+    om = np.asarray(prob["omega_l"], np.float64).reshape(-1, d * d)
+    if not np.array_equal(om, np.tile(np.eye(d).reshape(1, d * d), (len(om), 1))):
+        raise ValueError("write_g2o_sbacam: EDGE_PROJECT_P2MC / EDGE_PROJECT_P2SC lines carry no information matrix: omega_l must be the identity")
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    point_ids = n + np.arange(len(pts)) if point_ids is None else np.asarray(point_ids)
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    with open(path, "w") as f:
+        for k in range(n):
+            f.write("VERTEX_CAM %d %s %s\n" % (ids[k], fmt(est[k]), fmt(intr[k])))
+        for j in range(len(pts)):
+            f.write("VERTEX_XYZ %d %s\n" % (point_ids[j], fmt(pts[j])))
+        fixed = [ids[k] for k in range(n) if prob["hidx"][k] < 0] + [point_ids[j] for j in range(len(pts)) if prob["pt_hidx"][j] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(int(i)) for i in fixed))
+        tag = "EDGE_PROJECT_P2SC" if stereo else "EDGE_PROJECT_P2MC"
+        for e in range(len(zl)):
+            f.write("%s %d %d %s\n" % (tag, point_ids[prob["vl"][e]], ids[prob["vp"][e]], fmt(zl[e])))
+
+
+def sbacam_ba_problem(rd, fixed_cams=None, fixed_points=None):
+    """read_g2o result of a VERTEX_CAM file -> the problem dict of lm.setup_device_sbacam_ba (the layout of
+    synthetic.make_sbacam_ba): free cameras by vertex id, then free points by vertex id (sparse_optimizer.cpp:174-187); fixed
+    vertices from the file's FIX lines unless given; the information of every observation is the identity."""
+    if rd.get("kind") != "sbacam" or not len(rd["cam_points"]):
+        raise ValueError("sbacam_ba_problem: not a VERTEX_CAM file with VERTEX_XYZ points")
+    n, L = len(rd["estimates"]), len(rd["cam_points"])
+    hidx, pt_hidx, nP, nL = landmark_hessian_index(n, L, rd["fixed"] if fixed_cams is None else fixed_cams,
+                                                   rd["cam_fixed_points"] if fixed_points is None else fixed_points)
+    d = 3 if rd["cam_stereo"] else 2
+    m = len(rd["cam_vp"])
+    return dict(est=rd["estimates"], hidx=hidx, nP=nP, nL=nL, points=rd["cam_points"], pt_hidx=pt_hidx, vp=rd["cam_vp"],
+                vl=rd["cam_vl"], zl=rd["cam_zl"], omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)),
+                intrinsics=rd["cam_intrinsics"], stereo=bool(rd["cam_stereo"]))
 
 
 def hessian_index(n_vertices, fixed):

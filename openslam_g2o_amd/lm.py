@@ -311,7 +311,7 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
 
 class DevicePoseGraph:
     """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3, and the
-    landmark observations bound beside them: setup_device_landmark_slam, setup_device_sim3_ba)."""
+    landmark observations bound beside them: setup_device_landmark_slam, setup_device_sim3_ba, setup_device_sbacam_ba)."""
 
     device_resident = True
 
@@ -443,6 +443,38 @@ def setup_device_sim3_ba(prob, huber_delta=0.0, schur=True, device=0, options=No
     s.pgSetSim3FixScale(prob.get("fix_scale", False))
     s.pgSetEstimates(prob["est"], hidx)
     s.pgSetSim3ProjectEdges(k1, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob["intrinsics"])
+    s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
+    if huber_delta > 0:
+        s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    s.landmark_sets = (k0, k1)
+    s.pose_set = k0
+    return s, DevicePoseGraph(s)
+
+
+def setup_device_sbacam_ba(prob, huber_delta=0.0, schur=True, device=0, options=None):
+    """HipBlockSolver for an openslam_g2o_amd.synthetic.make_sbacam_ba (or g2o_io.sbacam_ba_problem) graph: bundle adjustment in
+    the reference's SBA format -- VertexCam cameras with intrinsics and baselines of their own observing VertexSBAPointXYZ
+    points through EdgeProjectP2MC (zl [m][2]) or EdgeProjectP2SC (zl [m][3]); camera and point estimates, errors and the
+    analytic Jacobians on the device; BlockSolver_6_3 semantics, points marginalised (schur=True).  huber_delta > 0: Huber
+    kernel on the observation set.  Returns (solver, DevicePoseGraph); solver.landmark_sets = (the empty VertexCam set's id,
+    observation set id), solver.pose_set = the former."""
+    import numpy as np
+    from . import capi
+    s = capi.HipBlockSolver(6, 3, device)
+    for name, value in (options or {}).items():
+        s.setOption(name, value)
+    hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
+    zl = np.asarray(prob["zl"], np.float64)
+    if zl.ndim != 2 or zl.shape[1] not in (2, 3):
+        raise ValueError("setup_device_sbacam_ba: zl is [m][2] (EdgeProjectP2MC) or [m][3] (EdgeProjectP2SC)")
+    d = zl.shape[1]
+    none = np.zeros(0, np.int32)
+    k0 = s.addEdgeSet(6, none, none)
+    k1 = s.addEdgeSet(d, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    s.buildStructure(prob["nP"], prob["nL"], schur)
+    s.pgSetEdges(k0, 12, none, none, np.zeros((0, 7)), np.zeros((0, 36)))
+    s.pgSetEstimates(prob["est"], hidx)
+    s.pgSetCamProjectEdges(k1, 11 + d, prob["vp"], prob["vl"], zl, prob["omega_l"], prob["intrinsics"])
     s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
     if huber_delta > 0:
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)

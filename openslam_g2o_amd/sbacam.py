@@ -1,0 +1,138 @@
+"""Host-side arithmetic of the reference's SBA-format types, for the generators, the file reader / writer and the tests:
+
+  SBACam::update                                         g2o/types/sba/sbacam.h:101-117
+  SBACam::transformW2F (w2n = [R' | -R' t])              g2o/types/sba/sbacam.h:120-130
+  SBACam::setDr (dRdx/y/z = dRid{x,y,z} R')              g2o/types/sba/sbacam.h:162-181
+  EdgeProjectP2MC / EdgeProjectP2SC::computeError        g2o/types/sba/types_sba.h:170-192, :209-247
+  EdgeProjectP2SC / EdgeProjectP2MC::linearizeOplus      g2o/types/sba/types_sba.cpp:249-328, :334-403 (analytic)
+  VertexSBAPointXYZ::oplusImpl                           g2o/types/sba/types_sba.h:151-155
+  Eigen: toRotationMatrix, quaternion product
+
+ONE body of formulas, written operation for operation and generic over the arithmetic F, as openslam_g2o_amd/sim3.py is: FP64
+below (Python floats = IEEE doubles), tests/sbacam_helpers.py adds mpmath at 60 digits.  F supplies num(x) and sqrt.  There is
+no data-dependent branch in any of it.  The device kernels (csrc/pg_cam_project.inc) state the same operations in HIP, in the
+same order and without contraction to fused multiply-adds, and share no code with this file.
+
+Layouts as in the C ABI: a camera is 7 doubles (tx, ty, tz, qx, qy, qz, qw), camera-to-world (SE3Quat::toVector, VertexCam::write);
+its intrinsics are (fx, fy, cx, cy, baseline); a step is (dt[3], dq[3]); the Jacobian of an edge is (Jcam d x 6, Jpoint d x 3),
+the camera first as in the landmark slot -- the reference's edges have the point as vertex 0 (Jcam = _jacobianOplusXj, Jpoint =
+_jacobianOplusXi).  d = 2 (EdgeProjectP2MC) or 3 (EdgeProjectP2SC, third row = u in the right image).  Like the reference there
+is no guard for a point on or behind the image plane."""
+import numpy as np
+
+from .sim3 import FP64, _vec, q_mul, q_to_R, to_f64  # noqa: F401
+
+IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def _dot3(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def w2n(F, cam):
+    """transformW2F: (R', -R' t) with R = toRotationMatrix(q) of the quaternion as stored; R' as a list of rows."""
+    cam = _vec(F, cam)
+    R = q_to_R(F, cam[3:7])
+    Rt = [[R[j][i] for j in range(3)] for i in range(3)]
+    return Rt, [-_dot3(Rt[i], cam[0:3]) for i in range(3)]
+
+
+def camera_point(F, cam, X):
+    """pc = w2n (X, 1): the point in camera coordinates."""
+    X = _vec(F, X)
+    Rt, w3 = w2n(F, cam)
+    return [_dot3(Rt[i], X) + w3[i] for i in range(3)]
+
+
+def project_error(F, cam, X, kc, z, stereo=False):
+    """computeError: ((fx px + cx pz) / pz, (fy py + cy pz) / pz [, (fx (px - baseline) + cx pz) / pz]) - z."""
+    px, py, pz = camera_point(F, cam, X)
+    fx, fy, cx, cy, b = _vec(F, kc)
+    z = _vec(F, z)
+    e = [(fx * px + cx * pz) / pz - z[0], (fy * py + cy * pz) / pz - z[1]]
+    if stereo:
+        e.append((fx * (px - b) + cx * pz) / pz - z[2])
+    return e
+
+
+def project_jacobians(F, cam, X, kc, stereo=False):
+    """linearizeOplus: every column is ((pz dp0 - px dp2) ipz2fx, (pz dp1 - py dp2) ipz2fy [, (pz dp0 - (px - b) dp2) ipz2fx])
+    of a dp = d(pc) / d(parameter): -w2n.col(i) for the camera's translation, dRd{x,y,z} (X - t) for its quaternion's x, y, z,
+    +w2n.col(i) for the point.  Returns (Jcam d x 6, Jpoint d x 3) as row lists J[row][col]."""
+    cam, X = _vec(F, cam), _vec(F, X)
+    fx, fy, cx, cy, b = _vec(F, kc)
+    Rt, w3 = w2n(F, cam)
+    px, py, pz = [_dot3(Rt[i], X) + w3[i] for i in range(3)]
+    pxb = px - b
+    ipz2 = F.num(1.0) / (pz * pz)
+    ipz2fx, ipz2fy = ipz2 * fx, ipz2 * fy
+    pwt = [X[i] - cam[i] for i in range(3)]
+    rp = [_dot3(Rt[i], pwt) for i in range(3)]
+    r2 = [v + v for v in rp]
+    zero = F.num(0.0)
+    # dRidx = [0 0 0; 0 0 2; 0 -2 0], dRidy = [0 0 -2; 0 0 0; 2 0 0], dRidz = [0 2 0; -2 0 0; 0 0 0], each times R' (X - t)
+    rot = [[zero, r2[2], -r2[1]], [-r2[2], zero, r2[0]], [r2[1], -r2[0], zero]]
+
+    def column(dp):
+        c = [(pz * dp[0] - px * dp[2]) * ipz2fx, (pz * dp[1] - py * dp[2]) * ipz2fy]
+        if stereo:
+            c.append((pz * dp[0] - pxb * dp[2]) * ipz2fx)
+        return c
+
+    cols = [column([-Rt[0][c], -Rt[1][c], -Rt[2][c]]) for c in range(3)] + [column(dp) for dp in rot]
+    pcols = [column([Rt[0][c], Rt[1][c], Rt[2][c]]) for c in range(3)]
+    d = 3 if stereo else 2
+    return [[cols[c][r] for c in range(6)] for r in range(d)], [[pcols[c][r] for c in range(3)] for r in range(d)]
+
+
+def oplus(F, cam, x):
+    """SBACam::update: t += x[0:3]; qr = (x[3:6], sqrt(1 - |x[3:6]|^2)); q <- q qr, then q / |q|.  No sign flip."""
+    cam, x = _vec(F, cam), _vec(F, x)
+    qr = [x[3], x[4], x[5], F.sqrt(F.num(1.0) - (x[3] * x[3] + x[4] * x[4] + x[5] * x[5]))]
+    p = q_mul(cam[3:7], qr)
+    norm = F.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3])
+    return [cam[i] + x[i] for i in range(3)] + [v / norm for v in p]
+
+
+# ------------------------------------------------------------------------------------------------ whole edge lists
+def project_edges(F, cams, points, vp, vl, meas, intrinsics, stereo=False, jac=True):
+    """err [n][d] and (jac) J0 [n][d x 6] (camera), J1 [n][d x 3] (point) column-major of a whole edge list, rounded to fp64;
+    intrinsics [n_cams][5] indexed by vp.  Blocks of fixed vertices are evaluated like the others."""
+    n, d = len(vp), 3 if stereo else 2
+    err = np.zeros((n, d))
+    J0, J1 = np.zeros((n, 6 * d)), np.zeros((n, 3 * d))
+    for k in range(n):
+        a, b = int(vp[k]), int(vl[k])
+        err[k] = to_f64(project_error(F, cams[a], points[b], intrinsics[a], meas[k], stereo))
+        if jac:
+            Jc, Jx = project_jacobians(F, cams[a], points[b], intrinsics[a], stereo)
+            J0[k] = to_f64([Jc[r][c] for c in range(6) for r in range(d)])
+            J1[k] = to_f64([Jx[r][c] for c in range(3) for r in range(d)])
+    return (J0, J1, err) if jac else err
+
+
+def update(F, cams, hidx, x):
+    """oplus of every free camera with its 6 entries of the solution x; fixed cameras are returned as they are."""
+    out = np.array(cams, np.float64).copy()
+    for v in range(len(cams)):
+        h = int(hidx[v])
+        if h >= 0:
+            out[v] = to_f64(oplus(F, cams[v], x[6 * h:6 * h + 6]))
+    return out
+
+
+def moved_points(points, pt_hidx, nP, x):
+    """VertexSBAPointXYZ::oplusImpl with the point slices of x: exactly points + x (one fp64 addition per coordinate)."""
+    out = np.array(points, np.float64).copy()
+    for v in range(len(out)):
+        h = int(pt_hidx[v])
+        if h >= 0:
+            o = 6 * nP + 3 * (h - nP)
+            out[v] = out[v] + x[o:o + 3]
+    return out
+
+
+def transform(cam):
+    """(R, t) of a stored camera in fp64: q and -q are the same rotation."""
+    cam = np.asarray(cam, np.float64)
+    return np.array(q_to_R(FP64, list(cam[3:7]))), cam[0:3].copy()

@@ -689,3 +689,69 @@ def make_sim3_ba(n_cams, n_points, obs_per_point, seed, sim3_edges=True, fix_sca
                pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
                omega_l=np.tile(np.eye(2).reshape(1, 4), (m, 1)), intrinsics=intr)
     return out
+
+
+def _sbacam_project(cams, X, vp, vl, intr, stereo):
+    """(proj [m][2|3], depth [m]) of points X[vl] in the cameras cams[vp], vectorised (the scalar statement is sbacam.py's)."""
+    from .g2o_io import _quat_to_R
+    R = _quat_to_R(cams[:, 3:7])[vp]
+    pc = np.einsum("mji,mj->mi", R, X[vl] - cams[vp, 0:3])             # R' (X - t)
+    k = intr[vp]
+    cols = [(k[:, 0] * pc[:, 0] + k[:, 2] * pc[:, 2]) / pc[:, 2], (k[:, 1] * pc[:, 1] + k[:, 3] * pc[:, 2]) / pc[:, 2]]
+    if stereo:
+        cols.append((k[:, 0] * (pc[:, 0] - k[:, 4]) + k[:, 2] * pc[:, 2]) / pc[:, 2])
+    return np.stack(cols, axis=1), pc[:, 2]
+
+
+def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_noise=0.2):
+    """Bundle adjustment in the reference's SBA format (BlockSolver_6_3): VertexCam cameras (camera-to-world, (tx, ty, tz, qx,
+    qy, qz, qw)) on a closed trajectory -- a circle of radius 4 with a vertical wave -- looking at the centre, observing
+    VertexSBAPointXYZ points of a ball of radius 1 around it through EdgeProjectP2MC (stereo=False, measurement (u, v)) or
+    EdgeProjectP2SC (stereo=True, (u, v, u_right)).  Every camera has intrinsics and a baseline of its own (fx != fy, non-zero
+    cx, cy, all different between cameras: SBACam::Kcam / baseline), so every observed depth is 2.5 ... 5.5 camera units (checked
+    for the true and the initial cameras).  Point j is observed by obs_per_point cameras spread over the trajectory, measurement
+    = its projection through the TRUE camera + pixel_noise * N(0, 1), information = identity (the .g2o format stores none:
+    types_sba.cpp:204-244).  Initial cameras: the true ones moved by 0.05 * N(0, 1) in t and a small quaternion 0.02 * N(0, 1)
+    through SBACam::update; initial points: the true ones + 0.02 * N(0, 1).  The first camera is fixed at its true pose.
+    Deterministic from seed.
+    Returns est [n_cams][7], est_true, points [L][3], points_true, hidx, pt_hidx, vp, vl, zl [m][2|3], omega_l [m][4|9],
+    intrinsics [n_cams][5] = (fx, fy, cx, cy, baseline), nP, nL, stereo."""
+    from . import sbacam as SB
+    from .g2o_io import _R_to_quat
+    from .sim3 import FP64 as F
+    if obs_per_point < 1 or obs_per_point > n_cams:
+        raise ValueError("make_sbacam_ba: 1 <= obs_per_point <= n_cams")
+    rng = CounterRng(seed + 1)
+    d = 3 if stereo else 2
+    ang = 2.0 * np.pi * np.arange(n_cams) / n_cams
+    centre = np.stack([4.0 * np.cos(ang), 4.0 * np.sin(ang), 0.5 * np.sin(2.0 * ang)], axis=1)
+    zc = -centre / np.linalg.norm(centre, axis=1, keepdims=True)       # the optical axis looks at the origin
+    xc = np.cross(zc, [0.0, 0.0, 1.0])
+    xc /= np.linalg.norm(xc, axis=1, keepdims=True)
+    yc = np.cross(zc, xc)
+    est_true = np.concatenate([centre, _R_to_quat(np.stack([xc, yc, zc], axis=2))], axis=1)   # camera-to-world: columns = the camera's axes
+    step = np.concatenate([0.05 * np.stack([rng.normal(60 + c, n_cams) for c in range(3)], axis=1),
+                           0.02 * np.stack([rng.normal(63 + c, n_cams) for c in range(3)], axis=1)], axis=1)
+    hidx = (np.arange(n_cams, dtype=np.int32) - 1).astype(np.int32)
+    nP = n_cams - 1
+    est = SB.update(F, est_true, hidx, step[1:].reshape(-1))
+    u = np.stack([rng.normal(40 + c, n_points) for c in range(3)], axis=1)
+    u /= np.maximum(np.linalg.norm(u, axis=1, keepdims=True), 1e-12)
+    pts_true = u * (rng.uniform(43, n_points) ** (1.0 / 3.0))[:, None]
+    pts = pts_true + 0.02 * np.stack([rng.normal(44 + c, n_points) for c in range(3)], axis=1)
+    k = np.arange(n_cams)
+    intr = np.stack([480.0 + 7.0 * k, 510.0 + 5.0 * k, 320.0 + 3.0 * k, 240.0 - 2.0 * k, 0.10 + 0.01 * k], axis=1)
+    stride = max(1, n_cams // obs_per_point)
+    start = np.minimum((rng.uniform(47, n_points) * n_cams).astype(np.int64), n_cams - 1)
+    vp = ((start[:, None] + stride * np.arange(obs_per_point)[None, :]) % n_cams).reshape(-1).astype(np.int32)
+    vl = np.repeat(np.arange(n_points, dtype=np.int32), obs_per_point)
+    m = len(vp)
+    zl = _sbacam_project(est_true, pts_true, vp, vl, intr, stereo)[0]
+    zl = zl + pixel_noise * np.stack([rng.normal(48 + c, m) for c in range(d)], axis=1)
+    for cams, X in ((est_true, pts_true), (est, pts)):
+        depth = _sbacam_project(cams, X, vp, vl, intr, stereo)[1]
+        if not ((depth >= 2.5) & (depth <= 5.5)).all():
+            raise ValueError("make_sbacam_ba: an observed depth outside 2.5 ... 5.5 camera units (%g ... %g)" % (depth.min(), depth.max()))
+    return dict(est=est, est_true=est_true, points=pts, points_true=pts_true, hidx=hidx,
+                pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
+                omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)), intrinsics=intr, nP=nP, nL=n_points, stereo=bool(stereo))
