@@ -263,7 +263,9 @@ int g2ohip_get_nnzb(g2ohip_solver* s, int which, int* nnzb);
 int g2ohip_get_pattern(g2ohip_solver* s, int which, int32_t* colptr, int32_t* rowidx);
 int g2ohip_copy_values(g2ohip_solver* s, int which, double* values_host);
 /* Device pointers + element counts of resident arrays (for multi-GPU exchange through RCCL):
- * which = G2OHIP_HSCHUR (values), or 100 = bschur. */
+ * which = G2OHIP_HSCHUR (values), or 100 = bschur.  For tests only, no part of the supported interface: 108 = the information
+ * matrices [n][3x3] of the bound GICP set as the last g2ohip_pg_linearize left them (G2OHIP_ERR_STATE without one; the pointer
+ * holds until the set is bound again) -- g2ohip_copy_edge_data returns no information matrices. */
 int g2ohip_device_array(g2ohip_solver* s, int which, double** ptr, size_t* count);
 /* BlockSolver::computeMarginals / LinearSolver::solvePattern (block_solver.hpp:489-498, linear_solver.h:63-69,
  * marginal_covariance_cholesky.cpp:71-220): blocks (rows[i], cols[i]) (pose block indices) of the inverse of Hpp
@@ -624,6 +626,39 @@ int g2ohip_pg_set_cam_project_edges(g2ohip_solver* s, int set, int type, const i
  * The kernel is timed under the "pg_landmark_linearize" slot. */
 int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const double* meas, const double* info,
                               const double* offset);
+/* ---- ... its GICP correspondences: scan-to-scan and multi-scan registration --------------------------------------------
+ * Type 15 = Edge_V_V_GICP over two VertexSE3 (g2o/types/icp/types_icp.h:167-244 computeError and the plane-to-plane
+ * information, types_icp.cpp:41-55 dRidx / dRidy / dRidz, types_icp.cpp:124-202 read and the analytic linearizeOplus that
+ * GICP_ANALYTIC_JACOBIANS selects).  ONE second pose-pose set of the same handle beside a type-2 set of g2ohip_pg_set_edges, in a
+ * slot of its own: independent of the landmark slot (types 4-6, do_schur 0 or 1) and of the prior slot; a later call replaces
+ * the binding.  The type-2 set may hold zero edges (a pure registration); its array pointers are non-null all the same.
+ *   e = X0^-1 (X1 pos1) - pos0, J0 = [-I | dRidx p1t, dRidy p1t, dRidz p1t], J1 = [R | R dRid{x,y,z}' pos1], R = R0' R1,
+ *   with respect to VertexSE3::oplusImpl; vertex 0 (vi) is the frame of pos0, vertex 1 (vj) the frame of pos1.
+ * Edge set `set` was added as a binary set with error_dim 3 and both vertex dimensions 6 over the poses' hessian indices (-1 =
+ * fixed); vi / vj index the pose table of g2ohip_pg_set_estimates.  Many edges on one vertex pair are the normal case, and a pair
+ * may appear in both orders.  meas [n][6] = (pos0, pos1); info [n][3x3] column-major is the point-to-plane information; cov ==
+ * NULL selects point-to-plane.  cov != NULL selects plane-to-plane (pl_pl = true): cov [n][18] = (cov0, cov1), 3x3 each, read by
+ * their upper triangles, and every g2ohip_pg_linearize -- the error-only one included -- rewrites the set's information to
+ * (cov0 + R cov1 R')^-1, so that g2ohip_chi2 and the robust weights see it as after the reference's computeError; info is then
+ * only the value the set holds before the first evaluation.  The normals are not passed: they serve to build info / cov
+ * (EdgeGICP::prec0 / cov0 / cov1, types_icp.h:90-158), which is host work (openslam_g2o_amd/gicp.py).
+ * Call after g2ohip_build_structure and g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).  G2OHIP_ERR_ARG: a pose set of type 1,
+ * 10 or 12, a set of other dimensions or a unary one, a set already bound in the pose-pose, landmark or prior slot, a null vi /
+ * vj / meas / info, an index outside the pose table, a hessian index that differs from the set's, a non-finite value, a cov0 or
+ * cov1 that is not symmetric positive definite (3x3 Cholesky on the host: cov0 + R cov1 R' is then invertible for every R) --
+ * validated before anything is committed.  While a GICP set is bound g2ohip_pg_set_edges refuses types 1, 10 and 12, and the
+ * landmark and prior entries refuse its set id.  (Of these, only type 12 on a zero-edge set is refused by the GICP rule alone:
+ * types 1 and 10 never fit a handle of pose dimension 6, and a set bound in one slot never has the dimensions of another --
+ * (6, 6, 6), (3, 6, 3), unary 6 and (3, 6, 6) -- so the set-id refusals name the cause and the dimension checks would refuse
+ * the same calls.)  g2ohip_pg_set_estimates with changed tables validates the set again; update /
+ * push / pop / discard_top are not concerned (the set owns no vertices); robust kernels as for any set; g2ohip_clear_edge_sets
+ * drops the binding; a GICP set grown by g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is
+ * bound again.  The assembly walks the edge list of one Hessian block with a fixed small group of lanes (one lane for an
+ * off-diagonal block), in edge order and without a cap on the list's length.
+ * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: VertexSCam / Edge_XYZ_VSC, more than one GICP set
+ * per handle, sharded solves, the g2o plugin adapter. */
+int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info,
+                             const double* cov);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -27,6 +27,7 @@ ERR_UNSUPPORTED = -4
 HPP, HPL, HLL, HSCHUR, DINV = 0, 1, 2, 3, 4
 PART_NO_VERTEX0, PART_NO_VERTEX1, PART_NO_CHI2 = 1, 2, 4      # g2ohip_set_edge_set_parts
 ARR_BSCHUR, ARR_X, ARR_B, ARR_EXCHANGE, ARR_XP, ARR_XBOUNDARY, ARR_XHALO, ARR_SCHUR_DIAG = 100, 101, 102, 103, 104, 105, 106, 107
+ARR_GICP_OMEGA = 108    # (tests only) information matrices [n][9] of the bound GICP set, rewritten by every plane-to-plane pgLinearize
 KERNEL_NONE, KERNEL_HUBER, KERNEL_PSEUDOHUBER, KERNEL_CAUCHY, KERNEL_SATURATED, KERNEL_DCS = 0, 1, 2, 3, 4, 5
 
 
@@ -61,7 +62,7 @@ EXPORTS = [
     "g2ohip_pg_push", "g2ohip_pg_pop", "g2ohip_pg_discard_top", "g2ohip_copy_edge_data",
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
-    "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges",
+    "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -169,6 +170,7 @@ def load():
     L.g2ohip_pg_set_sim3_project_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_cam_project_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_gicp_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_copy_edge_data.argtypes = [vp, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -538,6 +540,8 @@ class HipBlockSolver:
     def clearEdgeSets(self):
         _check(self.L.g2ohip_clear_edge_sets(self.h), "clearEdgeSets")
         self._set_sizes = {}
+        self.gicp_set = None                # (the library drops every front-end binding)
+        self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
     def updateStructure(self, new_poses, set_id=-1, v0=None, v1=None):
@@ -554,6 +558,9 @@ class HipBlockSolver:
         self.nP += int(new_poses)
         if n:
             self._set_sizes[set_id] += n
+            if set_id in getattr(self, "_pg_owner_sets", ()):     # growth of the pose-pose or landmark set drops the whole front end
+                self.gicp_set = None
+                self._pg_owner_sets = set()
         return True
 
     def setProfiling(self, on):
@@ -709,6 +716,13 @@ class HipBlockSolver:
             raise ValueError("pgSetEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
         _check(self.L.g2ohip_pg_set_edges(self.h, set_id, edge_type, _ip(vi), _ip(vj), _dp(meas), _dp(info)), "pgSetEdges")
         self._pg = (edge_type, stride)      # (a refused call leaves the previous binding, here as in the library)
+        self._note_pg_owner(set_id)
+
+    def _note_pg_owner(self, set_id):
+        """ids bound as the pose-pose or landmark set: growing one of them drops the front end's bindings (updateStructure)."""
+        if not hasattr(self, "_pg_owner_sets"):
+            self._pg_owner_sets = set()
+        self._pg_owner_sets.add(set_id)
 
     def pgSetSim3FixScale(self, fix_scale):
         """VertexSim3Expmap::_fix_scale for every vertex of an EdgeSim3 binding (default off)."""
@@ -755,6 +769,7 @@ class HipBlockSolver:
                 raise ValueError("pgSetLandmarkEdges: offset is an isometry [12] (R column-major | t)")
         _check(self.L.g2ohip_pg_set_landmark_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
                                                    None if off is None else _dp(off)), "pgSetLandmarkEdges")
+        self._note_pg_owner(set_id)
 
     def pgSetLandmarkCameraEdges(self, set_id, edge_type, pose_vertex, point_vertex, meas, info, offset, kcam):
         """Projective observations of point landmarks beside an EdgeSE3 pose set: edge_type 5 = EdgeSE3PointXYZDepth
@@ -774,6 +789,7 @@ class HipBlockSolver:
             raise ValueError("pgSetLandmarkCameraEdges: kcam is (fx, fy, cx, cy)")
         _check(self.L.g2ohip_pg_set_landmark_camera_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info),
                                                           None if off is None else _dp(off), _dp(kc)), "pgSetLandmarkCameraEdges")
+        self._note_pg_owner(set_id)
 
     def pgSetSim3ProjectEdges(self, set_id, pose_vertex, point_vertex, meas, info, intrinsics):
         """EdgeSim3ProjectXYZ (type 11) beside an EdgeSim3 pose set (type 10, possibly with zero edges): meas [n][2], info
@@ -788,6 +804,7 @@ class HipBlockSolver:
             raise ValueError("pgSetSim3ProjectEdges: intrinsics is [n_poses][4] = (fx, fy, cx, cy)")
         _check(self.L.g2ohip_pg_set_sim3_project_edges(self.h, set_id, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
                "pgSetSim3ProjectEdges")
+        self._note_pg_owner(set_id)
 
     def pgSetCamProjectEdges(self, set_id, edge_type, pose_vertex, point_vertex, meas, info, intrinsics):
         """SBA-format observations beside a VertexCam set (type 12, which holds zero edges): edge_type 13 = EdgeProjectP2MC
@@ -805,6 +822,7 @@ class HipBlockSolver:
             raise ValueError("pgSetCamProjectEdges: intrinsics is [n_cams][5] = (fx, fy, cx, cy, baseline)")
         _check(self.L.g2ohip_pg_set_cam_project_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
                "pgSetCamProjectEdges")
+        self._note_pg_owner(set_id)
 
     def pgSetPriorEdges(self, set_id, edge_type, pose_vertex, meas, info, offset=None):
         """Unary priors on poses: edge_type 7 = EdgeSE2Prior (meas [n][3]), 8 = EdgeSE2XYPrior ([n][2]) beside EdgeSE2,
@@ -823,6 +841,26 @@ class HipBlockSolver:
                 raise ValueError("pgSetPriorEdges: offset is an isometry [12] (R column-major | t)")
         _check(self.L.g2ohip_pg_set_prior_edges(self.h, set_id, edge_type, _ip(pv), _dp(meas), _dp(info),
                                                 None if off is None else _dp(off)), "pgSetPriorEdges")
+
+    gicp_set = None     # set id of the bound Edge_V_V_GICP set (pgSetGicpEdges)
+
+    def pgSetGicpEdges(self, set_id, vi, vj, meas, info, cov=None):
+        """Edge_V_V_GICP (type 15) as a second pose-pose set beside an EdgeSE3 pose set (type 2, possibly with zero edges): vi /
+        vj index the table of pgSetEstimates (vi: the frame of pos0, vj: the frame of pos1), meas [n][6] = (pos0, pos1), info
+        [n][3x3] the point-to-plane information.  cov None: point-to-plane.  cov [n][18] = (cov0, cov1): plane-to-plane, every
+        pgLinearize rewrites the set's information to (cov0 + R cov1 R')^-1.  The set is a binary one with error_dim 3
+        (addEdgeSet(3, hidx[vi], hidx[vj])).  After pgSetEdges."""
+        vi, vj, meas, info = _i32(vi), _i32(vj), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        if len(vi) != n or len(vj) != n or meas.size != n * 6 or info.size != n * 9:
+            raise ValueError("pgSetGicpEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        if cov is not None:
+            cov = _f64(cov)
+            if cov.size != n * 18:
+                raise ValueError("pgSetGicpEdges: cov is [n][18] = (cov0, cov1), 3x3 column-major each")
+        _check(self.L.g2ohip_pg_set_gicp_edges(self.h, set_id, _ip(vi), _ip(vj), _dp(meas), _dp(info),
+                                               None if cov is None else _dp(cov)), "pgSetGicpEdges")
+        self.gicp_set = set_id
 
     def pgSetLandmarkEstimates(self, points, hidx):
         """points [n][landmark_dim]; hidx[v] = the landmark's hessian index in the whole system (>= num_poses) or -1."""

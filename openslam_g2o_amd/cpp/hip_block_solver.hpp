@@ -122,6 +122,11 @@ class HipBlockSolver {
     return ok(g2ohip_pg_set_edges(h_, set, type, vi, vj, meas, info), "pgSetEdges");
   }
   bool pgSetSim3FixScale(bool fixScale) { return ok(g2ohip_pg_set_sim3_fix_scale(h_, fixScale ? 1 : 0), "pgSetSim3FixScale"); }
+  // GICP correspondences (g2ohip_pg_set_gicp_edges): type 15 = Edge_V_V_GICP, a second pose-pose set (error_dim 3) beside an
+  // EdgeSE3 one; meas [n][6] = (pos0, pos1), info [n][3x3]; cov nullptr = point-to-plane, [n][18] = (cov0, cov1) = plane-to-plane
+  bool pgSetGicpEdges(int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info, const double* cov) {
+    return ok(g2ohip_pg_set_gicp_edges(h_, set, vi, vj, meas, info, cov), "pgSetGicpEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

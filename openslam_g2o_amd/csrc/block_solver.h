@@ -102,6 +102,7 @@ class BlockSolver {
   void pg_set_cam_project_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                 const double* info, int n_cams, const double* intrinsics);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
+  void pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
   void pg_linearize(bool jacobians);
@@ -473,6 +474,14 @@ class BlockSolver {
     std::vector<int> h_vq;         // host copy: index validation (pg_validate_priors)
     DevBuf<double> pr_meas;
     double pr_offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    // ONE second pose-pose set `gicp_set` of Edge_V_V_GICP (type 15) beside a type-2 set, independent of the landmark and prior
+    // slots: gi / gj index `poses`, gicp_meas [n][6] = (pos0, pos1), gicp_cov [n][18] = (cov0, cov1) with gicp_plpl (plane-to-plane:
+    // pg_linearize rewrites the set's own_omega on every evaluation).  The set owns no vertices either.
+    int gicp_set = -1;
+    bool gicp_plpl = false;
+    DevBuf<int> gi, gj;
+    std::vector<int> h_gi, h_gj;   // host copies: index validation (pg_validate)
+    DevBuf<double> gicp_meas, gicp_cov;
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

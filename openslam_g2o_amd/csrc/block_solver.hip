@@ -2085,6 +2085,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_sim3.inc"
 #include "pg_sim3_project.inc"
 #include "pg_cam_project.inc"
+#include "pg_gicp.inc"
 #include "ba_stereo.inc"
 #undef PG_R
 
@@ -2343,7 +2344,8 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     es.external = false;
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
-    // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again)
+    // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
+    // (pg_set_gicp_edges again)
     if (set == pg_.set || set == pg_.lm_set) {
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -3043,7 +3045,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set;
+  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5458,6 +5460,9 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (type == 12 && (p_ != 6 || l_ != 3)) throw ArgFailure("pg_set_edges: the VertexCam table (12) needs a solver of (pose, landmark) dimensions (6, 3)");
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d) throw ArgFailure("pg_set_edges: the set must be a binary pose-pose set of matching dimension");
   const size_t n = (size_t)es.n, ms = (size_t)pg_pose_stride(type);
+  if (type != 2 && pg_.gicp_set >= 0)
+    throw ArgFailure("pg_set_edges: an Edge_V_V_GICP set (15) is bound: it stands beside an EdgeSE3 pose set (2) only");
+  if (set == pg_.gicp_set) throw ArgFailure("pg_set_edges: the set is bound as the GICP set");
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam is not on the device yet (it has no analytic Jacobian in the reference)");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
@@ -5530,6 +5535,7 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
       pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
                             pg_.points.n);
     if (pg_.pr_set >= 0) pg_validate_priors(*sets_[pg_.pr_set], pg_.h_vq.data(), pg_.h_vq.size(), hidx, nv);
+    if (pg_.gicp_set >= 0) pg_validate(*sets_[pg_.gicp_set], pg_.h_gi.data(), pg_.h_gj.data(), pg_.h_gi.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -5630,6 +5636,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   const std::string w(who);
   if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
   if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
+  if (set == pg_.gicp_set) throw ArgFailure(w + ": the set is bound as the GICP set");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -5684,6 +5691,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
       if (!std::isfinite(offset[i])) throw ArgFailure("pg_set_prior_edges: non-finite offset");
   if (set == pg_.set) throw ArgFailure("pg_set_prior_edges: the set is bound as the pose-pose set");
   if (set == pg_.lm_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the landmark set");
+  if (set == pg_.gicp_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the GICP set");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -5705,6 +5713,74 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   es.own_J0.alloc(n * d * dp);
   es.own_err.alloc(n * d);
   es.J0 = es.own_J0.p; es.J1 = nullptr; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ---- ... its GICP correspondences: Edge_V_V_GICP (type 15) as a second pose-pose set beside an EdgeSE3 one (pg_gicp.inc) -----
+namespace {
+// 3x3 column-major, read by its upper triangle: symmetric (lower triangle equal up to rounding) and positive definite (Cholesky)
+bool gicp_spd(const double* c) {
+  const double a = c[0], b = c[3], cc = c[6], d = c[4], e = c[7], f = c[8];
+  const double scale = std::max({std::fabs(a), std::fabs(d), std::fabs(f)});
+  if (std::fabs(c[1] - b) > 1e-12 * scale || std::fabs(c[2] - cc) > 1e-12 * scale || std::fabs(c[5] - e) > 1e-12 * scale) return false;
+  if (!(a > 0.0)) return false;
+  const double l00 = std::sqrt(a), l10 = b / l00, l20 = cc / l00;
+  const double s11 = d - l10 * l10;
+  if (!(s11 > 0.0)) return false;
+  const double l11 = std::sqrt(s11), l21 = (e - l20 * l10) / l11;
+  const double s22 = f - l20 * l20 - l21 * l21;
+  return s22 > 0.0;
+}
+}  // namespace
+
+void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_gicp_edges: call pg_set_edges first (the EdgeSE3 set the GICP set stands beside; it may be empty)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type != 2) throw ArgFailure("pg_set_gicp_edges: Edge_V_V_GICP (15) goes with an EdgeSE3 pose set (2)");
+  if (set == pg_.set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the pose-pose set");
+  if (set == pg_.lm_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the landmark set");
+  if (set == pg_.pr_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the prior set");
+  EdgeSet& es = *sets_[set];
+  if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
+    throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
+  if (!vi || !vj || !meas || !info) throw ArgFailure("pg_set_gicp_edges: null array");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0) throw ArgFailure("pg_set_gicp_edges: negative vertex index in edge " + std::to_string(k));
+    for (int i = 0; i < 6; ++i)
+      if (!std::isfinite(meas[6 * k + i])) throw ArgFailure("pg_set_gicp_edges: non-finite measurement in edge " + std::to_string(k));
+    for (int i = 0; i < 9; ++i)
+      if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_gicp_edges: non-finite information in edge " + std::to_string(k));
+    if (cov) {
+      for (int i = 0; i < 18; ++i)
+        if (!std::isfinite(cov[18 * k + i])) throw ArgFailure("pg_set_gicp_edges: non-finite covariance in edge " + std::to_string(k));
+      // (both positive definite: cov0 + R cov1 R' is then invertible for every rotation R)
+      if (!gicp_spd(cov + 18 * k) || !gicp_spd(cov + 18 * k + 9))
+        throw ArgFailure("pg_set_gicp_edges: cov0 / cov1 of edge " + std::to_string(k) + " is not symmetric positive definite");
+    }
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  pg_.gicp_set = set;
+  pg_.gicp_plpl = cov != nullptr;
+  pg_.h_gi.assign(vi, vi + n);
+  pg_.h_gj.assign(vj, vj + n);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.gi.upload(vi, n, st_);
+  pg_.gj.upload(vj, n, st_);
+  pg_.gicp_meas.upload(meas, n * 6, st_);
+  if (cov) pg_.gicp_cov.upload(cov, n * 18, st_);
+  es.own_omega.upload(info, n * 9, st_);
+  es.own_J0.alloc(n * 18);
+  es.own_J1.alloc(n * 18);
+  es.own_err.alloc(n * 3);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
   es.external = false;
   es.has_data = false;
   es.has_err = false;
@@ -5751,19 +5827,24 @@ void BlockSolver::pg_linearize(bool jacobians) {
   EdgeSet* ep = pg_.pr_set >= 0 ? sets_[pg_.pr_set].get() : nullptr;
   if (ep && (int)pg_.h_vq.size() != ep->n)
     throw StateFailure("pg_linearize: the prior edge set has grown since pg_set_prior_edges (g2ohip_update_structure): call pg_set_prior_edges again");
+  EdgeSet* eg = pg_.gicp_set >= 0 ? sets_[pg_.gicp_set].get() : nullptr;
+  if (eg && (int)pg_.h_gi.size() != eg->n)
+    throw StateFailure("pg_linearize: the GICP edge set has grown since pg_set_gicp_edges (g2ohip_update_structure): call pg_set_gicp_edges again");
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     if (jacobians) es.has_data = true;
     if (jacobians && el) el->has_data = true;
     if (jacobians && ep) ep->has_data = true;
+    if (jacobians && eg) eg->has_data = true;
     return;
   }
   pg_.err_valid = true;
   if (jacobians) pg_.jac_valid = true;
   chi2_valid_ = false;
+  // (a type-2 set may hold zero edges -- a pure registration, all constraints in the GICP set -- and then launches nothing)
   if (pg_.type == 1)
     hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  else if (pg_.type == 2)
+  else if (pg_.type == 2 && es.n > 0)
     hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
   else if (pg_.type == 10 && es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
@@ -5778,9 +5859,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
       prof.end(KernelProf::kPgSim3Jacobian, st_);
     }
   }
-  const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0;
+  const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch || pr_launch || gicp_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                        pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
@@ -5833,7 +5914,18 @@ void BlockSolver::pg_linearize(bool jacobians) {
         });
     });
   }
-  if (lm_launch || pr_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (gicp_launch) {   // Edge_V_V_GICP; plane-to-plane: the set's information is rewritten with every evaluation -- pg_gicp.inc
+    const dim3 grid(grid_for(eg->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      with_bool(pg_.gicp_plpl, [&](auto plpl) {
+        constexpr bool PLPL = plpl;
+        hipLaunchKernelGGL((pg_gicp_linearize_kernel<PLPL, STAGED>), grid, block, 0, st_, eg->n, pg_.poses.val.p, pg_.gi.p, pg_.gj.p,
+                           pg_.gicp_meas.p, pg_.gicp_cov.p, eg->own_J0.p, eg->own_J1.p, eg->own_err.p, eg->own_omega.p, jac);
+      });
+    });
+  }
+  if (lm_launch || pr_launch || gicp_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
@@ -5844,6 +5936,10 @@ void BlockSolver::pg_linearize(bool jacobians) {
   if (ep) {
     ep->has_err = true;
     if (jacobians) ep->has_data = true;
+  }
+  if (eg) {
+    eg->has_err = true;
+    if (jacobians) eg->has_data = true;
   }
 }
 
@@ -5975,6 +6071,11 @@ void BlockSolver::device_array(int which, double** ptr, size_t* count) {
     case 105: *ptr = ex_.merged ? ex_.tail : ex_.buf1.p; *count = (size_t)std::max(1, ex_.nbb * p_ * p_ + ex_.nbp * p_); break;   // exchange_setup buffers (what exchange_pack(1) fills)
     case 106: *ptr = ex_.buf3.p; *count = (size_t)ex_.nh * p_ + 1; break;
     case 107: *ptr = d_mf_diag.p; *count = mf_ready_ ? (size_t)nP_ * p_ * p_ : 0; break;   // schur_operator_prepare: diagonal blocks
+    case 108:   // the information matrices of the bound GICP set, [n][3x3]: what the last pg_linearize left there (pg_gicp.inc)
+      if (pg_.gicp_set < 0) throw StateFailure("device_array 108: no GICP set is bound (pg_set_gicp_edges)");
+      *ptr = sets_[pg_.gicp_set]->own_omega.p;
+      *count = pg_.h_gi.size() * 9;
+      break;
     default: throw ArgFailure("bad array selector");
   }
 }

@@ -693,6 +693,10 @@ int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t
                               const double* offset) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_prior_edges(set, type, pose_vertex, meas, info, offset); });
 }
+int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info,
+                             const double* cov) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_gicp_edges(set, vi, vj, meas, info, cov); });
+}
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_landmark_estimates(n_points, points, hidx); });
 }

@@ -61,8 +61,12 @@ def read_g2o(path):
     normalised as VertexCam::read does, cam_intrinsics [n][5] = (fx, fy, cx, cy, baseline), cam_point_ids, cam_points [L][3]
     (the VERTEX_XYZ lines, sorted by id), cam_vp / cam_vl (camera-table and point-table index of every EDGE_PROJECT_P2MC /
     EDGE_PROJECT_P2SC line), cam_zl [m][2|3], cam_stereo and cam_fixed_points (sbacam_ba_problem turns them into a problem
-    dict); a file that mixes the two edge tags raises ValueError."""
+    dict); a file that mixes the two edge tags raises ValueError.
+    A file with EDGE_V_V_GICP lines (i j pos0 normal0 pos1 normal1: Edge_V_V_GICP::read, g2o/types/icp/types_icp.cpp:124-160) over
+    VERTEX_SE3:QUAT also gives gicp_vi / gicp_vj (pose-table indices), gicp_meas [m][6] = (pos0, pos1) and gicp_normal0 /
+    gicp_normal1 [m][3] (gicp_problem turns them into a problem dict); a file without them gives none of these keys."""
     from . import sim3 as S3
+    g_i, g_j, g_vals = [], [], []
     sim3_extras = []
     spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
@@ -105,6 +109,10 @@ def read_g2o(path):
                 ej.append(int(t[2]))
                 meas.append(S3.sim3_inverse(S3.FP64, S3.sim3_exp(S3.FP64, [float(x) for x in t[3:10]])))
                 info.append(_upper_to_full([float(x) for x in t[10:38]], 7))
+            elif tag == "EDGE_V_V_GICP":
+                g_i.append(int(t[1]))
+                g_j.append(int(t[2]))
+                g_vals.append([float(x) for x in t[3:15]])
             elif tag == "VERTEX_CAM":
                 kind = kind or "sbacam"
                 vid.append(int(t[1]))
@@ -219,6 +227,11 @@ def read_g2o(path):
                    lm_param=np.asarray(lparam, np.int32), offsets=offsets, fixed_points=[plut[f] for f in fixed if f in plut])
         if cameras or any(k != "xyz" for k in lkind):
             out.update(lm_kind=lkind, cameras=cameras)
+    if g_i:
+        gv = np.asarray(g_vals, np.float64).reshape(-1, 12)
+        out.update(gicp_vi=np.asarray([lut[a] for a in g_i], np.int32), gicp_vj=np.asarray([lut[a] for a in g_j], np.int32),
+                   gicp_meas=np.concatenate([gv[:, 0:3], gv[:, 6:9]], axis=1), gicp_normal0=gv[:, 3:6].copy(),
+                   gicp_normal1=gv[:, 9:12].copy())
     if qv:
         out.update(pr_v=np.asarray([lut[a] for a in qv], np.int32), pr_kind=qkind, pr_meas=qmeas, pr_info=qinfo,
                    pr_param=np.asarray(qparam, np.int32), offsets=offsets)
@@ -330,6 +343,56 @@ def sbacam_ba_problem(rd, fixed_cams=None, fixed_points=None):
     return dict(est=rd["estimates"], hidx=hidx, nP=nP, nL=nL, points=rd["cam_points"], pt_hidx=pt_hidx, vp=rd["cam_vp"],
                 vl=rd["cam_vl"], zl=rd["cam_zl"], omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)),
                 intrinsics=rd["cam_intrinsics"], stereo=bool(rd["cam_stereo"]))
+
+
+def write_g2o_gicp(path, prob, ids=None):
+    """make_gicp-style problem -> `.g2o` text: VERTEX_SE3:QUAT lines, a FIX line for the poses of hessian index -1, the EdgeSE3
+    odometry as EDGE_SE3:QUAT and the correspondences as EDGE_V_V_GICP "i j pos0 normal0 pos1 normal1" (Edge_V_V_GICP::write,
+    g2o/types/icp/types_icp.cpp:206-226).  The format stores neither an information matrix nor the plane-to-plane switch: a read
+    builds R0' diag(.01, .01, 1) R0 from normal0, as Edge_V_V_GICP::read does.  %.17g: a read gives the written doubles back."""
+    T = np.asarray(prob["poses"], np.float64).reshape(-1, 12)
+    n = len(T)
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    qt = lambda A: np.concatenate([A[:, 9:12], _R_to_quat(A[:, 0:9].reshape(-1, 3, 3).transpose(0, 2, 1))], axis=1)
+    with open(path, "w") as f:
+        for k, v in enumerate(qt(T)):
+            f.write("VERTEX_SE3:QUAT %d %s\n" % (ids[k], fmt(v)))
+        fixed = [ids[k] for k in range(n) if prob["hidx"][k] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(int(i)) for i in fixed))
+        Z = np.asarray(prob["Z"], np.float64).reshape(-1, 12)
+        om = np.asarray(prob["omega"], np.float64).reshape(-1, 6, 6)
+        for e in range(len(Z)):
+            f.write("EDGE_SE3:QUAT %d %d %s %s\n" % (ids[prob["vi"][e]], ids[prob["vj"][e]], fmt(qt(Z[e:e + 1])[0]),
+                                                     fmt(om[e][i, j] for i in range(6) for j in range(i, 6))))
+        gm = np.asarray(prob["gmeas"], np.float64).reshape(-1, 6)
+        for e in range(len(gm)):
+            f.write("EDGE_V_V_GICP %d %d %s %s %s %s\n" % (ids[prob["gi"][e]], ids[prob["gj"][e]], fmt(gm[e, 0:3]),
+                                                           fmt(prob["normal0"][e]), fmt(gm[e, 3:6]), fmt(prob["normal1"][e])))
+
+
+def gicp_problem(rd, fixed=None, plane_to_plane=False, epsilon=0.01):
+    """read_g2o result of a VERTEX_SE3:QUAT file with EDGE_V_V_GICP lines -> the problem dict of lm.setup_device_gicp (the layout
+    of synthetic.make_gicp).  The information of every correspondence is what Edge_V_V_GICP::read builds, R0' diag(.01, .01, 1)
+    R0 with R0 = makeRot0 of normal0.  plane_to_plane: also gcov = (cov0(epsilon), cov1(epsilon)) of the two normals -- the switch
+    is no part of the file format.  fixed: indices into the pose table (default: the file's FIX lines; a file without any gets
+    pose 0 fixed as the gauge)."""
+    from . import gicp as G
+    if rd.get("kind") != "se3" or "gicp_vi" not in rd:
+        raise ValueError("gicp_problem: not a VERTEX_SE3:QUAT file with EDGE_V_V_GICP lines")
+    n = len(rd["estimates"])
+    fixed = (rd["fixed"] or [0]) if fixed is None else fixed
+    hidx, nP = hessian_index(n, fixed)
+    n0, n1 = rd["gicp_normal0"], rd["gicp_normal1"]
+    gcov = None
+    if plane_to_plane:
+        gcov = np.stack([np.concatenate([G.cov(a, epsilon).T.reshape(9), G.cov(b, epsilon).T.reshape(9)]) for a, b in zip(n0, n1)])
+    return dict(kind="se3", n=n, nP=nP, poses=_iso_from_qt(rd["estimates"]), hidx=hidx, vi=rd["vi"], vj=rd["vj"],
+                Z=_iso_from_qt(rd["meas"]) if len(rd["vi"]) else np.zeros((0, 12)),
+                omega=np.asarray(rd["info"], np.float64).reshape(-1, 36), gi=rd["gicp_vi"], gj=rd["gicp_vj"], gmeas=rd["gicp_meas"],
+                ginfo=np.stack([G.read_information(a).T.reshape(9) for a in n0]), gcov=gcov, normal0=n0, normal1=n1,
+                plane_to_plane=bool(plane_to_plane))
 
 
 def hessian_index(n_vertices, fixed):

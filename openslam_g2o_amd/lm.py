@@ -481,3 +481,29 @@ def setup_device_sbacam_ba(prob, huber_delta=0.0, schur=True, device=0, options=
     s.landmark_sets = (k0, k1)
     s.pose_set = k0
     return s, DevicePoseGraph(s)
+
+
+def setup_device_gicp(prob, huber_delta=0.0, device=0, options=None):
+    """HipBlockSolver for an openslam_g2o_amd.synthetic.make_gicp (or g2o_io.gicp_problem) graph: VertexSE3 scans joined by
+    Edge_V_V_GICP correspondences (gi, gj, gmeas, ginfo and -- plane-to-plane -- gcov) and, optionally, EdgeSE3 odometry (vi, vj,
+    Z, omega; empty arrays for a pure registration).  Poses, errors, the analytic Jacobians and the plane-to-plane information
+    stay on the device; BlockSolver_6_3 semantics without landmarks.  huber_delta > 0: Huber kernel on the GICP set.  Returns
+    (solver, DevicePoseGraph); solver.pose_set = the EdgeSE3 set's id, solver.gicp_set = the GICP set's."""
+    import numpy as np
+    from . import capi
+    s = capi.HipBlockSolver(6, 3, device)
+    for name, value in (options or {}).items():
+        s.setOption(name, value)
+    hidx = np.asarray(prob["hidx"], np.int32)
+    vi, vj = np.asarray(prob["vi"], np.int32), np.asarray(prob["vj"], np.int32)
+    gi, gj = np.asarray(prob["gi"], np.int32), np.asarray(prob["gj"], np.int32)
+    k0 = s.addEdgeSet(6, hidx[vi], hidx[vj])
+    k1 = s.addEdgeSet(3, hidx[gi], hidx[gj])
+    s.buildStructure(prob["nP"], 0, False)
+    s.pgSetEdges(k0, 2, vi, vj, np.asarray(prob["Z"], np.float64).reshape(-1, 12), np.asarray(prob["omega"], np.float64).reshape(-1, 36))
+    s.pgSetEstimates(prob["poses"], hidx)
+    s.pgSetGicpEdges(k1, gi, gj, prob["gmeas"], prob["ginfo"], prob.get("gcov"))
+    if huber_delta > 0:
+        s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    s.pose_set = k0
+    return s, DevicePoseGraph(s)

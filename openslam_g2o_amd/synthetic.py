@@ -755,3 +755,76 @@ def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_
     return dict(est=est, est_true=est_true, points=pts, points_true=pts_true, hidx=hidx,
                 pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
                 omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)), intrinsics=intr, nP=nP, nL=n_points, stereo=bool(stereo))
+
+
+_GICP_PLANES = np.array([[1.0, 0.1, 0.2, 6.0], [0.1, 0.5, 1.0, 2.5], [-0.3, 0.2, 1.0, 3.0], [-1.0, 0.3, 0.4, 5.0], [0.2, 0.6, -1.0, 2.0]])
+
+
+def make_gicp(n_scans, pts_per_pair, pairs=None, plane_to_plane=False, seed=0, odometry=True, noise_point=0.01, noise_normal=0.01,
+              perturb=(0.15, 0.06), epsilon=0.01):
+    """Scan registration with Edge_V_V_GICP between VertexSE3 (g2o/examples/icp/gicp_demo.cpp at more than two poses): n_scans
+    scans on a short trajectory (0.4 units and a few hundredths of a radian from scan to scan) see points on five planes; every
+    entry (a, b) of `pairs` (default: the consecutive scans) carries pts_per_pair correspondences: a world point on one of the
+    planes, its position in scan a (pos0) and in scan b (pos1), each + noise_point * N(0, 1), and the plane's unit normal in
+    either frame + noise_normal * N(0, 1), normalised.  Information = EdgeGICP::prec0(epsilon) of normal0 (what
+    Edge_V_V_GICP::read builds with epsilon = .01); plane_to_plane: cov = (cov0(epsilon), cov1(epsilon)) as well.  The normals
+    stay on the host.  Initial poses: the true ones multiplied from the right by a motion of perturb[0] * N(0, 1) in t and
+    the rotation vector perturb[1] * N(0, 1); scan 0 is fixed at its true pose.  odometry: type-2 EdgeSE3 edges
+    between consecutive scans (noise 0.05 / 0.02, information diag(400, ..., 2500, ...)); without them the arrays are empty and
+    the registration is held by the correspondences alone.  Deterministic from seed.
+    Returns kind = "se3", n, nP, poses [n][12], poses_true, hidx, vi, vj, Z, omega (odometry), gi, gj, gmeas [m][6], ginfo
+    [m][9], gcov [m][18] or None, normal0, normal1 [m][3], plane_to_plane."""
+    from . import gicp as G
+    if n_scans < 2 or pts_per_pair < 1:
+        raise ValueError("make_gicp: at least two scans and one correspondence per pair")
+    pairs = [(s, s + 1) for s in range(n_scans - 1)] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    if any(a == b or min(a, b) < 0 or max(a, b) >= n_scans for a, b in pairs):
+        raise ValueError("make_gicp: a pair is two different scans")
+    rng = CounterRng(seed + 1)
+    s = np.arange(n_scans)
+    t = np.stack([0.4 * s, 0.1 * np.sin(1.3 * s), 0.05 * np.cos(0.7 * s)], axis=1)
+    R = _exp_so3(np.stack([0.03 * np.sin(0.9 * s), 0.02 * s, 0.05 * np.cos(1.1 * s) - 0.05], axis=1))[0]
+    step = np.concatenate([perturb[0] * np.stack([rng.normal(10 + c, n_scans) for c in range(3)], axis=1),
+                           perturb[1] * np.stack([rng.normal(13 + c, n_scans) for c in range(3)], axis=1)], axis=1)
+    step[0] = 0.0
+    Re, te = R @ _exp_so3(step[:, 3:])[0], np.einsum("nij,nj->ni", R, step[:, :3]) + t
+    m = len(pairs) * pts_per_pair
+    gi = np.repeat(np.array([a for a, _ in pairs], np.int32), pts_per_pair)
+    gj = np.repeat(np.array([b for _, b in pairs], np.int32), pts_per_pair)
+    nrm = _GICP_PLANES[:, :3] / np.linalg.norm(_GICP_PLANES[:, :3], axis=1, keepdims=True)
+    pl = np.minimum((rng.uniform(20, m) * len(nrm)).astype(np.int64), len(nrm) - 1)
+    n_w = nrm[pl]
+    e1 = np.cross(n_w, [0.0, 1.0, 0.3])
+    e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+    e2 = np.cross(n_w, e1)
+    x_w = n_w * _GICP_PLANES[pl, 3:4] + e1 * (4.0 * rng.uniform(21, m) - 2.0)[:, None] + e2 * (4.0 * rng.uniform(22, m) - 2.0)[:, None]
+    Rt = R.transpose(0, 2, 1)
+
+    def seen(v, k0):
+        p = np.einsum("nij,nj->ni", Rt[v], x_w - t[v]) + noise_point * np.stack([rng.normal(k0 + c, m) for c in range(3)], axis=1)
+        nn = np.einsum("nij,nj->ni", Rt[v], n_w) + noise_normal * np.stack([rng.normal(k0 + 3 + c, m) for c in range(3)], axis=1)
+        return p, nn / np.linalg.norm(nn, axis=1, keepdims=True)
+    pos0, normal0 = seen(gi, 30)
+    pos1, normal1 = seen(gj, 40)
+    if max(np.abs(normal0[:, 1]).max(), np.abs(normal1[:, 1]).max()) > 0.95:
+        raise ValueError("make_gicp: a normal along (0, 1, 0), where EdgeGICP::makeRot0 is ill-conditioned")
+    ginfo = np.stack([G.prec(nv, epsilon).T.reshape(9) for nv in normal0])
+    gcov = None
+    if plane_to_plane:
+        gcov = np.stack([np.concatenate([G.cov(a, epsilon).T.reshape(9), G.cov(b, epsilon).T.reshape(9)]) for a, b in zip(normal0, normal1)])
+    if odometry:
+        vi, vj = np.arange(n_scans - 1, dtype=np.int32), np.arange(1, n_scans, dtype=np.int32)
+        ne = n_scans - 1
+        zq = 0.02 * np.stack([rng.normal(53 + c, ne) for c in range(3)], axis=1)
+        zq = np.concatenate([zq, np.sqrt(1.0 - (zq * zq).sum(axis=1))[:, None]], axis=1)
+        Rm = Rt[vi] @ R[vj] @ _quat_to_rot(zq)
+        tm = np.einsum("nij,nj->ni", Rt[vi], t[vj] - t[vi]) + 0.05 * np.stack([rng.normal(50 + c, ne) for c in range(3)], axis=1)
+        Z = _iso_pack(Rm, tm)
+        omega = np.tile(np.diag([400.0] * 3 + [2500.0] * 3).reshape(1, 36), (ne, 1))
+    else:
+        vi = vj = np.zeros(0, np.int32)
+        Z, omega = np.zeros((0, 12)), np.zeros((0, 36))
+    return dict(kind="se3", n=n_scans, nP=n_scans - 1, poses=_iso_pack(Re, te), poses_true=_iso_pack(R, t),
+                hidx=(np.arange(n_scans, dtype=np.int32) - 1).astype(np.int32), vi=vi, vj=vj, Z=Z, omega=omega, gi=gi, gj=gj,
+                gmeas=np.concatenate([pos0, pos1], axis=1), ginfo=ginfo, gcov=gcov, normal0=normal0, normal1=normal1,
+                plane_to_plane=bool(plane_to_plane), pairs=pairs)
