@@ -650,66 +650,190 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
     for (int r = 0; r < NR; ++r) cacc[r] = 0.0;
     const bool diag = ddiag[ld - td0] != 0;
     const int k0 = dptr[ld - td0] - e0, k1 = dptr[ld - td0 + 1] - e0;
+    // rhs contribution of a diagonal entry, B (Dinv b_l) = V (Sg C' b_l): this lane's rows Vr[rr + NR * c] of V_s
+    auto rhs_add = [&](const double (&Vr)[NR * LD], int lm) {
+#pragma unroll
+      for (int c = 0; c < LD; ++c) {
+        const double bv = bsm[lm * LD + c];
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) cacc[rr] += Vr[rr + NR * c] * bv;
+      }
+    };
     // (the entry word of the NEXT iteration is requested one iteration ahead: entry -> slot addresses -> blocks is a chain of two
     // LDS round trips per iteration otherwise; reading past the list ends inside the tile's own LDS tables and is never used)
     int pk_next = ep[k0 + ge];
-    for (int k = k0 + ge; k < k1; k += GE) {
-      const int pk = pk_next, lm = el[k];
-      pk_next = ep[k + GE];
-      const int s1 = pk & 0xffff, s2 = (pk >> 16) & 0xffff;
-      double W[NR * LD];   // W[rr + NR * c] = V_s1(gc*NR + rr, c)   (V = B C: schur_tile_prepare)
+    // A diagonal destination sums V_s V_s' (s1 == s2): symmetric, and element (r, c) runs the very chain of fused multiply-adds of
+    // element (c, r) with the factors commuted -- the same bits.  Where EVERY active lane group of the wave holds a diagonal
+    // destination in this round (a wave vote: the branch is uniform, a divergent one would issue both bodies) only one triangle
+    // is accumulated, the block is read from LDS once, and the full block is rebuilt once per destination after the sum over
+    // the entry parts.  Same summation order per element as the general body below: the stored block does not change.
+    // (A tile with a landmark block that is not positive definite takes the general body: Sg = diag(+-1) keeps the products
+    // exactly symmetric, but the scaled and the plain copy of the rows would both have to stay in registers.)
+    // The triangle body reads slot s1 alone: EVERY entry of a diagonal destination has s1 == s2, because a landmark has one Hpl
+    // block per pose (its rows in pl_row are unique) and a tile over two different chunks of a split landmark pairs different poses
+    // (build_structure).  A planner that ever emits a diagonal entry with s1 != s2 must clear the destination's flag in td_diag.
+    if (!neg && __ballot(!diag) == 0) {
+      constexpr int NS = NR * (NR + 1) / 2;   // T[rr (rr + 1) / 2 + cc], cc <= rr
       typedef VSlot<PD, LD, GC> VS;
-      if constexpr (VS::PERM) {   // this lane's half: eight doubles 16-byte aligned, the ninth next to them (VSlot)
-        const double* sp = Bs + s1 * PL;
-        double h8[8];
-        lds_block<8>(sp + (gc ? 10 : 0), h8);
+      if constexpr (GC == 1) {
+        double T[NS];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) W[i] = h8[i];
-        W[8] = sp[gc ? 9 : 8];
+        for (int i = 0; i < NS; ++i) T[i] = 0.0;
+        for (int k = k0 + ge; k < k1; k += GE) {
+          const int pk = pk_next, lm = el[k];
+          pk_next = ep[k + GE];
+          double V[PL];
+          lds_block<PL>(Bs + (pk & 0xffff) * PL, V);
+          rhs_add(V, lm);   // (GC = 1: VSlot::off(rr, c) = rr + NR * c)
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr)
+#pragma unroll
+            for (int cc = 0; cc <= rr; ++cc) {
+              double v = T[rr * (rr + 1) / 2 + cc];
+#pragma unroll
+              for (int kk = 0; kk < LD; ++kk) v = fma(V[VS::off(rr, kk)], V[VS::off(cc, kk)], v);
+              T[rr * (rr + 1) / 2 + cc] = v;
+            }
+        }
+        if (GE > 1) {
+#pragma unroll
+          for (int i = 0; i < NS; ++i) T[i] = ge_sum(T[i]);
+        }
+#pragma unroll
+        for (int c = 0; c < PD; ++c)
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr) acc[rr + NR * c] = rr >= c ? T[rr * (rr + 1) / 2 + c] : T[c * (c + 1) / 2 + rr];
       } else {
-        const double* B1p = Bs + s1 * PL + gc * NR;
+        // Row halves: this lane's rows W, the other half's rows O.  T = W W' (the lane's own diagonal sub-block, lower triangle) and
+        // X = W O' (the off-diagonal sub-block, elements rr >= cc: its other elements are the partner lane's X, transposed) --
+        // NR (NR + 1) of the NR * PD elements, the same instructions on both kinds of lanes.
+        double T[NS], X[NS];
 #pragma unroll
-        for (int kk = 0; kk < LD; ++kk)
+        for (int i = 0; i < NS; ++i) T[i] = X[i] = 0.0;
+        for (int k = k0 + ge; k < k1; k += GE) {
+          const int pk = pk_next, lm = el[k];
+          pk_next = ep[k + GE];
+          const double* sp = Bs + (pk & 0xffff) * PL;
+          double W[NR * LD], O[NR * LD];   // [rr + NR * kk]
+          if constexpr (VS::PERM) {
+            double h8[8];
+            lds_block<8>(sp + (gc ? 10 : 0), h8);
 #pragma unroll
-          for (int rr = 0; rr < NR; ++rr) W[rr + NR * kk] = B1p[rr + PD * kk];
-      }
-      if (diag) {   // s1 == s2: rhs contribution B (Dinv b_l) = V (Sg C' b_l), this lane's rows
+            for (int i = 0; i < 8; ++i) W[i] = h8[i];
+            W[8] = sp[gc ? 9 : 8];
+            lds_block<8>(sp + (gc ? 0 : 10), h8);
 #pragma unroll
-        for (int c = 0; c < LD; ++c) {
-          const double bv = bsm[lm * LD + c];
+            for (int i = 0; i < 8; ++i) O[i] = h8[i];
+            O[8] = sp[gc ? 8 : 9];
+          } else {
 #pragma unroll
-          for (int rr = 0; rr < NR; ++rr) cacc[rr] += W[rr + NR * c] * bv;
+            for (int kk = 0; kk < LD; ++kk)
+#pragma unroll
+              for (int rr = 0; rr < NR; ++rr) {
+                W[rr + NR * kk] = sp[gc * NR + rr + PD * kk];
+                O[rr + NR * kk] = sp[(1 - gc) * NR + rr + PD * kk];
+              }
+          }
+          rhs_add(W, lm);
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr)
+#pragma unroll
+            for (int cc = 0; cc <= rr; ++cc) {
+              double v = T[rr * (rr + 1) / 2 + cc], x = X[rr * (rr + 1) / 2 + cc];
+#pragma unroll
+              for (int kk = 0; kk < LD; ++kk) {
+                v = fma(W[rr + NR * kk], W[cc + NR * kk], v);
+                x = fma(W[rr + NR * kk], O[cc + NR * kk], x);
+              }
+              T[rr * (rr + 1) / 2 + cc] = v;
+              X[rr * (rr + 1) / 2 + cc] = x;
+            }
         }
-      }
-      if (neg) {   // (tile with a landmark block that is not positive definite: V_s1 Sg)
-        constexpr int CP = TileSplit<LD>::CP;
+        if (GE > 1) {
 #pragma unroll
-        for (int c = 0; c < LD; ++c) {
-          const double sv = Cs[lm * CP + LD * LD + c];
-#pragma unroll
-          for (int rr = 0; rr < NR; ++rr) W[rr + NR * c] *= sv;
+          for (int i = 0; i < NS; ++i) {
+            T[i] = ge_sum(T[i]);
+            X[i] = ge_sum(X[i]);
+          }
         }
+        // the partner lane (other row half, same entry part) holds the elements above the diagonal of this lane's off-diagonal
+        // sub-block; the sub-block of the first NR columns is the own one for gc = 0 and the off-diagonal one for gc = 1
+        auto gc_partner = [](double v) {
+          if (PAIR12) return dpp_permute<0x140>(dpp_permute<0x1B>(v));   // lane ^ 12 = (lane ^ 3) ^ 15
+          if (QUAD) return dpp_permute<0x4E>(v);                          // GE == 2: gc is lane bit 1
+          return dpp_permute<0xB1>(v);                                    // gc is the low lane bit
+        };
+        double Xp[NS];
+#pragma unroll
+        for (int rr = 1; rr < NR; ++rr)
+#pragma unroll
+          for (int cc = 0; cc < rr; ++cc) Xp[rr * (rr + 1) / 2 + cc] = gc_partner(X[rr * (rr + 1) / 2 + cc]);
+#pragma unroll
+        for (int cc = 0; cc < NR; ++cc)
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr) {
+            const double own = rr >= cc ? T[rr * (rr + 1) / 2 + cc] : T[cc * (cc + 1) / 2 + rr];
+            const double off = rr >= cc ? X[rr * (rr + 1) / 2 + cc] : Xp[cc * (cc + 1) / 2 + rr];
+            acc[rr + NR * cc] = gc ? off : own;
+            acc[rr + NR * (NR + cc)] = gc ? own : off;
+          }
       }
-      // this lane's rows of W * B_s2'
-      double B2[PL];
-      lds_block<PL>(Bs + s2 * PL, B2);
-      // (accumulated term by term: three fused multiply-adds per element and entry, no separate add -- the kernel is bound by
-      // instruction issue)
+      if (GE > 1) {
 #pragma unroll
-      for (int c = 0; c < PD; ++c)
+        for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
+      }
+    } else {
+      for (int k = k0 + ge; k < k1; k += GE) {
+        const int pk = pk_next, lm = el[k];
+        pk_next = ep[k + GE];
+        const int s1 = pk & 0xffff, s2 = (pk >> 16) & 0xffff;
+        double W[NR * LD];   // W[rr + NR * c] = V_s1(gc*NR + rr, c)   (V = B C: schur_tile_prepare)
+        typedef VSlot<PD, LD, GC> VS;
+        if constexpr (VS::PERM) {   // this lane's half: eight doubles 16-byte aligned, the ninth next to them (VSlot)
+          const double* sp = Bs + s1 * PL;
+          double h8[8];
+          lds_block<8>(sp + (gc ? 10 : 0), h8);
 #pragma unroll
-        for (int rr = 0; rr < NR; ++rr) {
-          double v = acc[rr + NR * c];
+          for (int i = 0; i < 8; ++i) W[i] = h8[i];
+          W[8] = sp[gc ? 9 : 8];
+        } else {
+          const double* B1p = Bs + s1 * PL + gc * NR;
 #pragma unroll
-          for (int kk = 0; kk < LD; ++kk) v = fma(W[rr + NR * kk], B2[VS::off(c, kk)], v);
-          acc[rr + NR * c] = v;
+          for (int kk = 0; kk < LD; ++kk)
+#pragma unroll
+            for (int rr = 0; rr < NR; ++rr) W[rr + NR * kk] = B1p[rr + PD * kk];
         }
-    }
-    if (GE > 1) {   // lanes with the same gc are GC apart
+        if (diag) rhs_add(W, lm);   // s1 == s2
+        if (neg) {   // (tile with a landmark block that is not positive definite: V_s1 Sg)
+          constexpr int CP = TileSplit<LD>::CP;
 #pragma unroll
-      for (int i = 0; i < NR * PD; ++i) acc[i] = ge_sum(acc[i]);
+          for (int c = 0; c < LD; ++c) {
+            const double sv = Cs[lm * CP + LD * LD + c];
 #pragma unroll
-      for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
+            for (int rr = 0; rr < NR; ++rr) W[rr + NR * c] *= sv;
+          }
+        }
+        // this lane's rows of W * B_s2'
+        double B2[PL];
+        lds_block<PL>(Bs + s2 * PL, B2);
+        // (accumulated term by term: three fused multiply-adds per element and entry, no separate add -- the kernel is bound by
+        // instruction issue)
+#pragma unroll
+        for (int c = 0; c < PD; ++c)
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr) {
+            double v = acc[rr + NR * c];
+#pragma unroll
+            for (int kk = 0; kk < LD; ++kk) v = fma(W[rr + NR * kk], B2[VS::off(c, kk)], v);
+            acc[rr + NR * c] = v;
+          }
+      }
+      if (GE > 1) {   // lanes with the same gc are GC apart
+#pragma unroll
+        for (int i = 0; i < NR * PD; ++i) acc[i] = ge_sum(acc[i]);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
+      }
     }
     double* out = Pd + (size_t)ld * PD * PD + gc * NR * PD;
     if constexpr ((NR * PD) % 2 == 0) {   // 16-byte pieces, dealt round-robin to the GE lanes (all hold the sum)
@@ -2816,27 +2940,44 @@ void BlockSolver::build_structure(int nP, int nL, bool do_schur) {
           }
         }
       }, 8);
-      {
-        size_t ntd = 0, nte = 0;
-        for (const TileOut& o : outs) {
-          ntd += o.dest.size();
-          nte += o.pack.size();
-        }
-        td_dest.reserve(ntd);
-        td_ptr.reserve(ntd + 1);
-        te_pack.reserve(nte);
-        te_lm.reserve(nte);
+      size_t ntd = 0, nte = 0;
+      for (const TileOut& o : outs) {
+        ntd += o.dest.size();
+        nte += o.pack.size();
       }
+      td_dest.reserve(ntd);
+      td_ptr.reserve(ntd + 1);
+      te_pack.reserve(nte);
+      te_lm.reserve(nte);
+      // Inside a round of the destination loop (one destination per lane group of the workgroup) the diagonal destinations go
+      // first, each kind still longest first: a wave takes the triangle-only body of schur_tile_dests only where all its lane
+      // groups hold diagonal destinations, and with the plain order every wave of a round gets a few of each kind.  A
+      // permutation of a tile's destinations: the slots of a destination stay in tile order and its entries in their order.
+      // The round width is the one of the lane-group width pick_group gives for these tables.  A launch that maps it to another
+      // width (edge classes: with_lane_group<1, 8> turns 4 into a neighbour) has rounds of another size: the vote is taken on what
+      // the wave really holds, so results are the same, but fewer waves are all-diagonal there.
+      const int round_groups = kThreads / pick_group((double)nte / std::max<size_t>(1, ntd));   // (the width solve_schur_impl picks)
+      std::vector<int> run_order, run_first;
       for (size_t ti = 0; ti < descs.size(); ++ti) {
         const TileDesc& td = descs[ti];
         TileOut& o = outs[ti];
-        for (size_t r = 0; r < o.dest.size(); ++r) {
+        const int nruns = (int)o.dest.size();
+        run_order.clear();
+        run_first.assign(nruns + 1, 0);
+        for (int r = 0; r < nruns; ++r) run_first[r + 1] = run_first[r] + o.cnt[r];
+        for (int r0 = 0; r0 < nruns; r0 += round_groups) {
+          const int r1 = std::min(nruns, r0 + round_groups);
+          for (int want = 1; want >= 0; --want)
+            for (int r = r0; r < r1; ++r)
+              if (hs_row_is_diag[o.dest[r]] == want) run_order.push_back(r);
+        }
+        for (int r : run_order) {
           td_dest.push_back(o.dest[r]);
           rd_cnt[o.dest[r]]++;
           td_ptr.push_back(td_ptr.back() + o.cnt[r]);
+          te_pack.insert(te_pack.end(), o.pack.begin() + run_first[r], o.pack.begin() + run_first[r + 1]);
+          te_lm.insert(te_lm.end(), o.lml.begin() + run_first[r], o.lml.begin() + run_first[r + 1]);
         }
-        te_pack.insert(te_pack.end(), o.pack.begin(), o.pack.end());
-        te_lm.insert(te_lm.end(), o.lml.begin(), o.lml.end());
         t_l0.push_back(td.l0); t_l1.push_back(td.l1); t_q0.push_back(td.q0); t_ns.push_back(td.ns); t_q1.push_back(td.q1); t_n1.push_back(td.n1);
         tile_td0.push_back((int)td_dest.size());
         std::vector<int>().swap(o.dest);   // (release as we go)
