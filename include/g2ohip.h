@@ -434,6 +434,31 @@ int g2ohip_ba_set_edges_classes(g2ohip_solver* s, int set, const int32_t* cam_ve
  * and use_graph work as for any generic set.  Everything below (set_estimates ... discard_top) acts on it unchanged. */
 int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_vertex, const int32_t* point_vertex, const double* meas,
                                const double* info, double focal_length, double cx, double cy, double baseline);
+/* A SECOND slot beside the projection slot: ONE set of pose-pose constraints between cameras, EdgeSE3Expmap (tag EDGE_SE3:EXPMAP,
+ * g2o/types/sba/types_six_dof_expmap.h:111-130: odometry, loop closures, the terms that tie a local window to the rest of the map).
+ * Vertex 0 of an edge is Ti = cams[vi[k]], vertex 1 is Tj = cams[vj[k]] (indices into the camera table of g2ohip_ba_set_estimates,
+ * fixed cameras included); meas [n][12] = the measurement C as an isometry, R column-major | t, like a camera; information
+ * [n][6x6] column-major (NULL = identity, written on the device).  Error e = log(Tj^-1 C Ti) in the order (omega, upsilon), log as
+ * SE3Quat::log is written (g2o/types/slam3d/se3quat.h:178-215, its branch at d > 0.99999 included; like the reference no guard near
+ * a relative rotation of pi or for a trace outside [-1, 3]).  Jacobians as EdgeSE3Expmap::linearizeOplus
+ * (types_six_dof_expmap.cpp:271-286): J0 = adj(Tj^-1 C), J1 = -adj(Ti^-1 C^-1), adj as se3quat.h:259-268 -- the reference's ADJOINT
+ * FORM, which is the derivative of the error at e = 0 only, not the derivative of the logarithm.
+ * Edge set `set` was added as a binary set with error_dim 6 and both vertex dimensions 6 on a (6, 3) solver, and is not the set of
+ * the projection slot.  After g2ohip_build_structure AND after g2ohip_ba_set_edges* / g2ohip_ba_set_stereo_edges (otherwise
+ * G2OHIP_ERR_STATE; so is a set that carries per-edge robust kernels at the binding -- set them on the bound set).  Null vi / vj /
+ * meas, non-finite values, indices outside the camera table, cam_hidx[vi[k]] / cam_hidx[vj[k]] that differ from the set's vertex
+ * 0 / 1 (-1 = fixed), a set of another shape or the projection set itself: G2OHIP_ERR_ARG.  A rejected call leaves the previous
+ * binding usable.  Many edges on one pair and a pair in both orders are legal, and so are zero edges.  A later call replaces the
+ * binding (a call that binds another set leaves the set that was bound without edge data: g2ohip_build_system returns
+ * G2OHIP_ERR_STATE until g2ohip_set_edge_data feeds it, unless it is empty), a later g2ohip_ba_set_edges* / g2ohip_ba_set_stereo_edges keeps it, g2ohip_ba_set_estimates with changed tables validates
+ * it again, g2ohip_clear_edge_sets drops it; after g2ohip_update_structure has grown the set g2ohip_ba_linearize returns
+ * G2OHIP_ERR_STATE until it is bound again (a guard: today g2ohip_update_structure refuses every structure that can hold a
+ * projection binding -- it needs a landmark in the structure).  g2ohip_ba_linearize writes the set's errors (and, with jacobians = 1, its Jacobians,
+ * on the fused path of the projection set too); chi2 and robust weights go the generic way (g2ohip_set_robust_kernel(_per_edge) on
+ * the set); the fused assembly and back-substitution of the projection set stay in place, since the set touches no landmark.
+ * NOT covered: the g2o plugin adapter (EdgeSE3Expmap stays on its host path there), a pose set without a projection set (a pure
+ * VertexSE3Expmap pose graph), more than one pose set per handle, EdgeProjectPSI2UV, sharded solves, fused kernels for the set. */
+int g2ohip_ba_set_pose_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info);
 /* setEstimate for every vertex + the index mapping: cam_hidx[v] = hessianIndex (-1 fixed),
  * point_hidx[v] = landmark index (0-based, i.e. hessianIndex - num_poses) or -1. */
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,

@@ -92,6 +92,12 @@ class HipBlockSolver {
                         double focalLength, double cx, double cy, double baseline) {
     return ok(g2ohip_ba_set_stereo_edges(h_, set, camVertex, pointVertex, meas, info, focalLength, cx, cy, baseline), "baSetStereoEdges");
   }
+  // EdgeSE3Expmap constraints between two cameras in the second slot of the device-resident BA front end (g2ohip_ba_set_pose_edges,
+  // after baSetStereoEdges / g2ohip_ba_set_edges): `set` was added as a binary set with errorDim 6 over two 6-dof poses; vi / vj index
+  // the camera table (vertex 0 / vertex 1), meas [n][12] = the measurement as an isometry, info [n][6x6] or nullptr (identity)
+  bool baSetPoseEdges(int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
+    return ok(g2ohip_ba_set_pose_edges(h_, set, vi, vj, meas, info), "baSetPoseEdges");
+  }
   // EdgeSE3PointXYZDepth (type 5) / EdgeSE3PointXYZDisparity (type 6) observations with one ParameterCamera, kept on the device
   // beside an EdgeSE3 pose set of g2ohip_pg_set_edges (handle()): offset isometry [12] or nullptr, kcam = fx, fy, cx, cy
   bool pgSetLandmarkCameraEdges(int set, int type, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas,

@@ -141,6 +141,8 @@ class BlockSolver {
   // the same slot bound to a set of stereo observations (EdgeProjectXYZ2UVU, error (u_left, v_left, u_right)): ba_stereo.inc
   void ba_set_stereo_edges(int set, const int* cam_vertex, const int* point_vertex, const double* meas, const double* info, double f,
                            double cx, double cy, double baseline);
+  // a second slot beside it: one set of EdgeSE3Expmap constraints between two cameras (ba_pose_edge.inc); info == nullptr: identity
+  void ba_set_pose_edges(int set, const int* vi, const int* vj, const double* meas, const double* info);
   void ba_set_estimates(int n_cams, const double* cams, const int* cam_hidx, int n_points, const double* points, const int* point_hidx);
   void ba_get_estimates(double* cams, double* points);
   void ba_get_estimates_of(int n_cams, const int* cam_idx, double* cams, int n_points, const int* point_idx, double* points);   // selected vertices
@@ -428,6 +430,15 @@ class BlockSolver {
     DevBuf<double> sel_out;
     bool ll_slots_ok = false;
     bool has_backup = false;
+    // ONE binary set of EdgeSE3Expmap constraints `pose_set` between two cameras beside the projection slot (ba_set_pose_edges,
+    // ba_pose_edge.inc): pvi / pvj index `cams` (vertex 0 / vertex 1), pose_meas [n][12] = the measurement as an isometry.  The
+    // set owns no vertices: ba_linearize fills its own_J0 / own_J1 / own_err, nothing else knows of it.  Its Jacobians are
+    // needed whenever Jacobians are asked for, on the fused path too (jac_valid speaks of the projection set alone).
+    int pose_set = -1;
+    DevBuf<int> pvi, pvj;
+    std::vector<int> h_pvi, h_pvj;   // host copies: index validation (pg_validate)
+    DevBuf<double> pose_meas;
+    bool pose_jac_valid = false;
   } ba_;
   // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks

@@ -2211,6 +2211,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_cam_project.inc"
 #include "pg_gicp.inc"
 #include "ba_stereo.inc"
+#include "ba_pose_edge.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -3186,7 +3187,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set;
+  const bool front_end_set = set == ba_.set || set == ba_.pose_set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -3248,7 +3249,7 @@ void BlockSolver::set_robust_kernel_per_edge(int set, const int* kind, const dou
 void BlockSolver::invalidate_graphs() {
   // (called by every setter that changes what the kernels read: also drops the cached evaluations)
   chi2_valid_ = false;
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   pg_.err_valid = pg_.jac_valid = false;
   drop_graph_segments();
 }
@@ -5029,7 +5030,7 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
   ba_.h_cam_v.assign(cam_vertex, cam_vertex + n);
   ba_.h_pt_v.assign(point_vertex, point_vertex + n);
   if (n_classes > 1) cam_vertex = camc.data();   // (validated plain; from here on the indices carry the class)
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   chi2_valid_ = false;
   es.has_err = false;      // errors of the previous edge data are gone
   ba_.cam_v.upload(cam_vertex, n, st_);
@@ -5231,7 +5232,7 @@ void BlockSolver::ba_set_stereo_edges(int set, const int* cam_vertex, const int*
   ba_.ctab.release();
   ba_.h_cam_v.assign(cam_vertex, cam_vertex + n);
   ba_.h_pt_v.assign(point_vertex, point_vertex + n);
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   chi2_valid_ = false;
   ba_.sys_version = -1;
   ba_.fused_ok = false;
@@ -5256,6 +5257,66 @@ void BlockSolver::ba_set_stereo_edges(int set, const int* cam_vertex, const int*
   es.own_J0.alloc(n * 9);
   es.own_J1.alloc(n * 18);
   es.own_err.alloc(n * 3);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;   // becomes valid with the first ba_linearize
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipGetLastError());
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ---- ... and, beside the projection slot, ONE set of pose-pose constraints: EdgeSE3Expmap (ba_pose_edge.inc) --------------------
+// A binary set (error 6, both vertices 6-dof cameras) that owns no vertices: ba_linearize writes its J0 / J1 / err next to the
+// projection producer, the generic assembly, chi2 and robust kernels take over, and ba_recompute_ok() keeps the fused path of the
+// projection set (the set touches no landmark).  Bound after the projection slot; a later ba_set_edges* / ba_set_stereo_edges
+// keeps it, ba_set_estimates with new tables validates it again, clear_edge_sets drops it, a set grown by update_structure is
+// refused by its edge count until it is bound again (a guard only: update_structure refuses structures with landmarks, and without a
+// landmark in the structure no projection set has a 3-dof vertex 0, so no projection binding exists to stand beside).  A call
+// that binds ANOTHER set takes the data of the set that leaves the slot with it.  Validate, then commit.
+void BlockSolver::ba_set_pose_edges(int set, const int* vi, const int* vj, const double* meas, const double* info) {
+  invalidate_graphs();
+  require_structure();
+  if (ba_.set < 0) throw StateFailure("ba_set_pose_edges: call ba_set_edges / ba_set_stereo_edges first (the projection set the pose set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (set == ba_.set) throw ArgFailure("ba_set_pose_edges: the set is bound as the projection set");
+  EdgeSet& es = *sets_[set];
+  if (es.unary || es.d != 6 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6 || l_ != 3)
+    throw ArgFailure("ba_set_pose_edges: the set must be EdgeSE3Expmap-shaped (binary, d=6, both vertices 6-dof poses) on a (6, 3) solver");
+  if (!vi || !vj || !meas) throw ArgFailure("ba_set_pose_edges: null array");
+  if (es.rk.p)   // (the rule of ba_set_edges)
+    throw StateFailure("ba_set_pose_edges: the set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound set");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0) throw ArgFailure("ba_set_pose_edges: negative vertex index in edge " + std::to_string(k));
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(meas[12 * k + i])) throw ArgFailure("ba_set_pose_edges: non-finite measurement in edge " + std::to_string(k));
+    if (info)
+      for (int i = 0; i < 36; ++i)
+        if (!std::isfinite(info[36 * k + i])) throw ArgFailure("ba_set_pose_edges: non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate(es, vi, vj, n, ba_.cams.h_hidx.data(), ba_.cams.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  if (ba_.pose_set >= 0 && ba_.pose_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its
+    EdgeSet& old = *sets_[ba_.pose_set];            // next source (build_system refuses it until then, unless it is empty)
+    old.has_data = old.has_err = false;
+  }
+  ba_.pose_set = set;
+  ba_.h_pvi.assign(vi, vi + n);
+  ba_.h_pvj.assign(vj, vj + n);
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  ba_.pvi.upload(vi, n, st_);
+  ba_.pvj.upload(vj, n, st_);
+  ba_.pose_meas.upload(meas, n * 12, st_);
+  if (!info) {   // information().setIdentity(), written on the device
+    es.own_omega.alloc(n * 36);
+    if (n) hipLaunchKernelGGL(identity6_kernel, dim3(grid_for(n * 36)), dim3(kThreads), 0, st_, n, es.own_omega.p);
+  } else {
+    es.own_omega.upload(info, n * 36, st_);
+  }
+  es.own_J0.alloc(n * 36);
+  es.own_J1.alloc(n * 36);
+  es.own_err.alloc(n * 6);
   es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
   es.external = false;
   es.has_data = false;   // becomes valid with the first ba_linearize
@@ -5370,10 +5431,11 @@ void BlockSolver::ba_set_estimates(int n_cams, const double* cams, const int* ca
   if (!same) {
     if (ba_.set >= 0)
       ba_validate_edges(*sets_[ba_.set], ba_.h_cam_v.data(), ba_.h_pt_v.data(), ba_.h_cam_v.size(), cam_hidx, n_cams, point_hidx, n_points);
+    if (ba_.pose_set >= 0) pg_validate(*sets_[ba_.pose_set], ba_.h_pvi.data(), ba_.h_pvj.data(), ba_.h_pvi.size(), cam_hidx, n_cams);
     invalidate_graphs();
   }
   ++ba_.est_version;
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   chi2_valid_ = false;
   ba_.has_backup = false;
   if (same) {
@@ -5473,8 +5535,16 @@ void BlockSolver::ba_linearize(bool jacobians) {
   const bool fused = ba_fused && ba_.fused_ok;
   // fused mode: build_system re-evaluates the Jacobians itself, only the errors (for chi2) are produced here
   const bool need_jac = jacobians && !fused;
-  if (ba_.err_valid && (!need_jac || ba_.jac_valid)) {   // the estimates have not moved since the last evaluation
+  // ... but the pose set beside it (ba_set_pose_edges) is assembled by the generic kernels whatever the projection set does: its
+  // Jacobians are written whenever Jacobians are asked for, and that is tracked apart from jac_valid
+  EdgeSet* ep = ba_.pose_set >= 0 ? sets_[ba_.pose_set].get() : nullptr;
+  if (ep && (int)ba_.h_pvi.size() != ep->n)
+    throw StateFailure("ba_linearize: the pose edge set has grown since ba_set_pose_edges (g2ohip_update_structure): call ba_set_pose_edges again");
+  const bool proj_done = ba_.err_valid && (!need_jac || ba_.jac_valid);
+  const bool pose_done = !ep || (ba_.err_valid && (!jacobians || ba_.pose_jac_valid));
+  if (proj_done && pose_done) {   // the estimates have not moved since the last evaluation
     if (jacobians) es.has_data = true;
+    if (jacobians && ep) ep->has_data = true;
     return;
   }
   if (need_jac && (es.own_J0.n < (size_t)es.n * es.d * 3 || es.own_J1.n < (size_t)es.n * es.d * 6)) {   // (left out by ba_set_edges on the fused path)
@@ -5486,14 +5556,19 @@ void BlockSolver::ba_linearize(bool jacobians) {
   }
   ba_.err_valid = true;
   if (need_jac) ba_.jac_valid = true;
+  if (jacobians && ep) ba_.pose_jac_valid = true;
   chi2_valid_ = false;
-  if (profiling) tfe_.start(st_);
+  // (the stage times speak of a whole evaluation: a launch of the pose kernel alone, which only completes one, leaves them)
+  const bool timed = profiling && !proj_done;
+  if (timed) tfe_.start(st_);
   // the chi2 of these errors rides along: 1 024 partial sums in this set's slot of the trial read-back buffer (chi2() and
   // trial_stats() take them from there while err_valid holds)
   const int lgrid = grid_for(es.n);
   if (d_red_multi.n < (sets_.size() + 1) * kMaxBlocks) d_red_multi.alloc((sets_.size() + 1) * kMaxBlocks);
   if (ba_.chi_part.n < (size_t)lgrid) ba_.chi_part.alloc(lgrid);
-  if (ba_.stereo) {
+  if (proj_done) {
+    // (only the pose set's Jacobians are missing: an error-only evaluation, then one with Jacobians at the same estimates)
+  } else if (ba_.stereo) {
     if (es.n > 0)   // (the kernel clamps its edge index to n - 1)
       with_bool(ba_stereo_staged, [&](auto staged) {
         constexpr bool STAGED = staged;
@@ -5507,21 +5582,29 @@ void BlockSolver::ba_linearize(bool jacobians) {
                        es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, ba_.chi_part.p,
                        ba_.n_classes > 1 ? ba_.ctab.p : (const double*)nullptr);
   }
-  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(1024), 0, st_, ba_.chi_part.p, lgrid, d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks);
-  if (profiling) {
+  if (!proj_done)
+    hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(1024), 0, st_, ba_.chi_part.p, lgrid, d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks);
+  if (!pose_done && ep->n > 0)   // EdgeSE3Expmap beside the projection set -- ba_pose_edge.inc (the kernel clamps its edge index to n - 1)
+    hipLaunchKernelGGL(ba_pose_edge_linearize_kernel, dim3(grid_for(ep->n)), dim3(kThreads), 0, st_, ep->n, ba_.cams.val.p, ba_.pvi.p,
+                       ba_.pvj.p, ba_.pose_meas.p, ep->own_J0.p, ep->own_J1.p, ep->own_err.p, jacobians ? 1 : 0);
+  if (timed) {
     tfe_.stop(st_);
     (jacobians ? times.linearize : times.residuals) = tfe_.seconds();
   }
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
+  if (ep) {
+    ep->has_err = true;
+    if (jacobians) ep->has_data = true;
+  }
 }
 
 void BlockSolver::ba_update() {
   require_structure();
   if (ba_.cams.n <= 0) throw StateFailure("ba_update before ba_set_estimates");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   ++ba_.est_version;
   ba_fetch_fence();
   if (profiling) tfe_.start(st_);
@@ -5548,7 +5631,7 @@ void BlockSolver::ba_push() {
 }
 void BlockSolver::ba_pop() {
   if (!ba_.has_backup) throw StateFailure("ba_pop without push");
-  ba_.err_valid = ba_.jac_valid = false;
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
   ba_fetch_fence();
   ba_.cams.pop(st_);
   ba_.pts.pop(st_);

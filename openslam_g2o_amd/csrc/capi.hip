@@ -539,6 +539,9 @@ int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_ver
                                const double* info, double focal_length, double cx, double cy, double baseline) {
   return entry(s, [&](BlockSolver& b) { b.ba_set_stereo_edges(set, cam_vertex, point_vertex, meas, info, focal_length, cx, cy, baseline); });
 }
+int g2ohip_ba_set_pose_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
+  return entry(s, [&](BlockSolver& b) { b.ba_set_pose_edges(set, vi, vj, meas, info); });
+}
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,
                             const double* points, const int32_t* point_hidx) {
   return entry(s, [&](BlockSolver& b) { b.ba_set_estimates(n_cams, cams, cam_hidx, n_points, points, point_hidx); });

@@ -563,6 +563,8 @@ def write_g2o_landmarks(path, prob):
 #                                                      vertex 0, types_six_dof_expmap.h:133)
 # EDGE_PROJECT_XYZ2UVU:EXPMAP point pose u v u_r i00 i01 i02 i11 i12 i22   (stereo; types_six_dof_expmap.cpp:328-351: no
 #                                                      parameter id on the line)
+# EDGE_SE3:EXPMAP i j tx ty tz qx qy qz qw + 21 upper-triangle information values   (EdgeSE3Expmap, vertex 0 = i, vertex 1 = j;
+#                                                      types_six_dof_expmap.cpp:109-135: the line holds the INVERSE of the measurement)
 # FIX id ...                                           optimizable_graph.cpp:407-420
 def _quat_to_R(q):
     """(x, y, z, w) -> rotation matrices [n][3][3] (Eigen's toRotationMatrix, no normalisation)."""
@@ -605,7 +607,10 @@ def _R_to_quat(R):
 
 def write_g2o_ba(path, prob):
     """openslam_g2o_amd.synthetic-style BA problem -> `.g2o` text (cameras get ids 0..P-1, points P..P+L-1).  A problem with
-    observation = "stereo" writes EDGE_PROJECT_XYZ2UVU:EXPMAP lines and its baseline in the parameter line."""
+    observation = "stereo" writes EDGE_PROJECT_XYZ2UVU:EXPMAP lines and its baseline in the parameter line.  pose_edges
+    (synthetic.make_ba_odometry) are written as EDGE_SE3:EXPMAP lines: the inverse of each measurement as (t, unit quaternion),
+    then the upper triangle of its information (identity when the problem has none)."""
+    from . import se3expmap as X
     stereo = prob.get("observation") == "stereo"
     cams, pts = np.asarray(prob["cams"]), np.asarray(prob["pts"])
     P = len(cams)
@@ -635,14 +640,25 @@ def write_g2o_ba(path, prob):
             io = (1.0, 0.0, 1.0) if info is None else (info[e][0], info[e][2], info[e][3])   # column-major 2x2 -> upper
             f.write("EDGE_PROJECT_XYZ2UV:EXPMAP %d %d 0 %.17g %.17g %.17g %.17g %.17g\n" % (
                 P + prob["pt_idx"][e], prob["cam_idx"][e], prob["meas"][e][0], prob["meas"][e][1], *io))
+        pe = prob.get("pose_edges")
+        if pe is not None:
+            v7 = X.iso_to_vector7(X.invert(pe["meas"]))
+            for e in range(len(pe["vi"])):
+                W = np.eye(6) if pe.get("info") is None else np.asarray(pe["info"][e]).reshape(6, 6).T
+                io = [W[i, j] for i in range(6) for j in range(i, 6)]
+                f.write("EDGE_SE3:EXPMAP %d %d %s\n" % (pe["vi"][e], pe["vj"][e], " ".join("%.17g" % v for v in (*v7[e], *io))))
 
 
 def read_g2o_ba(path):
     """`.g2o` BA file -> problem dict in the layout of openslam_g2o_amd.synthetic.make_ba_problem (index mapping:
     free poses by vertex id, then points by vertex id, sparse_optimizer.cpp:174-187; FIX or no FIX: gauge left to the caller).
     A file of EDGE_PROJECT_XYZ2UVU:EXPMAP lines gives observation = "stereo", baseline (the fourth field of
-    PARAMS_CAMERAPARAMETERS), meas [E][3] and omega [E][9]; one that mixes the two edge tags raises ValueError."""
+    PARAMS_CAMERAPARAMETERS), meas [E][3] and omega [E][9]; one that mixes the two edge tags raises ValueError.  A file with
+    EDGE_SE3:EXPMAP lines gives pose_edges in the layout of synthetic.make_ba_odometry (the measurement = the inverse of what
+    the line holds); a file without the tag gives no such key."""
+    from . import se3expmap as X
     stereo, baseline = None, None
+    p_i, p_j, p_v7, p_info = [], [], [], []
     cam_id, cam_v, pt_id, pt_v, e_pt, e_cam, meas, info, fixed = [], [], [], [], [], [], [], [], []
     f_, cx, cy = None, None, None
     with open(path) as fh:
@@ -677,6 +693,11 @@ def read_g2o_ba(path):
                 meas.append([float(t[4]), float(t[5])])
                 i00, i01, i11 = float(t[6]), float(t[7]), float(t[8])
                 info.append([i00, i01, i01, i11])
+            elif tag == "EDGE_SE3:EXPMAP":
+                p_i.append(int(t[1]))
+                p_j.append(int(t[2]))
+                p_v7.append([float(x) for x in t[3:10]])
+                p_info.append(_upper_to_full([float(x) for x in t[10:31]], 6).T.reshape(36))   # column-major 6x6
             elif tag == "FIX":
                 fixed.extend(int(x) for x in t[1:])
     if f_ is None:
@@ -711,4 +732,9 @@ def read_g2o_ba(path):
         if baseline is None:
             raise ValueError("PARAMS_CAMERAPARAMETERS of %s has no baseline field" % path)
         out.update(observation="stereo", baseline=baseline)
+    if p_i:
+        vi = np.asarray([clut[a] for a in p_i], np.int32)
+        vj = np.asarray([clut[a] for a in p_j], np.int32)
+        out["pose_edges"] = dict(n=len(vi), vi=vi, vj=vj, v0=cam_hidx[vi].astype(np.int32), v1=cam_hidx[vj].astype(np.int32),
+                                 meas=X.invert(X.vector7_to_iso(np.asarray(p_v7, np.float64))), info=np.asarray(p_info, np.float64))
     return out

@@ -286,11 +286,14 @@ class DeviceBAGraph:
         self.s.baDiscardTop()
 
 
-def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
+def setup_device_ba(prob, huber_delta=0.0, device=0, options=None, huber_delta_pose=0.0):
     """Build a HipBlockSolver for an openslam_g2o_amd.synthetic BA problem with the estimates, errors
     and Jacobians produced on the device.  Returns (solver, graph).  options: g2ohip_set_option pairs that have to be
     in place before buildStructure (ordering / kernel selection knobs).  A problem with observation = "stereo"
-    (make_ba_problem(..., stereo_baseline=b)) is a set of EdgeProjectXYZ2UVU: error_dim 3, bound through baSetStereoEdges."""
+    (make_ba_problem(..., stereo_baseline=b)) is a set of EdgeProjectXYZ2UVU: error_dim 3, bound through baSetStereoEdges.
+    A problem with pose_edges (synthetic.make_ba_odometry, g2o_io.read_g2o_ba of a file with EDGE_SE3:EXPMAP) gets a second,
+    binary set of EdgeSE3Expmap constraints between its cameras, bound through baSetPoseEdges; huber_delta_pose > 0 puts a Huber
+    kernel on that set.  Its id is the projection set's + 1."""
     import numpy as np
     from . import capi
     stereo = prob.get("observation") == "stereo"
@@ -298,12 +301,19 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None):
     for name, value in (options or {}).items():
         s.setOption(name, value)
     k = s.addEdgeSet(3 if stereo else 2, prob["v0"], prob["v1"])
+    pe = prob.get("pose_edges")
+    if pe is not None:
+        kp = s.addEdgeSet(6, pe["v0"], pe["v1"])
     s.buildStructure(prob["nP"], prob["nL"], True)
     if stereo:
         s.baSetStereoEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"], prob["baseline"])
     else:
         s.baSetEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"])
     s.baSetEstimates(prob["cams"], prob["cam_hidx"], prob["pts"], np.arange(prob["L"], dtype=np.int32))
+    if pe is not None:
+        s.baSetPoseEdges(kp, pe["vi"], pe["vj"], pe["meas"], pe.get("info"))
+        if huber_delta_pose > 0:
+            s.setRobustKernel(kp, capi.KERNEL_HUBER, huber_delta_pose)
     if huber_delta > 0:
         s.setRobustKernel(k, capi.KERNEL_HUBER, huber_delta)
     return s, DeviceBAGraph(s)

@@ -125,6 +125,37 @@ def make_ba_problem(P, L, seed=42, spacing=0.5, obs_per_landmark=5, outlier_frac
     return prob
 
 
+def make_ba_odometry(P, L, loop_every=10, sigma_rot=0.002, sigma_trans=0.01, seed=42, **ba_args):
+    """make_ba_problem(P, L, seed=seed, **ba_args) -- mono, or stereo with stereo_baseline -- with a set of EdgeSE3Expmap
+    constraints between its cameras (types_six_dof_expmap.h:111-130) under the key pose_edges: odometry between consecutive
+    cameras (k, k + 1) and loop closures (k, k + loop_every) for every loop_every-th camera k; pairs of two fixed cameras are
+    left out.  The measurement of an edge (vertex 0 = Ti, vertex 1 = Tj) is Tj exp(noise) Ti^-1 of the TRUE cameras -- the
+    true relative pose times a small exp(noise), placed so that the error at the truth, log(Tj^-1 C Ti), is the noise itself
+    wherever the cameras stand (omega ~ N(0, sigma_rot^2), upsilon ~ N(0, sigma_trans^2): normal streams 60 .. 65) -- and
+    the information diag(1 / sigma_rot^2 x 3, 1 / sigma_trans^2 x 3) of every edge.
+    pose_edges = dict(n, vi, vj (indices into cams), v0, v1 (hessian indices, -1 = fixed), meas [n][12], info [n][36])."""
+    from . import se3expmap as X
+    prob = make_ba_problem(P, L, seed=seed, **ba_args)
+    spacing = ba_args.get("spacing", 0.5)
+    truth = np.zeros((P, 12))
+    truth[:, 0] = truth[:, 4] = truth[:, 8] = 1.0
+    truth[:, 9] = -np.arange(P) * spacing
+    k = np.arange(P - 1)
+    lk = np.arange(0, max(P - loop_every, 0), loop_every)
+    vi = np.concatenate([k, lk]).astype(np.int32)
+    vj = np.concatenate([k + 1, lk + loop_every]).astype(np.int32)
+    h = prob["cam_hidx"]
+    keep = (h[vi] >= 0) | (h[vj] >= 0)
+    vi, vj = vi[keep], vj[keep]
+    n = len(vi)
+    rng = CounterRng(seed)
+    noise = np.stack([sigma_rot * rng.normal(60 + i, n) for i in range(3)] + [sigma_trans * rng.normal(63 + i, n) for i in range(3)], axis=1)
+    meas = X.pack(X.product(X.product(X.unpack(truth[vj]), X.unpack(X.exp(noise))), X.inverse(X.unpack(truth[vi]))))
+    info = np.tile(np.diag([1.0 / sigma_rot ** 2] * 3 + [1.0 / sigma_trans ** 2] * 3).reshape(36), (n, 1))
+    prob["pose_edges"] = dict(n=n, vi=vi, vj=vj, v0=h[vi].astype(np.int32), v1=h[vj].astype(np.int32), meas=meas, info=info)
+    return prob
+
+
 def make_ba_loops(P, L, laps=4, hubs=3, drop=0.2, seed=7, spacing=0.5, f=1000.0, cx=320.0, cy=240.0, hub_stride=3):
     """A bundle-adjustment graph that is NOT a band: the camera runs `laps` times back and forth along the same line
     (poses of different laps stand at the same places and see the same points -- loop closures everywhere, the reduced
