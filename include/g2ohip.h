@@ -265,7 +265,8 @@ int g2ohip_copy_values(g2ohip_solver* s, int which, double* values_host);
 /* Device pointers + element counts of resident arrays (for multi-GPU exchange through RCCL):
  * which = G2OHIP_HSCHUR (values), or 100 = bschur.  For tests only, no part of the supported interface: 108 = the information
  * matrices [n][3x3] of the bound GICP set as the last g2ohip_pg_linearize left them (G2OHIP_ERR_STATE without one; the pointer
- * holds until the set is bound again) -- g2ohip_copy_edge_data returns no information matrices. */
+ * holds until the set is bound again) -- g2ohip_copy_edge_data returns no information matrices; 109 = the inverse measurements
+ * [n][7] of the bound EdgeSBACam set as g2ohip_pg_set_cam_edges stored them (G2OHIP_ERR_STATE without one). */
 int g2ohip_device_array(g2ohip_solver* s, int which, double** ptr, size_t* count);
 /* BlockSolver::computeMarginals / LinearSolver::solvePattern (block_solver.hpp:489-498, linear_solver.h:63-69,
  * marginal_covariance_cholesky.cpp:71-220): blocks (rows[i], cols[i]) (pose block indices) of the inverse of Hpp
@@ -595,7 +596,7 @@ int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* p
  * the order of SE3Quat::toVector (g2o/types/slam3d/se3quat.h:138-148) and of VertexCam::write (types_sba.cpp:114-131); a
  * non-finite value or a quaternion of norm 0 is G2OHIP_ERR_ARG, otherwise the row is stored as given.  The type-12 pose-pose set
  * is the anchor the landmark slot needs and holds ZERO edges (added with error_dim 6 and n = 0; its arrays may be NULL): n > 0
- * is G2OHIP_ERR_ARG -- EdgeSBACam and EdgeSBAScale have no analytic Jacobian in the reference and are not on the device yet.
+ * is G2OHIP_ERR_ARG -- EdgeSBACam and EdgeSBAScale are bound with g2ohip_pg_set_cam_edges, each as a set of its own beside it.
  * g2ohip_pg_update applies SBACam::update (g2o/types/sba/sbacam.h:101-117): t += x[0:3], qr = (x[3:6], sqrt(1 - |x[3:6]|^2)),
  * q <- q qr, then q / |q|; no sign flip.  A step with |x[3:6]| > 1 gives NaN, as in the reference.
  * Beside it, in the single landmark slot, type 13 = EdgeProjectP2MC (types_sba.h:161-196; error_dim 2, meas [n][2], info
@@ -617,11 +618,38 @@ int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* p
  * types 1, 2 and 10.  Everything after the binding -- g2ohip_pg_set_landmark_estimates, g2ohip_pg_linearize / update / push /
  * pop / discard_top, robust kernels, do_schur 0 / 1, every linear_solver, g2ohip_clear_edge_sets -- acts on it unchanged; the
  * kernel is timed in the pg_landmark_linearize slot and has the staged and direct store forms of option pg_landmark_staged.
- * Not covered: EdgeSBACam, EdgeSBAScale, VertexIntrinsics / EdgeProjectP2MC_Intrinsics (a three-vertex edge), priors beside a
+ * Not covered: VertexIntrinsics / EdgeProjectP2MC_Intrinsics (a three-vertex edge), priors beside a
  * type-12 set, more than one landmark set per handle (mono and stereo at once), sharded solves, the g2o plugin adapter (it keeps
  * these edges on its host path). */
 int g2ohip_pg_set_cam_project_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
                                     const double* meas, const double* info, int n_cams, const double* intrinsics);
+/* ---- ... the SBA group's pose-pose constraints: odometry and loop closures between cameras, a known baseline -----------------
+ * type 16 = EdgeSBACam (types_sba.h:287-334; tag EDGE_CAM): meas [n][7] = (tx, ty, tz, qx, qy, qz, qw), info [n][6x6], a binary
+ *           set of error_dim 6.  e = (delta.t, delta.q.xyz), delta = Zinv * (Ci^-1 * Cj) with SE3Quat::inverse and operator*
+ *           (se3quat.h:104-128), the normalizeRotation the product ends with included (sign flip when w < 0, then q / |q|).  The
+ *           measurement is normalised as SE3Quat(Vector7d) does and inverted ONCE, at binding (setMeasurement).
+ * type 17 = EdgeSBAScale (types_sba.h:340-359; tag EDGE_SCALE): meas [n][1], info [n][1], a binary set of error_dim 1.
+ *           e = z - |t_j - t_i|.
+ * Each type binds to ONE slot of its own beside a type-12 pose set of g2ohip_pg_set_edges (which stays an empty anchor): either
+ * slot or both, with or without a type-13 / 14 projection set -- a pure VertexCam pose graph on a (6, 3) handle with no landmark
+ * included.  Both vertices of a set are 6-dof cameras (added over the cameras' hessian indices, -1 = fixed); vi / vj index the
+ * table of g2ohip_pg_set_estimates.  Many edges on one pair, and a pair in both orders, are legal; n = 0 is legal (arrays may
+ * then be NULL).  The reference defines no Jacobian for these edges: J is BaseBinaryEdge's numeric one (base_binary_edge.hpp:
+ * 132-201), column c of side v = (e(C_v (+) delta u_c) - e(C_v (+) -delta u_c)) / (2 delta), delta = 1e-9, (+) = SBACam::update;
+ * the device evaluates exactly that, without fused multiply-adds.  J0, J1 are [n][d x 6] column-major; the block of a fixed
+ * vertex is zeros; the rotation columns of an EdgeSBAScale block are exactly zero (the step does not reach t).
+ * Call after g2ohip_build_structure and g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).  G2OHIP_ERR_ARG: a type other than 16 /
+ * 17, a pose set of type 1, 2 or 10, a set of other dimensions or a unary one, a set bound in another slot, a null array with
+ * n > 0, an index outside the pose table, a hessian index that differs from the set's, a non-finite value, a measurement
+ * quaternion of norm 0 -- validated before anything is committed.  A later call replaces the slot's set and clears the data of
+ * the set that leaves it.  While either slot is bound g2ohip_pg_set_edges refuses types 1, 2 and 10, and the other
+ * g2ohip_pg_set_* entries refuse the slots' set ids.  g2ohip_pg_set_estimates with changed tables validates the sets again;
+ * update / push / pop / discard_top, chi2 and robust kernels act as for any set; g2ohip_clear_edge_sets drops the bindings; a
+ * set grown by g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.  The kernels
+ * are timed under the "pg_landmark_linearize" slot.  For tests only: g2ohip_device_array(109) = the stored inverse measurements
+ * [n][7] of the EdgeSBACam slot.  Not covered: sharded solves, the g2o plugin adapter. */
+int g2ohip_pg_set_cam_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const double* meas,
+                            const double* info);
 /* ---- ... its unary pose priors: GPS fixes, an anchor on the first pose, surveyed checkpoints ------------------------
  * One UNARY edge set of the same handle beside the pose-pose set of g2ohip_pg_set_edges, in a slot of its own (independent of
  * the landmark slot: with or without a landmark set, do_schur 0 or 1; a later call replaces the binding):

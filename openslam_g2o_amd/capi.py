@@ -27,6 +27,7 @@ ERR_UNSUPPORTED = -4
 HPP, HPL, HLL, HSCHUR, DINV = 0, 1, 2, 3, 4
 PART_NO_VERTEX0, PART_NO_VERTEX1, PART_NO_CHI2 = 1, 2, 4      # g2ohip_set_edge_set_parts
 ARR_BSCHUR, ARR_X, ARR_B, ARR_EXCHANGE, ARR_XP, ARR_XBOUNDARY, ARR_XHALO, ARR_SCHUR_DIAG = 100, 101, 102, 103, 104, 105, 106, 107
+ARR_CAM_ZINV = 109      # (tests only) inverse measurements [n][7] of the bound EdgeSBACam set, as pgSetCamEdges stored them
 ARR_GICP_OMEGA = 108    # (tests only) information matrices [n][9] of the bound GICP set, rewritten by every plane-to-plane pgLinearize
 KERNEL_NONE, KERNEL_HUBER, KERNEL_PSEUDOHUBER, KERNEL_CAUCHY, KERNEL_SATURATED, KERNEL_DCS = 0, 1, 2, 3, 4, 5
 
@@ -63,6 +64,7 @@ EXPORTS = [
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
+    "g2ohip_pg_set_cam_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -172,6 +174,7 @@ def load():
     L.g2ohip_pg_set_cam_project_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_gicp_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
     L.g2ohip_copy_edge_data.argtypes = [vp, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -542,6 +545,7 @@ class HipBlockSolver:
         _check(self.L.g2ohip_clear_edge_sets(self.h), "clearEdgeSets")
         self._set_sizes = {}
         self.gicp_set = None                # (the library drops every front-end binding)
+        self.cam_set = self.scale_set = None
         self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
@@ -561,6 +565,7 @@ class HipBlockSolver:
             self._set_sizes[set_id] += n
             if set_id in getattr(self, "_pg_owner_sets", ()):     # growth of the pose-pose or landmark set drops the whole front end
                 self.gicp_set = None
+                self.cam_set = self.scale_set = None
                 self._pg_owner_sets = set()
         return True
 
@@ -873,6 +878,26 @@ class HipBlockSolver:
         _check(self.L.g2ohip_pg_set_gicp_edges(self.h, set_id, _ip(vi), _ip(vj), _dp(meas), _dp(info),
                                                None if cov is None else _dp(cov)), "pgSetGicpEdges")
         self.gicp_set = set_id
+
+    cam_set = scale_set = None     # set ids of the bound EdgeSBACam / EdgeSBAScale sets (pgSetCamEdges)
+
+    def pgSetCamEdges(self, set_id, edge_type, vi, vj, meas, info):
+        """Pose-pose constraints beside a VertexCam set (type 12, which holds zero edges), each type in a slot of its own:
+        edge_type 16 = EdgeSBACam (meas [n][7] = (tx, ty, tz, qx, qy, qz, qw), normalised and inverted once here; info
+        [n][6x6]; a binary set of error_dim 6), 17 = EdgeSBAScale (meas [n], info [n]; error_dim 1).  vi / vj index the table of
+        pgSetEstimates.  The Jacobians are the reference's numeric ones.  After pgSetEdges."""
+        if edge_type not in (16, 17):
+            raise ValueError("pgSetCamEdges: edge_type 16 (EdgeSBACam) or 17 (EdgeSBAScale)")
+        vi, vj, meas, info = _i32(vi), _i32(vj), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        ms, d2 = (7, 36) if edge_type == 16 else (1, 1)
+        if len(vi) != n or len(vj) != n or meas.size != n * ms or info.size != n * d2:
+            raise ValueError("pgSetCamEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        _check(self.L.g2ohip_pg_set_cam_edges(self.h, set_id, edge_type, _ip(vi), _ip(vj), _dp(meas), _dp(info)), "pgSetCamEdges")
+        if edge_type == 16:
+            self.cam_set = set_id
+        else:
+            self.scale_set = set_id
 
     def pgSetLandmarkEstimates(self, points, hidx):
         """points [n][landmark_dim]; hidx[v] = the landmark's hessian index in the whole system (>= num_poses) or -1."""

@@ -133,6 +133,11 @@ class HipBlockSolver {
   bool pgSetGicpEdges(int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info, const double* cov) {
     return ok(g2ohip_pg_set_gicp_edges(h_, set, vi, vj, meas, info, cov), "pgSetGicpEdges");
   }
+  // SBA pose-pose constraints (g2ohip_pg_set_cam_edges) beside a VertexCam set: type 16 = EdgeSBACam (error_dim 6, meas [n][7] =
+  // (t, qx, qy, qz, qw), info [n][6x6]), 17 = EdgeSBAScale (error_dim 1, meas [n], info [n]); one slot per type
+  bool pgSetCamEdges(int set, int type, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
+    return ok(g2ohip_pg_set_cam_edges(h_, set, type, vi, vj, meas, info), "pgSetCamEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -103,6 +103,7 @@ class BlockSolver {
                                 const double* info, int n_cams, const double* intrinsics);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov);
+  void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
   void pg_linearize(bool jacobians);
@@ -493,6 +494,13 @@ class BlockSolver {
     DevBuf<int> gi, gj;
     std::vector<int> h_gi, h_gj;   // host copies: index validation (pg_validate)
     DevBuf<double> gicp_meas, gicp_cov;
+    // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
+    // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
+    // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.
+    int cam_set = -1, scale_set = -1;
+    DevBuf<int> ci, cj, si, sj;
+    std::vector<int> h_ci, h_cj, h_si, h_sj;   // host copies: index validation (pg_validate)
+    DevBuf<double> cam_zinv, scale_meas;
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

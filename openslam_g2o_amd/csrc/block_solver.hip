@@ -2209,6 +2209,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_sim3.inc"
 #include "pg_sim3_project.inc"
 #include "pg_cam_project.inc"
+#include "pg_sbacam_edge.inc"
 #include "pg_gicp.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
@@ -2257,7 +2258,7 @@ void dispatch_offdiag(int D, int DR, int DC, int nDst, const int* dst, const int
   };
   if (row(ic<2>, ic<3>, ic<2>) || row(ic<2>, ic<6>, ic<3>) || row(ic<3>, ic<3>, ic<3>) || row(ic<3>, ic<6>, ic<3>) ||
       row(ic<6>, ic<6>, ic<6>) || row(ic<7>, ic<7>, ic<7>) || row(ic<2>, ic<3>, ic<3>) || row(ic<2>, ic<6>, ic<6>) ||
-      row(ic<3>, ic<6>, ic<6>) || row(ic<1>, ic<3>, ic<2>) || row(ic<1>, ic<6>, ic<3>) || row(ic<2>, ic<7>, ic<3>) ||
+      row(ic<3>, ic<6>, ic<6>) || row(ic<1>, ic<3>, ic<2>) || row(ic<1>, ic<6>, ic<3>) || row(ic<1>, ic<6>, ic<6>) || row(ic<2>, ic<7>, ic<3>) ||
       row(ic<3>, ic<7>, ic<3>))
     return;
   throw ArgFailure("unsupported off-diagonal block shape (d,rows,cols) = (" + std::to_string(D) + "," + std::to_string(DR) + "," +
@@ -2470,7 +2471,7 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
     // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
-    // (pg_set_gicp_edges again)
+    // (pg_set_gicp_edges again) or a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again)
     if (set == pg_.set || set == pg_.lm_set) {
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -3187,7 +3188,8 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == ba_.pose_set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set;
+  const bool front_end_set = set == ba_.set || set == ba_.pose_set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
+                             set == pg_.cam_set || set == pg_.scale_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5687,8 +5689,11 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (type != 2 && pg_.gicp_set >= 0)
     throw ArgFailure("pg_set_edges: an Edge_V_V_GICP set (15) is bound: it stands beside an EdgeSE3 pose set (2) only");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_edges: the set is bound as the GICP set");
+  if (type != 12 && (pg_.cam_set >= 0 || pg_.scale_set >= 0))
+    throw ArgFailure("pg_set_edges: an EdgeSBACam (16) or EdgeSBAScale (17) set is bound: it stands beside a VertexCam set (12) only");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (type == 12 && n > 0)
-    throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam is not on the device yet (it has no analytic Jacobian in the reference)");
+    throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
   // type-12 set is always empty: it is the anchor of the camera table that the landmark slot needs)
   if ((n > 0 || (type != 10 && type != 12)) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
@@ -5760,6 +5765,8 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
                             pg_.points.n);
     if (pg_.pr_set >= 0) pg_validate_priors(*sets_[pg_.pr_set], pg_.h_vq.data(), pg_.h_vq.size(), hidx, nv);
     if (pg_.gicp_set >= 0) pg_validate(*sets_[pg_.gicp_set], pg_.h_gi.data(), pg_.h_gj.data(), pg_.h_gi.size(), hidx, nv);
+    if (pg_.cam_set >= 0) pg_validate(*sets_[pg_.cam_set], pg_.h_ci.data(), pg_.h_cj.data(), pg_.h_ci.size(), hidx, nv);
+    if (pg_.scale_set >= 0) pg_validate(*sets_[pg_.scale_set], pg_.h_si.data(), pg_.h_sj.data(), pg_.h_si.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -5861,6 +5868,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
   if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
   if (set == pg_.gicp_set) throw ArgFailure(w + ": the set is bound as the GICP set");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure(w + ": the set is bound as the EdgeSBACam or EdgeSBAScale set");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -5916,6 +5924,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (set == pg_.set) throw ArgFailure("pg_set_prior_edges: the set is bound as the pose-pose set");
   if (set == pg_.lm_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the landmark set");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the GICP set");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -5969,6 +5978,7 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   if (set == pg_.set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the pose-pose set");
   if (set == pg_.lm_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the landmark set");
   if (set == pg_.pr_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the prior set");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6008,6 +6018,74 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   es.external = false;
   es.has_data = false;
   es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
+// own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
+// validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
+// legal; the sets own no vertices.  EdgeSBACam::setMeasurement: the measurement is normalised (SE3Quat(Vector7d)) and inverted
+// once, here, on the device and in the reference's operation order; pg_.cam_zinv holds the inverses.
+void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_cam_edges: call pg_set_edges first (the empty VertexCam set (12) the set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 16 && type != 17) throw ArgFailure("pg_set_cam_edges: type must be 16 (EdgeSBACam) or 17 (EdgeSBAScale)");
+  if (pg_.type != 12) throw ArgFailure("pg_set_cam_edges: EdgeSBACam / EdgeSBAScale go with a VertexCam set (12)");
+  const bool cam = type == 16;
+  if (set == pg_.set) throw ArgFailure("pg_set_cam_edges: the set is bound as the pose-pose set");
+  if (set == pg_.lm_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the landmark set");
+  if (set == pg_.pr_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the prior set");
+  if (set == pg_.gicp_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the GICP set");
+  if (set == (cam ? pg_.scale_set : pg_.cam_set))
+    throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
+  EdgeSet& es = *sets_[set];
+  const int d = cam ? 6 : 1;
+  if (es.unary || es.d != d || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
+    throw ArgFailure(std::string("pg_set_cam_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions ") +
+                     (cam ? "(6, 6, 6)" : "(1, 6, 6)"));
+  const size_t n = (size_t)es.n, ms = cam ? 7 : 1;
+  if (n > 0 && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_cam_edges: null array");
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0) throw ArgFailure("pg_set_cam_edges: negative vertex index in edge " + std::to_string(k));
+    for (size_t i = 0; i < ms; ++i)
+      if (!std::isfinite(meas[ms * k + i])) throw ArgFailure("pg_set_cam_edges: non-finite measurement in edge " + std::to_string(k));
+    for (int i = 0; i < d * d; ++i)
+      if (!std::isfinite(info[(size_t)(d * d) * k + i])) throw ArgFailure("pg_set_cam_edges: non-finite information in edge " + std::to_string(k));
+    if (cam) {   // (a squared norm that is 0 or overflows cannot be normalised)
+      const double* q = meas + 7 * k + 3;
+      const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+      if (!(n2 > 0.0) || !std::isfinite(n2)) throw ArgFailure("pg_set_cam_edges: quaternion of norm 0 in the measurement of edge " + std::to_string(k));
+    }
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  int& slot = cam ? pg_.cam_set : pg_.scale_set;
+  if (slot >= 0 && slot != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
+    EdgeSet& old = *sets_[slot];
+    old.has_data = old.has_err = false;
+  }
+  slot = set;
+  (cam ? pg_.h_ci : pg_.h_si).assign(vi, vi + n);
+  (cam ? pg_.h_cj : pg_.h_sj).assign(vj, vj + n);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  (cam ? pg_.ci : pg_.si).upload(vi, n, st_);
+  (cam ? pg_.cj : pg_.sj).upload(vj, n, st_);
+  DevBuf<double>& dm = cam ? pg_.cam_zinv : pg_.scale_meas;
+  dm.upload(meas, n * ms, st_);
+  if (cam && n > 0)
+    hipLaunchKernelGGL(pg_sbacam_invert_meas_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, (int)n, dm.p);
+  es.own_omega.upload(info, n * d * d, st_);
+  es.own_J0.alloc(n * d * 6);
+  es.own_J1.alloc(n * d * 6);
+  es.own_err.alloc(n * d);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipGetLastError());
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
@@ -6054,11 +6132,17 @@ void BlockSolver::pg_linearize(bool jacobians) {
   EdgeSet* eg = pg_.gicp_set >= 0 ? sets_[pg_.gicp_set].get() : nullptr;
   if (eg && (int)pg_.h_gi.size() != eg->n)
     throw StateFailure("pg_linearize: the GICP edge set has grown since pg_set_gicp_edges (g2ohip_update_structure): call pg_set_gicp_edges again");
+  EdgeSet* ec = pg_.cam_set >= 0 ? sets_[pg_.cam_set].get() : nullptr;
+  EdgeSet* esc = pg_.scale_set >= 0 ? sets_[pg_.scale_set].get() : nullptr;
+  if ((ec && (int)pg_.h_ci.size() != ec->n) || (esc && (int)pg_.h_si.size() != esc->n))
+    throw StateFailure("pg_linearize: the EdgeSBACam / EdgeSBAScale edge set has grown since pg_set_cam_edges (g2ohip_update_structure): call pg_set_cam_edges again");
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     if (jacobians) es.has_data = true;
     if (jacobians && el) el->has_data = true;
     if (jacobians && ep) ep->has_data = true;
     if (jacobians && eg) eg->has_data = true;
+    if (jacobians && ec) ec->has_data = true;
+    if (jacobians && esc) esc->has_data = true;
     return;
   }
   pg_.err_valid = true;
@@ -6084,8 +6168,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
     }
   }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
+  const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0;
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch || gicp_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                        pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
@@ -6149,7 +6234,17 @@ void BlockSolver::pg_linearize(bool jacobians) {
       });
     });
   }
-  if (lm_launch || pr_launch || gicp_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (cam_launch) {   // EdgeSBACam: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sbacam_edge.inc
+    hipLaunchKernelGGL(pg_sbacam_error_kernel, dim3(grid_for(ec->n)), dim3(kThreads), 0, st_, ec->n, pg_.poses.val.p, pg_.ci.p, pg_.cj.p,
+                       pg_.cam_zinv.p, ec->own_err.p);
+    if (jacobians)
+      hipLaunchKernelGGL(pg_sbacam_jacobian_kernel, dim3(grid_for(12 * (size_t)ec->n)), dim3(kThreads), 0, st_, ec->n, pg_.poses.val.p,
+                         pg_.poses.hidx.p, pg_.ci.p, pg_.cj.p, pg_.cam_zinv.p, ec->own_J0.p, ec->own_J1.p);
+  }
+  if (scale_launch)   // EdgeSBAScale
+    hipLaunchKernelGGL(pg_sbascale_linearize_kernel, dim3(grid_for(esc->n)), dim3(kThreads), 0, st_, esc->n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, pg_.si.p, pg_.sj.p, pg_.scale_meas.p, esc->own_J0.p, esc->own_J1.p, esc->own_err.p, jac);
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
@@ -6165,6 +6260,11 @@ void BlockSolver::pg_linearize(bool jacobians) {
     eg->has_err = true;
     if (jacobians) eg->has_data = true;
   }
+  for (EdgeSet* e : {ec, esc})
+    if (e) {
+      e->has_err = true;
+      if (jacobians) e->has_data = true;
+    }
 }
 
 void BlockSolver::pg_update() {
@@ -6299,6 +6399,11 @@ void BlockSolver::device_array(int which, double** ptr, size_t* count) {
       if (pg_.gicp_set < 0) throw StateFailure("device_array 108: no GICP set is bound (pg_set_gicp_edges)");
       *ptr = sets_[pg_.gicp_set]->own_omega.p;
       *count = pg_.h_gi.size() * 9;
+      break;
+    case 109:   // the inverse measurements of the bound EdgeSBACam set, [n][7], as pg_set_cam_edges computed them (pg_sbacam_edge.inc)
+      if (pg_.cam_set < 0) throw StateFailure("device_array 109: no EdgeSBACam set is bound (pg_set_cam_edges)");
+      *ptr = pg_.cam_zinv.p;
+      *count = pg_.h_ci.size() * 7;
       break;
     default: throw ArgFailure("bad array selector");
   }

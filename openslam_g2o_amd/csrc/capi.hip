@@ -700,6 +700,10 @@ int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const
                              const double* cov) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_gicp_edges(set, vi, vj, meas, info, cov); });
 }
+int g2ohip_pg_set_cam_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const double* meas,
+                            const double* info) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_cam_edges(set, type, vi, vj, meas, info); });
+}
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_landmark_estimates(n_points, points, hidx); });
 }

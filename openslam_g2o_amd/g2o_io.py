@@ -61,7 +61,11 @@ def read_g2o(path):
     normalised as VertexCam::read does, cam_intrinsics [n][5] = (fx, fy, cx, cy, baseline), cam_point_ids, cam_points [L][3]
     (the VERTEX_XYZ lines, sorted by id), cam_vp / cam_vl (camera-table and point-table index of every EDGE_PROJECT_P2MC /
     EDGE_PROJECT_P2SC line), cam_zl [m][2|3], cam_stereo and cam_fixed_points (sbacam_ba_problem turns them into a problem
-    dict); a file that mixes the two edge tags raises ValueError.
+    dict); a file that mixes the two edge tags raises ValueError.  EDGE_CAM lines (id1 id2, 7 measurement values tx ty tz qx qy
+    qz qw, the 21 upper-triangle information entries row-major: EdgeSBACam::read, types_sba.cpp:138-152) also give cam_edge_vi /
+    cam_edge_vj (camera-table indices), cam_edge_meas [n][7] as written (the binding normalises and inverts) and cam_edge_info
+    [n][36]; EDGE_SCALE lines (id1 id2 meas info: EdgeSBAScale::read, types_sba.cpp:528-536) give cam_scale_vi / cam_scale_vj /
+    cam_scale_meas [n] / cam_scale_info [n]; a file without these tags gives none of these keys.
     A file with EDGE_V_V_GICP lines (i j pos0 normal0 pos1 normal1: Edge_V_V_GICP::read, g2o/types/icp/types_icp.cpp:124-160) over
     VERTEX_SE3:QUAT also gives gicp_vi / gicp_vj (pose-table indices), gicp_meas [m][6] = (pos0, pos1) and gicp_normal0 /
     gicp_normal1 [m][3] (gicp_problem turns them into a problem dict); a file without them gives none of these keys."""
@@ -71,6 +75,7 @@ def read_g2o(path):
     spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
     vid, vest, ei, ej, meas, info, fixed = [], [], [], [], [], [], []
     cam_extras, cam_pt, cam_cam, cam_meas, cam_stereo = [], [], [], [], None
+    ce_i, ce_j, ce_meas, ce_info, cs_i, cs_j, cs_meas, cs_info = [], [], [], [], [], [], [], []
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
     qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
@@ -128,6 +133,16 @@ def read_g2o(path):
                 cam_pt.append(int(t[1]))
                 cam_cam.append(int(t[2]))
                 cam_meas.append([float(x) for x in t[3:(6 if st else 5)]])
+            elif tag == "EDGE_CAM":
+                ce_i.append(int(t[1]))
+                ce_j.append(int(t[2]))
+                ce_meas.append([float(x) for x in t[3:10]])
+                ce_info.append(_upper_to_full([float(x) for x in t[10:31]], 6).reshape(36))
+            elif tag == "EDGE_SCALE":
+                cs_i.append(int(t[1]))
+                cs_j.append(int(t[2]))
+                cs_meas.append(float(t[3]))
+                cs_info.append(float(t[4]))
             elif tag == "VERTEX_XYZ":
                 spid.append(int(t[1]))
                 spest.append([float(x) for x in t[2:5]])
@@ -216,6 +231,12 @@ def read_g2o(path):
                    cam_vp=np.asarray([lut[a] for a in cam_cam], np.int32), cam_vl=np.asarray([splut[a] for a in cam_pt], np.int32),
                    cam_zl=np.asarray(cam_meas, np.float64).reshape(-1, d), cam_stereo=bool(cam_stereo),
                    cam_fixed_points=[splut[f] for f in fixed if f in splut])
+        if ce_i:
+            out.update(cam_edge_vi=np.asarray([lut[a] for a in ce_i], np.int32), cam_edge_vj=np.asarray([lut[a] for a in ce_j], np.int32),
+                       cam_edge_meas=np.asarray(ce_meas, np.float64).reshape(-1, 7), cam_edge_info=np.asarray(ce_info, np.float64).reshape(-1, 36))
+        if cs_i:
+            out.update(cam_scale_vi=np.asarray([lut[a] for a in cs_i], np.int32), cam_scale_vj=np.asarray([lut[a] for a in cs_j], np.int32),
+                       cam_scale_meas=np.asarray(cs_meas, np.float64), cam_scale_info=np.asarray(cs_info, np.float64))
     if pid or lp or offsets or cameras:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
@@ -302,7 +323,9 @@ def write_g2o_sbacam(path, prob, ids=None, point_ids=None):
     them (types_sba.cpp:114-131: t, the quaternion's coefficients, fx fy cx cy baseline), VERTEX_XYZ lines (ids point_ids,
     default n ..), FIX lines for the vertices of hessian index -1, and EDGE_PROJECT_P2MC / EDGE_PROJECT_P2SC lines "id_point
     id_cam u v [u_right]" -- the reference writes no information matrix (types_sba.cpp:215-244) and reads the identity, so
-    omega_l must be the identity.  %.17g: a read gives the written doubles back."""
+    omega_l must be the identity.  prob["cam_edges"] / prob["scale_edges"] (dict(vi, vj, meas, info)), when present, follow as
+    EDGE_CAM "id1 id2 tx ty tz qx qy qz qw" + the 21 upper-triangle information entries, row-major (EdgeSBACam::write, types_sba.cpp:
+    154-162) and EDGE_SCALE "id1 id2 meas info" (EdgeSBAScale::write, :538-542).  %.17g: a read gives the written doubles back."""
     est = np.asarray(prob["est"], np.float64).reshape(-1, 7)
     pts = np.asarray(prob["points"], np.float64).reshape(-1, 3)
     intr = np.asarray(prob["intrinsics"], np.float64).reshape(len(est), 5)
@@ -327,22 +350,36 @@ def write_g2o_sbacam(path, prob, ids=None, point_ids=None):
         tag = "EDGE_PROJECT_P2SC" if stereo else "EDGE_PROJECT_P2MC"
         for e in range(len(zl)):
             f.write("%s %d %d %s\n" % (tag, point_ids[prob["vl"][e]], ids[prob["vp"][e]], fmt(zl[e])))
+        ce, cs = prob.get("cam_edges"), prob.get("scale_edges")
+        if ce is not None:
+            cm, ci = np.asarray(ce["meas"], np.float64).reshape(-1, 7), np.asarray(ce["info"], np.float64).reshape(-1, 6, 6)
+            for e in range(len(cm)):
+                f.write("EDGE_CAM %d %d %s %s\n" % (ids[ce["vi"][e]], ids[ce["vj"][e]], fmt(cm[e]),
+                                                    fmt(ci[e][i, j] for i in range(6) for j in range(i, 6))))
+        if cs is not None:
+            for e in range(len(cs["vi"])):
+                f.write("EDGE_SCALE %d %d %s\n" % (ids[cs["vi"][e]], ids[cs["vj"][e]], fmt([cs["meas"][e], cs["info"][e]])))
 
 
 def sbacam_ba_problem(rd, fixed_cams=None, fixed_points=None):
     """read_g2o result of a VERTEX_CAM file -> the problem dict of lm.setup_device_sbacam_ba (the layout of
     synthetic.make_sbacam_ba): free cameras by vertex id, then free points by vertex id (sparse_optimizer.cpp:174-187); fixed
-    vertices from the file's FIX lines unless given; the information of every observation is the identity."""
-    if rd.get("kind") != "sbacam" or not len(rd["cam_points"]):
+    vertices from the file's FIX lines unless given; the information of every observation is the identity.  EDGE_CAM /
+    EDGE_SCALE lines become cam_edges / scale_edges = dict(vi, vj, meas, info); a file that has them may be without points."""
+    if rd.get("kind") != "sbacam" or not (len(rd["cam_points"]) or "cam_edge_vi" in rd or "cam_scale_vi" in rd):
         raise ValueError("sbacam_ba_problem: not a VERTEX_CAM file with VERTEX_XYZ points")
     n, L = len(rd["estimates"]), len(rd["cam_points"])
     hidx, pt_hidx, nP, nL = landmark_hessian_index(n, L, rd["fixed"] if fixed_cams is None else fixed_cams,
                                                    rd["cam_fixed_points"] if fixed_points is None else fixed_points)
     d = 3 if rd["cam_stereo"] else 2
     m = len(rd["cam_vp"])
-    return dict(est=rd["estimates"], hidx=hidx, nP=nP, nL=nL, points=rd["cam_points"], pt_hidx=pt_hidx, vp=rd["cam_vp"],
-                vl=rd["cam_vl"], zl=rd["cam_zl"], omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)),
-                intrinsics=rd["cam_intrinsics"], stereo=bool(rd["cam_stereo"]))
+    out = dict(est=rd["estimates"], hidx=hidx, nP=nP, nL=nL, points=rd["cam_points"], pt_hidx=pt_hidx, vp=rd["cam_vp"],
+               vl=rd["cam_vl"], zl=rd["cam_zl"], omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)),
+               intrinsics=rd["cam_intrinsics"], stereo=bool(rd["cam_stereo"]))
+    for key, pre in (("cam_edges", "cam_edge_"), ("scale_edges", "cam_scale_")):
+        if pre + "vi" in rd:
+            out[key] = dict(vi=rd[pre + "vi"], vj=rd[pre + "vj"], meas=rd[pre + "meas"], info=rd[pre + "info"])
+    return out
 
 
 def write_g2o_gicp(path, prob, ids=None):

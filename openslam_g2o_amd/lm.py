@@ -461,33 +461,55 @@ def setup_device_sim3_ba(prob, huber_delta=0.0, schur=True, device=0, options=No
     return s, DevicePoseGraph(s)
 
 
-def setup_device_sbacam_ba(prob, huber_delta=0.0, schur=True, device=0, options=None):
+def setup_device_sbacam_ba(prob, huber_delta=0.0, schur=True, device=0, options=None, cam_huber_delta=0.0):
     """HipBlockSolver for an openslam_g2o_amd.synthetic.make_sbacam_ba (or g2o_io.sbacam_ba_problem) graph: bundle adjustment in
     the reference's SBA format -- VertexCam cameras with intrinsics and baselines of their own observing VertexSBAPointXYZ
     points through EdgeProjectP2MC (zl [m][2]) or EdgeProjectP2SC (zl [m][3]); camera and point estimates, errors and the
     analytic Jacobians on the device; BlockSolver_6_3 semantics, points marginalised (schur=True).  huber_delta > 0: Huber
-    kernel on the observation set.  Returns (solver, DevicePoseGraph); solver.landmark_sets = (the empty VertexCam set's id,
-    observation set id), solver.pose_set = the former."""
+    kernel on the observation set.  Optional prob["cam_edges"] / prob["scale_edges"] = dict(vi, vj, meas, info): EdgeSBACam
+    (meas [n][7], info [n][36]) / EdgeSBAScale (meas [n], info [n]) constraints between cameras, each bound as a set of its own
+    (pgSetCamEdges; the numeric Jacobians of the reference, on the device); cam_huber_delta > 0: Huber kernel on the
+    EdgeSBACam set.  A problem with no points (no "vp", or an empty one) is a pure VertexCam pose graph: no observation set,
+    no Schur complement.  Returns (solver, DevicePoseGraph); solver.landmark_sets = (the empty VertexCam set's id,
+    observation set id or None), solver.pose_set = the former, solver.cam_set / solver.scale_set = the constraint sets' ids."""
     import numpy as np
     from . import capi
     s = capi.HipBlockSolver(6, 3, device)
     for name, value in (options or {}).items():
         s.setOption(name, value)
-    hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
-    zl = np.asarray(prob["zl"], np.float64)
-    if zl.ndim != 2 or zl.shape[1] not in (2, 3):
-        raise ValueError("setup_device_sbacam_ba: zl is [m][2] (EdgeProjectP2MC) or [m][3] (EdgeProjectP2SC)")
-    d = zl.shape[1]
+    hidx = np.asarray(prob["hidx"], np.int32)
+    with_points = len(prob.get("vp", ())) > 0
     none = np.zeros(0, np.int32)
     k0 = s.addEdgeSet(6, none, none)
-    k1 = s.addEdgeSet(d, hidx[prob["vp"]], pt_hidx[prob["vl"]])
-    s.buildStructure(prob["nP"], prob["nL"], schur)
+    k1 = None
+    if with_points:
+        pt_hidx = np.asarray(prob["pt_hidx"], np.int32)
+        zl = np.asarray(prob["zl"], np.float64)
+        if zl.ndim != 2 or zl.shape[1] not in (2, 3):
+            raise ValueError("setup_device_sbacam_ba: zl is [m][2] (EdgeProjectP2MC) or [m][3] (EdgeProjectP2SC)")
+        d = zl.shape[1]
+        k1 = s.addEdgeSet(d, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    pose_sets = []
+    for key, typ, dim in (("cam_edges", 16, 6), ("scale_edges", 17, 1)):
+        e = prob.get(key)
+        if e is not None:
+            vi, vj = np.asarray(e["vi"], np.int32), np.asarray(e["vj"], np.int32)
+            pose_sets.append((s.addEdgeSet(dim, hidx[vi], hidx[vj]), typ, vi, vj, e))
+    if with_points:
+        s.buildStructure(prob["nP"], prob["nL"], schur)
+    else:
+        s.buildStructure(prob["nP"], 0, False)
     s.pgSetEdges(k0, 12, none, none, np.zeros((0, 7)), np.zeros((0, 36)))
     s.pgSetEstimates(prob["est"], hidx)
-    s.pgSetCamProjectEdges(k1, 11 + d, prob["vp"], prob["vl"], zl, prob["omega_l"], prob["intrinsics"])
-    s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
-    if huber_delta > 0:
-        s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    if with_points:
+        s.pgSetCamProjectEdges(k1, 11 + d, prob["vp"], prob["vl"], zl, prob["omega_l"], prob["intrinsics"])
+        s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
+        if huber_delta > 0:
+            s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    for k, typ, vi, vj, e in pose_sets:
+        s.pgSetCamEdges(k, typ, vi, vj, e["meas"], e["info"])
+        if typ == 16 and cam_huber_delta > 0:
+            s.setRobustKernel(k, capi.KERNEL_HUBER, cam_huber_delta)
     s.landmark_sets = (k0, k1)
     s.pose_set = k0
     return s, DevicePoseGraph(s)

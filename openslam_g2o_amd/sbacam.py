@@ -6,12 +6,18 @@
   EdgeProjectP2MC / EdgeProjectP2SC::computeError        g2o/types/sba/types_sba.h:170-192, :209-247
   EdgeProjectP2SC / EdgeProjectP2MC::linearizeOplus      g2o/types/sba/types_sba.cpp:249-328, :334-403 (analytic)
   VertexSBAPointXYZ::oplusImpl                           g2o/types/sba/types_sba.h:151-155
-  Eigen: toRotationMatrix, quaternion product
+  SE3Quat(Vector7d), operator*, inverse, normalizeRotation g2o/types/slam3d/se3quat.h:86-93, :104-110, :123-128, :280-285
+  EdgeSBACam::computeError / setMeasurement              g2o/types/sba/types_sba.h:294-310
+  EdgeSBAScale::computeError                             g2o/types/sba/types_sba.h:347-353
+  BaseBinaryEdge::linearizeOplus (numeric branch)        g2o/core/base_binary_edge.hpp:132-201 (delta = 1e-9, central)
+  Eigen: toRotationMatrix, quaternion product, quaternion * vector, coeffs / norm (squared norm summed x, y, z, w)
 
 ONE body of formulas, written operation for operation and generic over the arithmetic F, as openslam_g2o_amd/sim3.py is: FP64
-below (Python floats = IEEE doubles), tests/sbacam_helpers.py adds mpmath at 60 digits.  F supplies num(x) and sqrt.  There is
-no data-dependent branch in any of it.  The device kernels (csrc/pg_cam_project.inc) state the same operations in HIP, in the
-same order and without contraction to fused multiply-adds, and share no code with this file.
+below (Python floats = IEEE doubles), tests/sbacam_helpers.py adds mpmath at 60 digits.  F supplies num(x) and sqrt.  The
+projection formulas have no data-dependent branch; the pose-pose edges (EdgeSBACam) have one, the sign flip of
+normalizeRotation, which is appended to `trace` when given.  The device kernels (csrc/pg_cam_project.inc,
+csrc/pg_sbacam_edge.inc) state the same operations in HIP, in the same order and without contraction to fused multiply-adds,
+and share no code with this file.
 
 Layouts as in the C ABI: a camera is 7 doubles (tx, ty, tz, qx, qy, qz, qw), camera-to-world (SE3Quat::toVector, VertexCam::write);
 its intrinsics are (fx, fy, cx, cy, baseline); a step is (dt[3], dq[3]); the Jacobian of an edge is (Jcam d x 6, Jpoint d x 3),
@@ -20,7 +26,7 @@ _jacobianOplusXi).  d = 2 (EdgeProjectP2MC) or 3 (EdgeProjectP2SC, third row = u
 is no guard for a point on or behind the image plane."""
 import numpy as np
 
-from .sim3 import FP64, _vec, q_mul, q_to_R, to_f64  # noqa: F401
+from .sim3 import DELTA64, FP64, _vec, q_mul, q_rot, q_to_R, to_f64  # noqa: F401
 
 IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)
 
@@ -92,6 +98,113 @@ def oplus(F, cam, x):
     p = q_mul(cam[3:7], qr)
     norm = F.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3])
     return [cam[i] + x[i] for i in range(3)] + [v / norm for v in p]
+
+
+# ------------------------------------------------------------------------------------------------ EdgeSBACam / EdgeSBAScale
+def normalize_rotation(F, q, trace=None):
+    """SE3Quat::normalizeRotation: coeffs *= -1 when w < 0, then coeffs / norm."""
+    flip = q[3] < 0
+    if trace is not None:
+        trace.append(("flip", bool(flip)))
+    if flip:
+        m1 = F.num(-1.0)
+        q = [v * m1 for v in q]
+    norm = F.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3])
+    return [v / norm for v in q]
+
+
+def se3_mul(F, a, b, trace=None):
+    """SE3Quat::operator*: t = a.t + a.q * b.t, q = a.q b.q, normalizeRotation."""
+    rt = q_rot(a[3:7], b[0:3])
+    return [a[i] + rt[i] for i in range(3)] + normalize_rotation(F, q_mul(a[3:7], b[3:7]), trace)
+
+
+def se3_inverse(F, a):
+    """SE3Quat::inverse: q = conjugate, t = q * (t * -1); nothing is normalised."""
+    m1 = F.num(-1.0)
+    q = [-a[3], -a[4], -a[5], a[6]]
+    return q_rot(q, [a[0] * m1, a[1] * m1, a[2] * m1]) + q
+
+
+def inverse_measurement(F, z, trace=None):
+    """EdgeSBACam::setMeasurement of SE3Quat(Vector7d z): normalizeRotation, then the inverse."""
+    z = _vec(F, z)
+    return se3_inverse(F, z[0:3] + normalize_rotation(F, z[3:7], trace))
+
+
+def cam_edge_error(F, ci, cj, zinv, trace=None):
+    """EdgeSBACam::computeError: delta = Zinv * (Ci^-1 * Cj); e = (delta.t, delta.q.xyz)."""
+    ci, cj, zinv = _vec(F, ci), _vec(F, cj), _vec(F, zinv)
+    d = se3_mul(F, zinv, se3_mul(F, se3_inverse(F, ci), cj, trace), trace)
+    return d[0:6]
+
+
+def _numeric(F, error, cams, fixed, d):
+    """BaseBinaryEdge::linearizeOplus, numeric branch: column c of side v = scalar * (e(C_v (+) delta u_c) - e(C_v (+) -delta u_c))
+    through oplus; the block of a fixed vertex is zeros.  Returns (J0, J1) as row lists J[row][col]."""
+    delta = F.num(DELTA64)
+    scalar = F.num(1.0) / (F.num(2.0) * delta)
+    zero = F.num(0.0)
+    out = []
+    for side in range(2):
+        J = [[zero] * 6 for _ in range(d)]
+        if not fixed[side]:
+            for c in range(6):
+                pair = []
+                for sign in (delta, -delta):
+                    moved = list(cams)
+                    moved[side] = oplus(F, cams[side], [sign if i == c else zero for i in range(6)])
+                    pair.append(error(moved[0], moved[1]))
+                for r in range(d):
+                    J[r][c] = scalar * (pair[0][r] - pair[1][r])
+        out.append(J)
+    return out
+
+
+def cam_edge_jacobians(F, ci, cj, zinv, fixed=(False, False)):
+    """The numeric Jacobians of EdgeSBACam, 6 x 6 per side."""
+    return _numeric(F, lambda a, b: cam_edge_error(F, a, b, zinv), (_vec(F, ci), _vec(F, cj)), fixed, 6)
+
+
+def scale_edge_error(F, ci, cj, z):
+    """EdgeSBAScale::computeError: z - |t_j - t_i| (squared norm summed x, y, z)."""
+    ci, cj = _vec(F, ci), _vec(F, cj)
+    d = [cj[i] - ci[i] for i in range(3)]
+    return [F.num(z) - F.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])]
+
+
+def scale_edge_jacobians(F, ci, cj, z, fixed=(False, False)):
+    """The numeric Jacobians of EdgeSBAScale, 1 x 6 per side, every column evaluated: a rotation step does not reach t, so both
+    evaluations of columns 3-5 read the same operands and those columns are exactly zero."""
+    return _numeric(F, lambda a, b: scale_edge_error(F, a, b, z), (_vec(F, ci), _vec(F, cj)), fixed, 1)
+
+
+def pose_edges(F, cams, vi, vj, meas, hidx=None, scale=False, jac=True, trace=None):
+    """err [n][d] and (jac) J0, J1 [n][d x 6] column-major of a whole EdgeSBACam (d = 6, meas [n][7] = the MEASUREMENTS, inverted
+    here as the binding does) or EdgeSBAScale (scale=True: d = 1, meas [n]) list, rounded to fp64.  hidx: the cameras' hessian
+    indices (-1 = fixed, block of zeros); None = all free."""
+    n, d = len(vi), 1 if scale else 6
+    err, J0, J1 = np.zeros((n, d)), np.zeros((n, 6 * d)), np.zeros((n, 6 * d))
+    meas = np.asarray(meas, np.float64).reshape(n, -1)
+    for k in range(n):
+        a, b = int(vi[k]), int(vj[k])
+        fixed = (False, False) if hidx is None else (hidx[a] < 0, hidx[b] < 0)
+        if scale:
+            err[k] = to_f64(scale_edge_error(F, cams[a], cams[b], meas[k, 0]))
+            J = scale_edge_jacobians(F, cams[a], cams[b], meas[k, 0], fixed) if jac else None
+        else:
+            zinv = inverse_measurement(F, meas[k], trace)
+            err[k] = to_f64(cam_edge_error(F, cams[a], cams[b], zinv, trace))
+            J = cam_edge_jacobians(F, cams[a], cams[b], zinv, fixed) if jac else None
+        if jac:
+            J0[k] = to_f64([J[0][r][c] for c in range(6) for r in range(d)])
+            J1[k] = to_f64([J[1][r][c] for c in range(6) for r in range(d)])
+    return (J0, J1, err) if jac else err
+
+
+def inverse_measurements(F, meas):
+    """[n][7] inverse measurements of an EdgeSBACam list, rounded to fp64: what the binding stores."""
+    return np.array([to_f64(inverse_measurement(F, z)) for z in np.asarray(meas, np.float64).reshape(-1, 7)]).reshape(-1, 7)
 
 
 # ------------------------------------------------------------------------------------------------ whole edge lists

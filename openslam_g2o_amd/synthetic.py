@@ -734,7 +734,8 @@ def _sbacam_project(cams, X, vp, vl, intr, stereo):
     return np.stack(cols, axis=1), pc[:, 2]
 
 
-def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_noise=0.2):
+def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_noise=0.2, cam_edges=None, scale_edges=None,
+                   sigma_trans=0.01, sigma_rot=0.002, sigma_scale=0.01):
     """Bundle adjustment in the reference's SBA format (BlockSolver_6_3): VertexCam cameras (camera-to-world, (tx, ty, tz, qx,
     qy, qz, qw)) on a closed trajectory -- a circle of radius 4 with a vertical wave -- looking at the centre, observing
     VertexSBAPointXYZ points of a ball of radius 1 around it through EdgeProjectP2MC (stereo=False, measurement (u, v)) or
@@ -745,8 +746,15 @@ def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_
     types_sba.cpp:204-244).  Initial cameras: the true ones moved by 0.05 * N(0, 1) in t and a small quaternion 0.02 * N(0, 1)
     through SBACam::update; initial points: the true ones + 0.02 * N(0, 1).  The first camera is fixed at its true pose.
     Deterministic from seed.
+    cam_edges = k (an int; None: none) adds EdgeSBACam constraints: odometry between consecutive cameras (i, i + 1) and, for
+    k >= 2, loop edges (i, (i + k) mod n_cams) for i = 0, k, 2k, ...; the measurement is the true relative pose Ci^-1 Cj moved by
+    sigma_trans * N(0, 1) in t and a small quaternion sigma_rot * N(0, 1) through SBACam::update, information = diag(1 /
+    sigma_trans^2 x 3, 1 / sigma_rot^2 x 3).  scale_edges = m (None: none) adds m EdgeSBAScale constraints between cameras half a
+    trajectory apart: the true distance + sigma_scale * N(0, 1), information 1 / sigma_scale^2.  n_points = 0 gives a pure
+    camera graph (no points, no observations).  With both at None the problem is the one of earlier versions, bit for bit.
     Returns est [n_cams][7], est_true, points [L][3], points_true, hidx, pt_hidx, vp, vl, zl [m][2|3], omega_l [m][4|9],
-    intrinsics [n_cams][5] = (fx, fy, cx, cy, baseline), nP, nL, stereo."""
+    intrinsics [n_cams][5] = (fx, fy, cx, cy, baseline), nP, nL, stereo and, when asked for, cam_edges = dict(vi, vj, meas
+    [n][7], info [n][36]), scale_edges = dict(vi, vj, meas [n], info [n])."""
     from . import sbacam as SB
     from .g2o_io import _R_to_quat
     from .sim3 import FP64 as F
@@ -783,9 +791,32 @@ def make_sbacam_ba(n_cams, n_points, obs_per_point, stereo=False, seed=0, pixel_
         depth = _sbacam_project(cams, X, vp, vl, intr, stereo)[1]
         if not ((depth >= 2.5) & (depth <= 5.5)).all():
             raise ValueError("make_sbacam_ba: an observed depth outside 2.5 ... 5.5 camera units (%g ... %g)" % (depth.min(), depth.max()))
-    return dict(est=est, est_true=est_true, points=pts, points_true=pts_true, hidx=hidx,
-                pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
-                omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)), intrinsics=intr, nP=nP, nL=n_points, stereo=bool(stereo))
+    out = dict(est=est, est_true=est_true, points=pts, points_true=pts_true, hidx=hidx,
+               pt_hidx=(nP + np.arange(n_points)).astype(np.int32), vp=vp, vl=vl, zl=zl,
+               omega_l=np.tile(np.eye(d).reshape(1, d * d), (m, 1)), intrinsics=intr, nP=nP, nL=n_points, stereo=bool(stereo))
+    if cam_edges is not None:
+        k = int(cam_edges)
+        pairs = [(i, i + 1) for i in range(n_cams - 1)]
+        if k >= 2:
+            pairs += [(i, (i + k) % n_cams) for i in range(0, n_cams, k) if (i + k) % n_cams != i]
+        vi, vj = np.array([a for a, _ in pairs], np.int32), np.array([b for _, b in pairs], np.int32)
+        ne = len(pairs)
+        noise = np.concatenate([sigma_trans * np.stack([rng.normal(70 + c, ne) for c in range(3)], axis=1),
+                                sigma_rot * np.stack([rng.normal(73 + c, ne) for c in range(3)], axis=1)], axis=1)
+        meas = np.zeros((ne, 7))
+        for e in range(ne):
+            rel = SB.se3_mul(F, SB.se3_inverse(F, list(est_true[vi[e]])), list(est_true[vj[e]]))
+            meas[e] = SB.oplus(F, rel, noise[e])
+        info = np.diag([1.0 / sigma_trans ** 2] * 3 + [1.0 / sigma_rot ** 2] * 3).reshape(1, 36)
+        out["cam_edges"] = dict(vi=vi, vj=vj, meas=meas, info=np.tile(info, (ne, 1)))
+    if scale_edges is not None:
+        ns = int(scale_edges)
+        vi = (np.arange(ns, dtype=np.int32) * max(1, n_cams // max(1, 2 * ns))) % n_cams
+        vj = ((vi + n_cams // 2) % n_cams).astype(np.int32)
+        dist = np.linalg.norm(est_true[vj, 0:3] - est_true[vi, 0:3], axis=1)
+        out["scale_edges"] = dict(vi=vi.astype(np.int32), vj=vj, meas=dist + sigma_scale * rng.normal(76, ns),
+                                  info=np.full(ns, 1.0 / sigma_scale ** 2))
+    return out
 
 
 _GICP_PLANES = np.array([[1.0, 0.1, 0.2, 6.0], [0.1, 0.5, 1.0, 2.5], [-0.3, 0.2, 1.0, 3.0], [-1.0, 0.3, 0.4, 5.0], [0.2, 0.6, -1.0, 2.0]])
