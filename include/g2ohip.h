@@ -458,8 +458,40 @@ int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_ver
  * on the fused path of the projection set too); chi2 and robust weights go the generic way (g2ohip_set_robust_kernel(_per_edge) on
  * the set); the fused assembly and back-substitution of the projection set stay in place, since the set touches no landmark.
  * NOT covered: the g2o plugin adapter (EdgeSE3Expmap stays on its host path there), a pose set without a projection set (a pure
- * VertexSE3Expmap pose graph), more than one pose set per handle, EdgeProjectPSI2UV, sharded solves, fused kernels for the set. */
+ * VertexSE3Expmap pose graph), more than one pose set per handle, sharded solves, fused kernels for the set. */
 int g2ohip_ba_set_pose_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info);
+/* The projection slot bound to ANCHORED INVERSE-DEPTH observations: EdgeProjectPSI2UV (g2o/types/sba/types_six_dof_expmap.h:158-178,
+ * types_six_dof_expmap.cpp:173-233; what g2o/examples/ba_anchored_inverse_depth runs), a THREE-vertex edge: vertex 0 the point
+ * psi = (x / z, y / z, 1 / z) in the frame of its anchor keyframe (an entry of `points`), vertex 1 the observing pose T =
+ * cams[cam_vertex[k]], vertex 2 the anchor pose A = cams[anchor_vertex[k]].  With x_a = (psi0, psi1, 1) / psi2 and y = T A^-1 x_a:
+ * e = meas - (f y0 / y2 + cx, f y1 / y2 + cy); the Jacobians are the reference's analytic ones (J_point = -Jcam [r1, r2, -R_ca x_a] /
+ * psi2, J_pose = -Jcam [-skew(y) | I], J_anchor = Jcam R_ca [-skew(x_a) | I]).  Like the reference there is no guard for psi2 == 0 or
+ * y2 <= 0.  The edge is bound as the three binary sets g2ohip_set_edge_set_parts documents for three vertices, all with error_dim 2 and
+ * the same number of edges, on a (6, 3) solver:
+ *   set_point_pose    (v0 = point, v1 = pose)    parts 0
+ *   set_point_anchor  (v0 = point, v1 = anchor)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_VERTEX1 | G2OHIP_PART_NO_CHI2
+ *   set_pose_anchor   (v0 = pose,  v1 = anchor)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_CHI2
+ * meas [n][2], information [n][2x2] (NULL = identity, written on the device).  The three sets are bound and released as ONE group and
+ * share their Jacobians, information and errors on the device (g2ohip_copy_edge_data of each returns its pair's two Jacobians).  They
+ * occupy the projection slot: a later g2ohip_ba_set_edges* / g2ohip_ba_set_stereo_edges replaces the binding (the three sets are
+ * then without edge data until g2ohip_set_edge_data feeds them), and this call replaces theirs; the EdgeSE3Expmap slot beside it
+ * keeps working.  Always the generic assembly (option "ba_fused" is ignored), do_schur 0 / 1, every linear_solver and use_graph.
+ * After g2ohip_build_structure (G2OHIP_ERR_STATE otherwise; so is a set that carries per-edge robust kernels at the binding).
+ * G2OHIP_ERR_ARG: a bad set id or the same id twice, wrong dimensions, parts or unequal edge counts, a null index or meas array, a
+ * non-finite value or focal_length == 0, an index outside the estimate tables, a hessian index that differs from the sets'
+ * (cam_hidx, num_poses + point_hidx, -1 = fixed), one of the sets being the bound pose-edge set.  A rejected call leaves the previous
+ * binding usable; g2ohip_ba_set_estimates with changed tables validates the binding again, anchors included;
+ * g2ohip_clear_edge_sets drops it.
+ * THE ANCHOR'S OWN OBSERVATION (cam_vertex[k] == anchor_vertex[k], which the reference example creates): the error depends on psi
+ * alone and the two camera Jacobians cancel exactly.  The reference maps both sides onto one diagonal block and adds the unsymmetric
+ * term A1' Omega A2 there (base_multi_edge.hpp:190-208); HERE such an edge must carry -1 on every camera side of all three sets
+ * (G2OHIP_ERR_ARG otherwise) and contributes to its point alone -- a deliberate deviation from the reference.
+ * Robust kernels: the generic assembly weighs each set by its own kernel, so the caller sets the SAME kernel -- set-level, or per
+ * edge after the binding -- on all three sets.
+ * NOT covered: the g2o plugin adapter, XYZ and inverse-depth points in one graph, edge classes, sharded solves. */
+int g2ohip_ba_set_inverse_depth_edges(g2ohip_solver* s, int set_point_pose, int set_point_anchor, int set_pose_anchor,
+                                      const int32_t* cam_vertex, const int32_t* anchor_vertex, const int32_t* point_vertex,
+                                      const double* meas, const double* info, double focal_length, double cx, double cy);
 /* setEstimate for every vertex + the index mapping: cam_hidx[v] = hessianIndex (-1 fixed),
  * point_hidx[v] = landmark index (0-based, i.e. hessianIndex - num_poses) or -1. */
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,

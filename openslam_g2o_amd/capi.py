@@ -54,7 +54,7 @@ EXPORTS = [
     "g2ohip_solve_schur", "g2ohip_solve_reduced", "g2ohip_solve_back_substitute", "g2ohip_ls_create",
     "g2ohip_ls_destroy", "g2ohip_ls_init", "g2ohip_ls_solve", "g2ohip_ls_solve_pattern", "g2ohip_ls_get_stats", "g2ohip_ls_set_option",
     "g2ohip_kernel_slots", "g2ohip_kernel_name", "g2ohip_kernel_time", "g2ohip_add_schur_pattern", "g2ohip_set_edge_set_parts",
-    "g2ohip_set_lambda_split", "g2ohip_host_register", "g2ohip_host_unregister", "g2ohip_ba_set_edges", "g2ohip_ba_set_edges_classes", "g2ohip_ba_set_stereo_edges", "g2ohip_ba_set_pose_edges", "g2ohip_ba_set_estimates", "g2ohip_ba_get_estimates", "g2ohip_ba_get_estimates_of", "g2ohip_ba_fetch_estimates_begin", "g2ohip_ba_fetch_estimates_wait",
+    "g2ohip_set_lambda_split", "g2ohip_host_register", "g2ohip_host_unregister", "g2ohip_ba_set_edges", "g2ohip_ba_set_edges_classes", "g2ohip_ba_set_stereo_edges", "g2ohip_ba_set_pose_edges", "g2ohip_ba_set_inverse_depth_edges", "g2ohip_ba_set_estimates", "g2ohip_ba_get_estimates", "g2ohip_ba_get_estimates_of", "g2ohip_ba_fetch_estimates_begin", "g2ohip_ba_fetch_estimates_wait",
     "g2ohip_ba_linearize", "g2ohip_ba_update", "g2ohip_ba_push", "g2ohip_ba_pop", "g2ohip_ba_discard_top",
     "g2ohip_set_partition", "g2ohip_solve_reduced_local", "g2ohip_solve_reduced_shared", "g2ohip_solve_reduced_finish",
     "g2ohip_schur_operator_prepare", "g2ohip_schur_operator_apply", "g2ohip_solve_async", "g2ohip_trial_stats_begin", "g2ohip_trial_stats", "g2ohip_solve_reduced_finish_async", "g2ohip_exchange_setup", "g2ohip_exchange_pack", "g2ohip_exchange_unpack", "g2ohip_exchange_status",
@@ -153,6 +153,7 @@ def load():
     L.g2ohip_ba_set_edges_classes.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_ba_set_stereo_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_double, C.c_double, C.c_double, C.c_double]
     L.g2ohip_ba_set_pose_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_ba_set_inverse_depth_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_double, C.c_double, C.c_double]
     L.g2ohip_ba_set_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_ba_get_estimates.argtypes = [vp, c_dbl_p, c_dbl_p]
     L.g2ohip_ba_get_estimates_of.argtypes = [vp, C.c_int, c_int_p, c_dbl_p, C.c_int, c_int_p, c_dbl_p]
@@ -622,6 +623,21 @@ class HipBlockSolver:
         if len(a) != n or len(b) != n or m.size != 12 * n or (inf is not None and inf.size != 36 * n):
             raise ValueError("baSetPoseEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
         _check(self.L.g2ohip_ba_set_pose_edges(self.h, set_id, _ip(a), _ip(b), _dp(m), None if inf is None else _dp(inf)), "baSetPoseEdges")
+
+    def baSetInverseDepthEdges(self, set_point_pose, set_point_anchor, set_pose_anchor, cam_vertex, anchor_vertex, point_vertex, meas,
+                               info=None, f=1000.0, cx=320.0, cy=240.0):
+        """EdgeProjectPSI2UV observations (point psi, observing pose, anchor pose) in the BA front end's projection slot
+        (g2ohip_ba_set_inverse_depth_edges): the three binary sets of the edge's vertex pairs, added with error_dim 2 and the
+        parts 0, PART_NO_VERTEX0 | PART_NO_VERTEX1 | PART_NO_CHI2 and PART_NO_VERTEX0 | PART_NO_CHI2 before buildStructure;
+        cam_vertex / anchor_vertex index the camera table, point_vertex the point table; meas [n][2], info [n][2x2] or None
+        (identity).  A robust kernel goes on all three sets."""
+        cv, av, pv, m = _i32(cam_vertex), _i32(anchor_vertex), _i32(point_vertex), _f64(meas)
+        inf = None if info is None else _f64(info)
+        n = self._set_sizes[set_point_pose]
+        if len(cv) != n or len(av) != n or len(pv) != n or m.size != 2 * n or (inf is not None and inf.size != 4 * n):
+            raise ValueError("baSetInverseDepthEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_point_pose, n))
+        _check(self.L.g2ohip_ba_set_inverse_depth_edges(self.h, set_point_pose, set_point_anchor, set_pose_anchor, _ip(cv), _ip(av), _ip(pv),
+                                                        _dp(m), None if inf is None else _dp(inf), f, cx, cy), "baSetInverseDepthEdges")
 
     def baSetEstimates(self, cams, cam_hidx, points, point_hidx):
         cams, points = _f64(cams), _f64(points)

@@ -98,6 +98,16 @@ class HipBlockSolver {
   bool baSetPoseEdges(int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
     return ok(g2ohip_ba_set_pose_edges(h_, set, vi, vj, meas, info), "baSetPoseEdges");
   }
+  // EdgeProjectPSI2UV observations (point psi, observing pose, anchor pose) in the projection slot (g2ohip_ba_set_inverse_depth_edges):
+  // the three binary sets of the edge's vertex pairs -- (point, pose), (point, anchor), (pose, anchor), errorDim 2, parts as the
+  // header lists them -- bound as one group; camVertex / anchorVertex index the camera table; info == nullptr: identity.  A robust
+  // kernel goes on all three sets.
+  bool baSetInverseDepthEdges(int setPointPose, int setPointAnchor, int setPoseAnchor, const int32_t* camVertex, const int32_t* anchorVertex,
+                              const int32_t* pointVertex, const double* meas, const double* info, double focalLength, double cx, double cy) {
+    return ok(g2ohip_ba_set_inverse_depth_edges(h_, setPointPose, setPointAnchor, setPoseAnchor, camVertex, anchorVertex, pointVertex, meas,
+                                                info, focalLength, cx, cy),
+              "baSetInverseDepthEdges");
+  }
   // EdgeSE3PointXYZDepth (type 5) / EdgeSE3PointXYZDisparity (type 6) observations with one ParameterCamera, kept on the device
   // beside an EdgeSE3 pose set of g2ohip_pg_set_edges (handle()): offset isometry [12] or nullptr, kcam = fx, fy, cx, cy
   bool pgSetLandmarkCameraEdges(int set, int type, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas,

@@ -144,6 +144,11 @@ class BlockSolver {
                            double cx, double cy, double baseline);
   // a second slot beside it: one set of EdgeSE3Expmap constraints between two cameras (ba_pose_edge.inc); info == nullptr: identity
   void ba_set_pose_edges(int set, const int* vi, const int* vj, const double* meas, const double* info);
+  // the projection slot bound to THREE-vertex observations (EdgeProjectPSI2UV: point, observing pose, anchor pose) as three binary
+  // sets of the same edge count: ba_psi.inc; info == nullptr: identity
+  void ba_set_inverse_depth_edges(int set_point_pose, int set_point_anchor, int set_pose_anchor, const int* cam_vertex,
+                                  const int* anchor_vertex, const int* point_vertex, const double* meas, const double* info, double f,
+                                  double cx, double cy);
   void ba_set_estimates(int n_cams, const double* cams, const int* cam_hidx, int n_points, const double* points, const int* point_hidx);
   void ba_get_estimates(double* cams, double* points);
   void ba_get_estimates_of(int n_cams, const int* cam_idx, double* cams, int n_points, const int* point_idx, double* points);   // selected vertices
@@ -344,6 +349,10 @@ class BlockSolver {
   void mf_prepare_lists();
   void ba_validate_edges(const struct EdgeSet& es, const int* cam_v, const int* pt_v, size_t n, const int* cam_hidx, int nc,
                          const int* pt_hidx, int np) const;
+  void ba_validate_psi_edges(const EdgeSet& a, const EdgeSet& b, const EdgeSet& c, const int* cam_v, const int* anchor_v, const int* pt_v,
+                             size_t n, const int* cam_hidx, int nc, const int* pt_hidx, int np) const;
+  void ba_psi_release();
+  void ba_psi_alias();
   bool ba_recompute_ok() const;
   bool ba_skip_hpl_ok() const;
   bool ba_fuse_ll_ok() const;
@@ -440,6 +449,14 @@ class BlockSolver {
     std::vector<int> h_pvi, h_pvj;   // host copies: index validation (pg_validate)
     DevBuf<double> pose_meas;
     bool pose_jac_valid = false;
+    // The projection slot bound to EdgeProjectPSI2UV (ba_set_inverse_depth_edges, ba_psi.inc): `set` is the (point, pose) set,
+    // psi_pa the (point, anchor) set, psi_ca the (pose, anchor) set -- one group, bound and released together.  anchor_v indexes
+    // `cams` like cam_v.  `set` owns J_point (own_J0), J_pose (own_J1), information and errors, psi_ca owns J_anchor (own_J1); every
+    // other J0 / J1 / omega / err pointer of the three aliases one of those (ba_psi_alias).  Always the generic path.
+    bool psi = false;
+    int psi_pa = -1, psi_ca = -1;
+    DevBuf<int> anchor_v;
+    std::vector<int> h_anchor_v;   // host copy: index validation (ba_validate_psi_edges)
   } ba_;
   // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
   // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks

@@ -2213,6 +2213,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_gicp.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
+#include "ba_psi.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -2477,7 +2478,10 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
       pg_ = PgFrontEnd();
       pg_.fix_scale = fix_scale;
     }
-    if (set == ba_.set) ba_.set = -1;
+    if (set == ba_.set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca))) {
+      ba_psi_release();   // (an inverse-depth binding goes as one group)
+      ba_.set = -1;
+    }
     // per-edge robust kernels cover the old edge count: the new edges get "none" (kind 0) until set_robust_kernel_per_edge is
     // called again -- the array is extended on the device so that no kernel reads past its end
     if (es.rk.p) {
@@ -3188,7 +3192,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == ba_.pose_set || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
+  const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
                              set == pg_.cam_set || set == pg_.scale_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
@@ -3233,7 +3237,7 @@ void BlockSolver::set_robust_kernel_per_edge(int set, const int* kind, const dou
     return;
   }
   if (!delta) throw ArgFailure("set_robust_kernel_per_edge: null delta array");
-  if (set == ba_.set && ba_.set >= 0 && !ba_.stereo)   // (a stereo set is assembled by the generic kernels, which read es.rk, and so does its producer)
+  if (set == ba_.set && ba_.set >= 0 && !ba_.stereo && !ba_.psi)   // (a stereo or inverse-depth set is assembled by the generic kernels, which read es.rk)
     throw StateFailure("set_robust_kernel_per_edge: the set is bound to the BA front end; per-edge kernels go through ba_set_edges_classes there");
   std::vector<double> h((size_t)es.n * 2);
   for (int k = 0; k < es.n; ++k) {
@@ -3531,7 +3535,7 @@ double BlockSolver::chi2() {
     if (es.n == 0 || (es.parts & 4)) continue;   // (parts bit 4: the edges of this set are counted by another one)
     if (!es.has_err) throw StateFailure("chi2: edge data missing");
     int nblocks = std::min(1024, grid_for(es.n));
-    if (ba_.err_valid && esp.get() == sets_[ba_.set].get()) {   // partial sums left by ba_linearize (same values trial_stats reads)
+    if (ba_.err_valid && !ba_.psi && esp.get() == sets_[ba_.set].get()) {   // partial sums left by ba_linearize (same values trial_stats reads)
       std::vector<double> h(kMaxBlocks);
       G2OHIP_HIP_CHECK(hipMemcpyAsync(h.data(), d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks, kMaxBlocks * sizeof(double), hipMemcpyDeviceToHost, st_));
       G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
@@ -4679,7 +4683,7 @@ void BlockSolver::trial_stats_begin(double lambda) {
     if (es.n == 0 || (es.parts & 4)) continue;
     if (!es.has_err) throw StateFailure("trial_stats: edge data missing");
     nblk[k + 1] = std::min(kMaxBlocks, grid_for(es.n));
-    if (ba_.err_valid && (int)k == ba_.set) {   // already there: ba_linearize left this set's partial sums in its slot
+    if (ba_.err_valid && !ba_.psi && (int)k == ba_.set) {   // already there: ba_linearize left this set's partial sums in its slot
       nblk[k + 1] = kMaxBlocks;
       continue;
     }
@@ -5014,6 +5018,7 @@ void BlockSolver::ba_set_edges_classes(int set, const int* cam_vertex, const int
       throw ArgFailure("ba_set_edges_classes: edge classes need the fused path (one observation per (pose, landmark) pair, no fixed landmark)");
   }
   lap("validation + Hpl block per edge");
+  ba_psi_release();
   ba_.set = set;
   ba_.n_edges = es.n;
   ba_.f = f; ba_.cx = cx; ba_.cy = cy;
@@ -5224,6 +5229,7 @@ void BlockSolver::ba_set_stereo_edges(int set, const int* cam_vertex, const int*
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   ba_validate_edges(es, cam_vertex, point_vertex, n, ba_.cams.h_hidx.data(), ba_.cams.n, ba_.pts.h_hidx.data(), ba_.pts.n);
+  ba_psi_release();
   ba_.set = set;
   ba_.n_edges = es.n;
   ba_.f = f; ba_.cx = cx; ba_.cy = cy;
@@ -5325,6 +5331,170 @@ void BlockSolver::ba_set_pose_edges(int set, const int* vi, const int* vj, const
   es.has_err = false;
   G2OHIP_HIP_CHECK(hipGetLastError());
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// ---- ... bound to anchored inverse-depth observations: EdgeProjectPSI2UV (ba_psi.inc) -----------------------------------------
+// A THREE-vertex edge (point psi, observing pose, anchor pose) as the three binary sets g2ohip_set_edge_set_parts documents for
+// three vertices, all of the same edge count and error dimension 2:
+//   set_pp  (point, pose)    dims (3, 6), parts 0                                  point and pose terms, Hpl(pose, point), chi2
+//   set_pa  (point, anchor)  dims (3, 6), parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  Hpl(anchor, point)
+//   set_ca  (pose, anchor)   dims (6, 6), parts NO_VERTEX0 | NO_CHI2               anchor terms, Hpp(pose, anchor)
+// They occupy the projection slot as ONE group: ba_linearize writes J_point / J_pose / information / errors into set_pp's buffers
+// and J_anchor into set_ca's own_J1, and every other pointer of the three aliases one of those (30 + 2 doubles per edge leave the
+// producer, not 60 + 6).  Always the generic path (fused_ok = false, the fused tables of an earlier mono binding are dropped).  A
+// later ba_set_edges* / ba_set_stereo_edges releases the whole group (ba_psi_release), this call releases theirs; the EdgeSE3Expmap
+// slot beside it stays.  An edge whose observing pose is its anchor must carry -1 on EVERY camera side of the three sets: its
+// error depends on psi alone and its two camera Jacobians cancel (DEVIATION from the reference, which adds the unsymmetric term
+// A1' Omega A2 to the shared diagonal block, base_multi_edge.hpp:190-208).  Robust kernels: the caller sets the same kernel on all
+// three sets (the generic assembly weighs each set by its own).  Validate, then commit.
+void BlockSolver::ba_set_inverse_depth_edges(int set_pp, int set_pa, int set_ca, const int* cam_vertex, const int* anchor_vertex,
+                                             const int* point_vertex, const double* meas, const double* info, double f, double cx,
+                                             double cy) {
+  invalidate_graphs();
+  require_structure();
+  const int ids[3] = {set_pp, set_pa, set_ca};
+  for (int id : ids)
+    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (set_pp == set_pa || set_pp == set_ca || set_pa == set_ca) throw ArgFailure("ba_set_inverse_depth_edges: the three sets must differ");
+  for (int id : ids)
+    if (id == ba_.pose_set) throw ArgFailure("ba_set_inverse_depth_edges: a set is bound as the pose-edge set (ba_set_pose_edges)");
+  EdgeSet &es = *sets_[set_pp], &ea = *sets_[set_pa], &ec = *sets_[set_ca];
+  if (p_ != 6 || l_ != 3 || es.unary || ea.unary || ec.unary || es.d != 2 || ea.d != 2 || ec.d != 2 || es.dim0 != 3 || es.dim1 != 6 ||
+      ea.dim0 != 3 || ea.dim1 != 6 || ec.dim0 != 6 || ec.dim1 != 6)
+    throw ArgFailure("ba_set_inverse_depth_edges: the sets must be (point, pose), (point, anchor), (pose, anchor) with d=2 on a (6, 3) solver");
+  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
+    throw ArgFailure("ba_set_inverse_depth_edges: parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
+  if (ea.n != es.n || ec.n != es.n) throw ArgFailure("ba_set_inverse_depth_edges: the three sets must hold the same number of edges");
+  if (!cam_vertex || !anchor_vertex || !point_vertex || !meas) throw ArgFailure("ba_set_inverse_depth_edges: null array");
+  if (!std::isfinite(f) || !std::isfinite(cx) || !std::isfinite(cy)) throw ArgFailure("ba_set_inverse_depth_edges: non-finite camera parameters");
+  if (f == 0.0) throw ArgFailure("ba_set_inverse_depth_edges: the focal length must not be zero");
+  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
+    throw StateFailure("ba_set_inverse_depth_edges: a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (!std::isfinite(meas[2 * k]) || !std::isfinite(meas[2 * k + 1])) throw ArgFailure("ba_set_inverse_depth_edges: non-finite measurement in edge " + std::to_string(k));
+    if (info)
+      for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(info[4 * k + i])) throw ArgFailure("ba_set_inverse_depth_edges: non-finite information in edge " + std::to_string(k));
+    if (cam_vertex[k] < 0 || anchor_vertex[k] < 0 || point_vertex[k] < 0) throw ArgFailure("ba_set_inverse_depth_edges: negative vertex index in edge " + std::to_string(k));
+  }
+  ba_validate_psi_edges(es, ea, ec, cam_vertex, anchor_vertex, point_vertex, n, ba_.cams.h_hidx.data(), ba_.cams.n, ba_.pts.h_hidx.data(), ba_.pts.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  // commit: whatever held the slot leaves it, with the data the device wrote for it
+  if (ba_.set >= 0 && !ba_.psi && ba_.set != set_pp && ba_.set != set_pa && ba_.set != set_ca) {
+    EdgeSet& old = *sets_[ba_.set];
+    old.has_data = old.has_err = false;
+  }
+  ba_psi_release();
+  ba_.set = set_pp;
+  ba_.psi = true;
+  ba_.psi_pa = set_pa;
+  ba_.psi_ca = set_ca;
+  ba_.n_edges = es.n;
+  ba_.f = f; ba_.cx = cx; ba_.cy = cy;
+  ba_.stereo = false;
+  ba_.baseline = 0;
+  ba_.n_classes = 1;
+  ba_.h_ctab.clear();
+  ba_.ctab.release();
+  ba_.h_cam_v.assign(cam_vertex, cam_vertex + n);
+  ba_.h_anchor_v.assign(anchor_vertex, anchor_vertex + n);
+  ba_.h_pt_v.assign(point_vertex, point_vertex + n);
+  ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
+  chi2_valid_ = false;
+  ba_.sys_version = -1;
+  ba_.fused_ok = false;
+  ba_.ll_slots_ok = false;
+  for (DevBuf<int>* b : {&ba_.edge_hpl, &ba_.pt_pm, &ba_.cam_pm, &ba_.cam_q, &ba_.pt_q, &ba_.cam_lm, &ba_.pt_lm, &ba_.hpl_lm, &ba_.row_lm,
+                         &ba_.ll_edge, &ba_.ll_row})
+    b->release();
+  for (DevBuf<double>* b : {&ba_.meas_pm, &ba_.omega_pm, &ba_.meas_lm, &ba_.omega_lm, &ba_.meas_q, &ba_.omega_q, &ba_.ll_meas, &ba_.ll_omega})
+    b->release();
+  ba_.ll_rec.release();
+  ba_.tile_ll.release();
+  ba_.cam_v.upload(cam_vertex, n, st_);
+  ba_.anchor_v.upload(anchor_vertex, n, st_);
+  ba_.pt_v.upload(point_vertex, n, st_);
+  ba_.meas.upload(meas, n * 2, st_);
+  ba_.omega_identity = info == nullptr;
+  if (!info) {   // information().setIdentity(): written on the device
+    es.own_omega.alloc(n * 4);
+    if (n) hipLaunchKernelGGL(identity2_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, n, es.own_omega.p);
+  } else {
+    es.own_omega.upload(info, n * 4, st_);
+  }
+  es.own_J0.alloc(n * 6);
+  es.own_J1.alloc(n * 12);
+  es.own_err.alloc(n * 2);
+  ec.own_J1.alloc(n * 12);
+  ba_psi_alias();
+  for (EdgeSet* e : {&es, &ea, &ec}) {
+    e->external = false;
+    e->has_data = false;   // becomes valid with the first ba_linearize
+    e->has_err = false;
+  }
+  G2OHIP_HIP_CHECK(hipGetLastError());
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// the pointers of the three sets of an inverse-depth binding onto the buffers two of them own; a pointer that had to be repaired
+// (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences
+void BlockSolver::ba_psi_alias() {
+  EdgeSet &es = *sets_[ba_.set], &ea = *sets_[ba_.psi_pa], &ec = *sets_[ba_.psi_ca];
+  const double *jp = es.own_J0.p, *jc = es.own_J1.p, *ja = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
+  const double* want[3][2] = {{jp, jc}, {jp, ja}, {jc, ja}};
+  EdgeSet* g[3] = {&es, &ea, &ec};
+  bool changed = false;
+  for (int i = 0; i < 3; ++i) {
+    EdgeSet& e = *g[i];
+    changed = changed || e.J0 != want[i][0] || e.J1 != want[i][1] || e.omega != om || e.err != er || e.external;
+    e.J0 = want[i][0];
+    e.J1 = want[i][1];
+    e.omega = om;
+    e.err = er;
+    e.external = false;
+  }
+  if (changed) drop_graph_segments();
+}
+
+// an inverse-depth binding leaves the projection slot: its sets keep no device-written data and no pointer into each other's buffers
+// (set_edge_data is their next source; build_system refuses them until then, unless they are empty)
+void BlockSolver::ba_psi_release() {
+  if (!ba_.psi) return;
+  for (int id : {ba_.set, ba_.psi_pa, ba_.psi_ca}) {
+    if (id < 0 || id >= (int)sets_.size()) continue;
+    EdgeSet& e = *sets_[id];
+    e.has_data = e.has_err = false;
+    e.J0 = e.J1 = e.omega = e.err = nullptr;
+  }
+  ba_.psi = false;
+  ba_.psi_pa = ba_.psi_ca = -1;
+  ba_.anchor_v.release();
+  ba_.h_anchor_v.clear();
+}
+
+// the three sets of an inverse-depth binding against the estimate tables: indices inside the tables (anchors included), the
+// hessian index of every side equal to the sets' (cam_hidx, nP + point_hidx, -1 = fixed), and -1 on every camera side of an edge
+// whose observing pose is its anchor
+void BlockSolver::ba_validate_psi_edges(const EdgeSet& a, const EdgeSet& b, const EdgeSet& c, const int* cam_v, const int* anchor_v,
+                                        const int* pt_v, size_t n, const int* cam_hidx, int nc, const int* pt_hidx, int np) const {
+  for (size_t k = 0; k < n; ++k)   // (needs no table: the rule of the anchor's own observation)
+    if (cam_v[k] == anchor_v[k] && (a.v1[k] != -1 || b.v1[k] != -1 || c.v0[k] != -1 || c.v1[k] != -1))
+      throw ArgFailure("ba: edge " + std::to_string(k) + " is observed by its own anchor: every camera side of its three sets must be -1");
+  if (n == 0 || nc == 0) return;
+  for (size_t k = 0; k < n; ++k) {
+    const int cv = cam_v[k], av = anchor_v[k], q = pt_v[k];
+    if (cv < 0 || cv >= nc) throw ArgFailure("ba: camera index " + std::to_string(cv) + " of edge " + std::to_string(k) + " outside the estimate table");
+    if (av < 0 || av >= nc) throw ArgFailure("ba: anchor index " + std::to_string(av) + " of edge " + std::to_string(k) + " outside the estimate table");
+    if (q < 0 || q >= np) throw ArgFailure("ba: point index " + std::to_string(q) + " of edge " + std::to_string(k) + " outside the estimate table");
+    const int hc = cam_hidx[cv], ha = cam_hidx[av], hp = pt_hidx[q];
+    if (hc >= nP_ || ha >= nP_ || hp >= nL_) throw ArgFailure("ba: hessian index of an estimate outside the structure");
+    const bool own = cv == av;
+    const int vc = (own || hc < 0) ? -1 : hc, va = (own || ha < 0) ? -1 : ha, vp = hp < 0 ? -1 : nP_ + hp;
+    if (a.v0[k] != vp || a.v1[k] != vc || b.v0[k] != vp || b.v1[k] != va || c.v0[k] != vc || c.v1[k] != va)
+      throw ArgFailure("ba: edge " + std::to_string(k) + ": the estimates' hessian indices (point " + std::to_string(vp) + ", pose " +
+                       std::to_string(vc) + ", anchor " + std::to_string(va) + ") differ from the three edge sets'");
+  }
 }
 
 // Edge -> estimate indices against the estimate tables and against the edge set's hessian indices: a wrong index would be
@@ -5431,7 +5601,10 @@ void BlockSolver::ba_set_estimates(int n_cams, const double* cams, const int* ca
   // launch sequences stay (the device addresses are the same).
   const bool same = ba_.cams.same(n_cams, 12, cam_hidx) && ba_.pts.same(n_points, 3, point_hidx);
   if (!same) {
-    if (ba_.set >= 0)
+    if (ba_.set >= 0 && ba_.psi)
+      ba_validate_psi_edges(*sets_[ba_.set], *sets_[ba_.psi_pa], *sets_[ba_.psi_ca], ba_.h_cam_v.data(), ba_.h_anchor_v.data(), ba_.h_pt_v.data(),
+                            ba_.h_cam_v.size(), cam_hidx, n_cams, point_hidx, n_points);
+    else if (ba_.set >= 0)
       ba_validate_edges(*sets_[ba_.set], ba_.h_cam_v.data(), ba_.h_pt_v.data(), ba_.h_cam_v.size(), cam_hidx, n_cams, point_hidx, n_points);
     if (ba_.pose_set >= 0) pg_validate(*sets_[ba_.pose_set], ba_.h_pvi.data(), ba_.h_pvj.data(), ba_.h_pvi.size(), cam_hidx, n_cams);
     invalidate_graphs();
@@ -5544,11 +5717,15 @@ void BlockSolver::ba_linearize(bool jacobians) {
     throw StateFailure("ba_linearize: the pose edge set has grown since ba_set_pose_edges (g2ohip_update_structure): call ba_set_pose_edges again");
   const bool proj_done = ba_.err_valid && (!need_jac || ba_.jac_valid);
   const bool pose_done = !ep || (ba_.err_valid && (!jacobians || ba_.pose_jac_valid));
+  // an inverse-depth binding is three sets over one evaluation: whatever is marked for the projection set is marked for all of them
+  EdgeSet* const group[3] = {&es, ba_.psi ? sets_[ba_.psi_pa].get() : nullptr, ba_.psi ? sets_[ba_.psi_ca].get() : nullptr};
   if (proj_done && pose_done) {   // the estimates have not moved since the last evaluation
-    if (jacobians) es.has_data = true;
+    for (EdgeSet* e : group)
+      if (e && jacobians) e->has_data = true;
     if (jacobians && ep) ep->has_data = true;
     return;
   }
+  if (ba_.psi) ba_psi_alias();   // (before err_valid / jac_valid are set: a repaired pointer drops the captured launch sequences)
   if (need_jac && (es.own_J0.n < (size_t)es.n * es.d * 3 || es.own_J1.n < (size_t)es.n * es.d * 6)) {   // (left out by ba_set_edges on the fused path)
     es.own_J0.alloc((size_t)es.n * es.d * 3);
     es.own_J1.alloc((size_t)es.n * es.d * 6);
@@ -5570,6 +5747,11 @@ void BlockSolver::ba_linearize(bool jacobians) {
   if (ba_.chi_part.n < (size_t)lgrid) ba_.chi_part.alloc(lgrid);
   if (proj_done) {
     // (only the pose set's Jacobians are missing: an error-only evaluation, then one with Jacobians at the same estimates)
+  } else if (ba_.psi) {
+    if (es.n > 0)   // EdgeProjectPSI2UV -- ba_psi.inc (the kernel clamps its edge index to n - 1); chi2 goes the generic way
+      hipLaunchKernelGGL(ba_psi_linearize_kernel, dim3(lgrid), dim3(kThreads), 0, st_, es.n, ba_.cams.val.p, ba_.pts.val.p, ba_.cam_v.p,
+                         ba_.anchor_v.p, ba_.pt_v.p, ba_.meas.p, ba_.f, ba_.cx, ba_.cy, es.own_J0.p, es.own_J1.p, group[2]->own_J1.p,
+                         es.own_err.p, need_jac ? 1 : 0);
   } else if (ba_.stereo) {
     if (es.n > 0)   // (the kernel clamps its edge index to n - 1)
       with_bool(ba_stereo_staged, [&](auto staged) {
@@ -5584,7 +5766,7 @@ void BlockSolver::ba_linearize(bool jacobians) {
                        es.omega, ba_.omega_identity ? 1 : 0, es.kernel_kind, es.delta, ba_.chi_part.p,
                        ba_.n_classes > 1 ? ba_.ctab.p : (const double*)nullptr);
   }
-  if (!proj_done)
+  if (!proj_done && !ba_.psi)
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(1024), 0, st_, ba_.chi_part.p, lgrid, d_red_multi.p + (size_t)(ba_.set + 1) * kMaxBlocks);
   if (!pose_done && ep->n > 0)   // EdgeSE3Expmap beside the projection set -- ba_pose_edge.inc (the kernel clamps its edge index to n - 1)
     hipLaunchKernelGGL(ba_pose_edge_linearize_kernel, dim3(grid_for(ep->n)), dim3(kThreads), 0, st_, ep->n, ba_.cams.val.p, ba_.pvi.p,
@@ -5594,8 +5776,11 @@ void BlockSolver::ba_linearize(bool jacobians) {
     (jacobians ? times.linearize : times.residuals) = tfe_.seconds();
   }
   G2OHIP_HIP_CHECK(hipGetLastError());
-  es.has_err = true;
-  if (jacobians) es.has_data = true;
+  for (EdgeSet* e : group)
+    if (e) {
+      e->has_err = true;
+      if (jacobians) e->has_data = true;
+    }
   if (ep) {
     ep->has_err = true;
     if (jacobians) ep->has_data = true;
@@ -6370,7 +6555,7 @@ void BlockSolver::copy_edge_data(int set, double* J0, double* J1, double* err) {
     if (!dst || !src || cnt == 0) return;
     G2OHIP_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost, st_));
   };
-  if (es.has_data && !(set == ba_.set && !ba_.jac_valid)) {
+  if (es.has_data && !(set == ba_.set && !ba_.psi && !ba_.jac_valid)) {   // (an inverse-depth set keeps the Jacobians of its last full evaluation)
     pull(J0, es.J0, n * es.d * es.dim0);
     if (!es.unary) pull(J1, es.J1, n * es.d * es.dim1);
   } else if (J0 || J1) {

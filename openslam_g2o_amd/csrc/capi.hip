@@ -542,6 +542,14 @@ int g2ohip_ba_set_stereo_edges(g2ohip_solver* s, int set, const int32_t* cam_ver
 int g2ohip_ba_set_pose_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
   return entry(s, [&](BlockSolver& b) { b.ba_set_pose_edges(set, vi, vj, meas, info); });
 }
+int g2ohip_ba_set_inverse_depth_edges(g2ohip_solver* s, int set_point_pose, int set_point_anchor, int set_pose_anchor,
+                                      const int32_t* cam_vertex, const int32_t* anchor_vertex, const int32_t* point_vertex,
+                                      const double* meas, const double* info, double focal_length, double cx, double cy) {
+  return entry(s, [&](BlockSolver& b) {
+    b.ba_set_inverse_depth_edges(set_point_pose, set_point_anchor, set_pose_anchor, cam_vertex, anchor_vertex, point_vertex, meas, info,
+                                 focal_length, cx, cy);
+  });
+}
 int g2ohip_ba_set_estimates(g2ohip_solver* s, int n_cams, const double* cams, const int32_t* cam_hidx, int n_points,
                             const double* points, const int32_t* point_hidx) {
   return entry(s, [&](BlockSolver& b) { b.ba_set_estimates(n_cams, cams, cam_hidx, n_points, points, point_hidx); });

@@ -293,29 +293,47 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None, huber_delta_p
     (make_ba_problem(..., stereo_baseline=b)) is a set of EdgeProjectXYZ2UVU: error_dim 3, bound through baSetStereoEdges.
     A problem with pose_edges (synthetic.make_ba_odometry, g2o_io.read_g2o_ba of a file with EDGE_SE3:EXPMAP) gets a second,
     binary set of EdgeSE3Expmap constraints between its cameras, bound through baSetPoseEdges; huber_delta_pose > 0 puts a Huber
-    kernel on that set.  Its id is the projection set's + 1."""
+    kernel on that set.  Its id is the projection set's + 1.
+    A problem with observation = "inverse_depth" (synthetic.make_ba_inverse_depth) is a set of three-vertex EdgeProjectPSI2UV
+    observations: the three binary sets of prob["pairs"] with their parts (ids 0, 1, 2 = solver.psi_sets), bound through
+    baSetInverseDepthEdges with the information matrices prob["info"] [E][4] if present; huber_delta goes to all three of them.
+    A pose set follows with id 3."""
     import numpy as np
     from . import capi
     stereo = prob.get("observation") == "stereo"
+    psi = prob.get("observation") == "inverse_depth"
     s = capi.HipBlockSolver(6, 3, device)
     for name, value in (options or {}).items():
         s.setOption(name, value)
-    k = s.addEdgeSet(3 if stereo else 2, prob["v0"], prob["v1"])
+    if psi:
+        parts = (0, capi.PART_NO_VERTEX0 | capi.PART_NO_VERTEX1 | capi.PART_NO_CHI2, capi.PART_NO_VERTEX0 | capi.PART_NO_CHI2)
+        s.psi_sets = []
+        for (v0, v1), pt in zip(prob["pairs"], parts):
+            s.psi_sets.append(s.addEdgeSet(2, v0, v1))
+            s.setEdgeSetParts(s.psi_sets[-1], pt)
+        k = s.psi_sets[0]
+    else:
+        k = s.addEdgeSet(3 if stereo else 2, prob["v0"], prob["v1"])
     pe = prob.get("pose_edges")
     if pe is not None:
         kp = s.addEdgeSet(6, pe["v0"], pe["v1"])
     s.buildStructure(prob["nP"], prob["nL"], True)
-    if stereo:
+    if psi:
+        s.baSetInverseDepthEdges(*s.psi_sets, prob["cam_idx"], prob["anchor_idx"], prob["pt_idx"], prob["meas"], prob.get("info"), prob["f"],
+                                 prob["cx"], prob["cy"])
+    elif stereo:
         s.baSetStereoEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"], prob["baseline"])
     else:
         s.baSetEdges(k, prob["cam_idx"], prob["pt_idx"], prob["meas"], None, prob["f"], prob["cx"], prob["cy"])
-    s.baSetEstimates(prob["cams"], prob["cam_hidx"], prob["pts"], np.arange(prob["L"], dtype=np.int32))
+    pt_hidx = prob.get("pt_hidx")   # (a problem with fixed points carries its own landmark numbering)
+    s.baSetEstimates(prob["cams"], prob["cam_hidx"], prob["pts"], np.arange(prob["L"], dtype=np.int32) if pt_hidx is None else pt_hidx)
     if pe is not None:
         s.baSetPoseEdges(kp, pe["vi"], pe["vj"], pe["meas"], pe.get("info"))
         if huber_delta_pose > 0:
             s.setRobustKernel(kp, capi.KERNEL_HUBER, huber_delta_pose)
     if huber_delta > 0:
-        s.setRobustKernel(k, capi.KERNEL_HUBER, huber_delta)
+        for kk in (s.psi_sets if psi else [k]):
+            s.setRobustKernel(kk, capi.KERNEL_HUBER, huber_delta)
     return s, DeviceBAGraph(s)
 
 

@@ -156,6 +156,33 @@ def make_ba_odometry(P, L, loop_every=10, sigma_rot=0.002, sigma_trans=0.01, see
     return prob
 
 
+def make_ba_inverse_depth(P, L, seed=42, **ba_args):
+    """make_ba_problem(P, L, seed=seed, **ba_args) (mono) in the anchored inverse-depth parametrisation of EdgeProjectPSI2UV
+    (types_six_dof_expmap.h:158-178; g2o/examples/ba_anchored_inverse_depth): the anchor of a point is its first observing camera,
+    pts [L][3] holds psi = invert_depth(T_anchor X) of the initial estimates, so that psi2uv.to_world(pts, cams[pt_anchor]) is the
+    XYZ scene.  The dictionary gains observation = "inverse_depth", pt_anchor [L], anchor_idx [E] = pt_anchor[pt_idx] and pairs =
+    the (v0, v1) hessian indices of the three binary sets that stand for the three-vertex edge -- (point, pose), (point, anchor),
+    (pose, anchor) -- with -1 on every camera side of an edge observed by its own anchor (its two camera Jacobians cancel); v0 / v1
+    are those of the (point, pose) pair.  Everything else is make_ba_problem's."""
+    from . import psi2uv
+    assert "stereo_baseline" not in ba_args
+    prob = make_ba_problem(P, L, seed=seed, **ba_args)
+    cam_idx, pt_idx, h, nP = prob["cam_idx"], prob["pt_idx"], prob["cam_hidx"], prob["nP"]
+    K = prob["E"] // L
+    pt_anchor = cam_idx.reshape(L, K)[:, 0].astype(np.int32)
+    anchor_idx = pt_anchor[pt_idx]
+    A = prob["cams"][pt_anchor]
+    R = A[:, 0:9].reshape(-1, 3, 3).transpose(0, 2, 1)
+    prob["pts"] = psi2uv.invert_depth((R @ prob["pts"][:, :, None])[:, :, 0] + A[:, 9:12])
+    own = cam_idx == anchor_idx
+    vp = (nP + pt_idx).astype(np.int32)
+    vc = np.where(own, -1, h[cam_idx]).astype(np.int32)
+    va = np.where(own, -1, h[anchor_idx]).astype(np.int32)
+    prob.update(observation="inverse_depth", pt_anchor=pt_anchor, anchor_idx=anchor_idx.astype(np.int32), v0=vp, v1=vc,
+                pairs=[(vp, vc), (vp, va), (vc, va)])
+    return prob
+
+
 def make_ba_loops(P, L, laps=4, hubs=3, drop=0.2, seed=7, spacing=0.5, f=1000.0, cx=320.0, cy=240.0, hub_stride=3):
     """A bundle-adjustment graph that is NOT a band: the camera runs `laps` times back and forth along the same line
     (poses of different laps stand at the same places and see the same points -- loop closures everywhere, the reduced
