@@ -34,6 +34,28 @@ def worst(got, ref, ops):
     return float(e[k]), k
 
 
+def per_row(got, ref, ops_rows, d):
+    """Per edge AND per output row of a column-major d x dim block (dim = 1: the components of err): max over the row of
+    |got - ref|, divided by max(max |ref row|, ops_rows[e, r]).  No floor of 1: the rows of one block carry different units
+    (pixels beside metres beside 1 / metres), and a row of small entries is held to ITS size.  ops_rows [n][d] is stored in
+    the fixture: the largest magnitude among the terms added or subtracted on the way to that row.  Returns [n][d]; a row whose
+    reference and operands are all zero (a structural zero row) gives 0 where got is 0 too and inf otherwise."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    n = ref.shape[0]
+    got, ref = got.reshape(n, -1, d), ref.reshape(n, -1, d)           # [e][column][row]
+    scale = np.maximum(np.abs(ref).max(axis=1), np.asarray(ops_rows, np.float64).reshape(n, d))
+    diff = np.abs(got - ref).max(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(diff == 0, 0.0, diff / scale)
+
+
+def worst_row(got, ref, ops_rows, d):
+    """(figure, edge, row) of the worst row of per_row."""
+    e = per_row(got, ref, ops_rows, d)
+    k, r = np.unravel_index(int(np.argmax(e)), e.shape)
+    return float(e[k, r]), int(k), int(r)
+
+
 def bound(fx, key):
     """Device bound of fixture output `key`: MARGIN x the oracle's own worst per-edge error against the extended-precision
     reference; only where the oracle is exact (figure 0) the rounding floor of that output (floor_<key> eps, derived in

@@ -226,6 +226,79 @@ def project_edge(T, X, z, f, cx, cy):
             jacobian(lambda a: project_error(a, X, z, f, cx, cy), expmap_oplus, C, 6), project_error(C, X, z, f, cx, cy))
 
 
+# ------------------------------------------------------------------------------------------------ priors, camera, stereo
+def se2_prior_error(x, z):
+    """EdgeSE2Prior: (Z^-1 X) as (x, y, theta)."""
+    return se2_mul(se2_inv(z), x)
+
+
+def se2_xy_prior_error(x, z):
+    """EdgeSE2XYPrior: t - z."""
+    return [x[0] - z[0], x[1] - z[1]]
+
+
+def se3_prior_error(X, Z, P):
+    """EdgeSE3Prior with ParameterSE3Offset P: toVectorMQT(Z^-1 X P)."""
+    E = iso_mul(iso_inv(Z), iso_mul(X, P))
+    return list(E[1]) + R_to_quat(E[0])[:3]
+
+
+def se3_prior_quat_w(X, Z, P):
+    return R_to_quat(iso_mul(iso_inv(Z), iso_mul(X, P))[0])[3]
+
+
+def camera_point_k(X, l, P, K):
+    """p = K (X P)^-1 l, K = (fx, fy, cx, cy)."""
+    W = iso_inv(iso_mul(X, P))
+    q = [a + b for a, b in zip(mv3(W[0], l), W[1])]
+    return [K[0] * q[0] + K[2] * q[2], K[1] * q[1] + K[3] * q[2], q[2]]
+
+
+def camera_error(X, l, z, P, K, disparity):
+    """EdgeSE3PointXYZDepth / EdgeSE3PointXYZDisparity: (p0 / p2, p1 / p2, p2 or 1 / p2) - z."""
+    p = camera_point_k(X, l, P, K)
+    return [p[0] / p[2] - z[0], p[1] / p[2] - z[1], (1 / p[2] if disparity else p[2]) - z[2]]
+
+
+def stereo_error(T, X, z, f, cx, cy, b):
+    """EdgeProjectXYZ2UVU: z - (f x / z + cx, f y / z + cy, f (x - b) / z + cx), (x, y, z) = T X."""
+    p = camera_point(T, X)
+    return [z[0] - (f * p[0] / p[2] + cx), z[1] - (f * p[1] / p[2] + cy), z[2] - (f * (p[0] - b) / p[2] + cx)]
+
+
+def se2_prior_edge(x, z):
+    """(J0 [3x3], None, err) of EdgeSE2Prior."""
+    x, z = V(x), V(z)
+    return jacobian(lambda a: se2_prior_error(a, z), se2_oplus, x, 3), None, se2_prior_error(x, z)
+
+
+def se2_xy_prior_edge(x, z):
+    """(J0 [2x3], None, err) of EdgeSE2XYPrior."""
+    x, z = V(x), V(z)
+    return jacobian(lambda a: se2_xy_prior_error(a, z), se2_oplus, x, 3), None, se2_xy_prior_error(x, z)
+
+
+def se3_prior_edge(T, Tz, off):
+    """(J0 [6x6], None, err) of EdgeSE3Prior."""
+    X, Z, P = iso(T), iso(Tz), iso(off)
+    return jacobian(lambda a: se3_prior_error(a, Z, P), se3_oplus, X, 6), None, se3_prior_error(X, Z, P)
+
+
+def camera_edge(T, l, z, off, K, disparity):
+    """(J pose [3x6], J landmark [3x3], err) of the depth / disparity edge."""
+    X, P, l, z, K = iso(T), iso(off), V(l), V(z), V(K)
+    return (jacobian(lambda a: camera_error(a, l, z, P, K, disparity), se3_oplus, X, 6),
+            jacobian(lambda b: camera_error(X, b, z, P, K, disparity), point_oplus, l, 3), camera_error(X, l, z, P, K, disparity))
+
+
+def stereo_edge(T, X, z, f, cx, cy, b):
+    """(J point [3x3], J camera [3x6], err): vertex 0 of EdgeProjectXYZ2UVU is the point."""
+    C, X, z = iso(T), V(X), V(z)
+    f, cx, cy, b = (mp.mpf(float(v)) for v in (f, cx, cy, b))
+    return (jacobian(lambda p: stereo_error(C, p, z, f, cx, cy, b), point_oplus, X, 3),
+            jacobian(lambda a: stereo_error(a, X, z, f, cx, cy, b), expmap_oplus, C, 6), stereo_error(C, X, z, f, cx, cy, b))
+
+
 # ------------------------------------------------------------------------------------------------ robust kernels
 HUBER, PSEUDO_HUBER, CAUCHY, SATURATED, DCS = 1, 2, 3, 4, 5
 
