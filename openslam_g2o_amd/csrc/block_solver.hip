@@ -611,7 +611,8 @@ __device__ __forceinline__ void schur_tile_prepare(double* Bs, double* Ds, doubl
 template <int PD, int LD, int G, class EL>
 __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double* Cs, const double* bsm, bool neg, const int* ep,
                                                  const int* dptr, const int* ddiag, const EL* el, int td0, int td1, int e0,
-                                                 double* __restrict__ Pd, double* __restrict__ Pr, int tid, int NT) {
+                                                 double* __restrict__ Pd, double* __restrict__ Pr, int tid, int NT, int abl = 0) {
+  // (abl & 4, timing experiments only: the loop runs but nothing is stored -- what the store path costs)
   constexpr int PL = PD * LD;
   // G lanes per destination block = GC row parts x GE entry parts: a lane owns NR = PD/GC ROWS of the block
   // (PD*PD/GC accumulator registers: what keeps 3 workgroups on a CU) and walks every GE-th entry.  With the row
@@ -642,8 +643,21 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
   const int quad = (tid >> 2) & 3;
   const int grp = PAIR12 ? (tid >> 4) * 2 + ((quad ^ (quad >> 1)) & 1) : tid / G, g = tid % G, ngroups = NT / G;
   const int gc = PAIR12 ? quad >> 1 : (QUAD ? g / GE : g % GC), ge = PAIR12 ? (tid & 3) : (QUAD ? g % GE : g / GC);
+  // The store of a lane's row part (NP 16-byte pieces), by lane group width:
+  //  * G = 8 and G = 4 with row halves (QUAD: the GE = 4 or 2 entry parts are the low lane bits), even NR * PD: DEAL.  Lane ge
+  //    stores the pieces ge, GE + ge, ...: NF store instructions with every lane of the group active, each writing GE consecutive
+  //    pieces (64 or 32 contiguous bytes) per row part, then the NP % GE pieces left over from the lanes ge < NP % GE.
+  //  * every other width (G = 1, 2, 16, the odd pose dimension 7, (NR * PD) % 2 != 0): one store instruction per piece (or per
+  //    double), issued by the lane u % GE alone.
+  // Same bytes at the same addresses either way.  (A wave's round is one contiguous range of Pd, but a store of whole 1 KB
+  // segments needs the pieces moved across the 16-lane rows: some 36 ds_bpermute and 48 selects per round in registers, or an LDS slab
+  // of 9 KB per workgroup, which the four 39 KB tiles of a CU leave no room for.)
+  constexpr int NP = NR * PD / 2, NF = NP / GE;
+  constexpr bool DEAL = QUAD && (NR * PD) % 2 == 0 && NF >= 1;
+  const bool ge_lo = (ge & 1) != 0, ge_hi = (ge & 2) != 0;
   for (int ld = td0 + grp; ld < td1; ld += ngroups) {
     double acc[NR * PD], cacc[NR];   // acc[rr + NR * c]: row gc*NR + rr, column c
+    double dealt[DEAL ? 2 * NF : 1];   // DEAL: the pieces GE * k + ge of the summed block, k < NF
 #pragma unroll
     for (int i = 0; i < NR * PD; ++i) acc[i] = 0.0;
 #pragma unroll
@@ -658,6 +672,21 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
 #pragma unroll
         for (int rr = 0; rr < NR; ++rr) cacc[rr] += Vr[rr + NR * c] * bv;
       }
+    };
+    // DEAL, every lane of the group holds the summed block: pick this lane's pieces (selects on ge)
+    auto deal_select = [&]() {
+#pragma unroll
+      for (int k = 0; k < (DEAL ? NF : 0); ++k)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          double v = acc[2 * (GE * k) + t];
+#pragma unroll
+          for (int j = 1; j < GE; ++j) {
+            const double cj = acc[2 * (GE * k + j) + t];   // (read before the select: a select between addresses would put acc into scratch)
+            v = ge == j ? cj : v;
+          }
+          dealt[2 * k + t] = v;
+        }
     };
     // (the entry word of the NEXT iteration is requested one iteration ahead: entry -> slot addresses -> blocks is a chain of two
     // LDS round trips per iteration otherwise; reading past the list ends inside the tile's own LDS tables and is never used)
@@ -782,6 +811,7 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
 #pragma unroll
         for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
       }
+      if constexpr (DEAL) deal_select();
     } else {
       for (int k = k0 + ge; k < k1; k += GE) {
         const int pk = pk_next, lm = el[k];
@@ -828,15 +858,76 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
             acc[rr + NR * c] = v;
           }
       }
-      if (GE > 1) {   // lanes with the same gc are GC apart
+      if constexpr (DEAL) {
+        // The sum over the entry parts as a reduce-scatter: a lane only needs the sum of the pieces it stores.  Of two neighbouring
+        // pieces the lane keeps one and hands the other to the lane ^ 1 (then the same with lane ^ 2 for GE = 4): half the
+        // exchanges and additions per step, and the lane ge ends with the pieces ge, GE + ge, ... without a select after the sum.
+        // Each element is the same two-level sum of the same four (two) terms as ge_sum gives -- a + b is b + a to the bit.
+        double k1[NF * GE];   // piece 2 m + (ge & 1), m < NF * GE / 2
+#pragma unroll
+        for (int m = 0; m < NF * GE / 2; ++m)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const double x = acc[2 * (2 * m) + t], y = acc[2 * (2 * m + 1) + t];
+            k1[2 * m + t] = (ge_lo ? y : x) + dpp_permute<0xB1>(ge_lo ? x : y);   // lane ^ 1
+          }
+#pragma unroll
+        for (int k = 0; k < NF; ++k)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            if constexpr (GE == 4) {
+              const double x = k1[2 * (2 * k) + t], y = k1[2 * (2 * k + 1) + t];
+              dealt[2 * k + t] = (ge_hi ? y : x) + dpp_permute<0x4E>(ge_hi ? x : y);   // lane ^ 2
+            } else {
+              dealt[2 * k + t] = k1[2 * k + t];
+            }
+          }
+#pragma unroll
+        for (int i = 2 * NF * GE; i < NR * PD; ++i) acc[i] = ge_sum(acc[i]);   // (the pieces left over: every lane sums them)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
+      } else if (GE > 1) {   // lanes with the same gc are GC apart
 #pragma unroll
         for (int i = 0; i < NR * PD; ++i) acc[i] = ge_sum(acc[i]);
 #pragma unroll
         for (int r = 0; r < NR; ++r) cacc[r] = ge_sum(cacc[r]);
       }
     }
+    if (abl & 4) {   // (timing only: everything the stores would need stays live, nothing is written unless the sum is a NaN)
+      double s = 0.0;
+      if constexpr (DEAL) {
+#pragma unroll
+        for (int i = 0; i < 2 * NF; ++i) s += dealt[i];
+#pragma unroll
+        for (int i = 2 * NF * GE; i < NR * PD; ++i) s += acc[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < NR * PD; ++i) s += acc[i];
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) s += cacc[r];
+      if (s != s) Pd[(size_t)ld * PD * PD] = s;
+      continue;
+    }
     double* out = Pd + (size_t)ld * PD * PD + gc * NR * PD;
-    if constexpr ((NR * PD) % 2 == 0) {   // 16-byte pieces, dealt round-robin to the GE lanes (all hold the sum)
+    if constexpr (DEAL) {
+      dbl2_u* out2 = reinterpret_cast<dbl2_u*>(out);
+#pragma unroll
+      for (int k = 0; k < NF; ++k) {
+        dbl2_u v;
+        v.x = dealt[2 * k];
+        v.y = dealt[2 * k + 1];
+        out2[GE * k + ge] = v;
+      }
+#pragma unroll
+      for (int u = NF * GE; u < NP; ++u)
+        if ((u % GE) == ge) {
+          dbl2_u v;
+          v.x = acc[2 * u];
+          v.y = acc[2 * u + 1];
+          out2[u] = v;
+        }
+    } else if constexpr ((NR * PD) % 2 == 0) {   // 16-byte pieces, dealt round-robin to the GE lanes (all hold the sum)
       dbl2_u* out2 = reinterpret_cast<dbl2_u*>(out);
 #pragma unroll
       for (int u = 0; u < NR * PD / 2; ++u)
@@ -852,9 +943,19 @@ __device__ __forceinline__ void schur_tile_dests(const double* Bs, const double*
         if (GE == 1 || (i % GE) == ge) out[i] = acc[i];
     }
     if (diag) {
+      if constexpr (DEAL && NR <= GE) {   // one store: the lane ge < NR writes row ge of the part
+        double v = cacc[0];
 #pragma unroll
-      for (int r = 0; r < NR; ++r)
-        if (GE == 1 || (r % GE) == ge) Pr[(size_t)ld * PD + gc * NR + r] = cacc[r];
+        for (int r = 1; r < NR; ++r) {
+          const double cr = cacc[r];
+          v = ge == r ? cr : v;
+        }
+        if (ge < NR) Pr[(size_t)ld * PD + gc * NR + ge] = v;
+      } else {
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+          if (GE == 1 || (r % GE) == ge) Pr[(size_t)ld * PD + gc * NR + r] = cacc[r];
+      }
     }
   }
 }
@@ -1671,7 +1772,7 @@ __global__ void __launch_bounds__(kThreads, G2OHIP_SCHUR_OCC) ba_schur_tile_kern
   }
   __syncthreads();
   if (!FLL) schur_tile_prepare<PD, LD, ((PD % 2 == 0 && G >= 2) ? 2 : 1)>(Bs, Ds, bsm, Cs, neg_flag, l0, nlm, ntot, slot_lm_first, slot_lm, q0, nslots, Dinv, Hll, lam, tid, NT);
-  if (!(store_hll & 2)) schur_tile_dests<PD, LD, G>(Bs, Cs, bsm, tile_flag(neg_flag), ep, dptr, ddiag, el, td0, td1, e0, Pd, Pr, tid, NT);
+  if (!(store_hll & 2)) schur_tile_dests<PD, LD, G>(Bs, Cs, bsm, tile_flag(neg_flag), ep, dptr, ddiag, el, td0, td1, e0, Pd, Pr, tid, NT, store_hll);
 }
 
 // K13 for the fused EdgeProjectXYZ2UV path: x_l = Dinv (b_l - Hpl' x_p) WITHOUT reading Hpl (block_solver.hpp:459-483).
@@ -3749,7 +3850,9 @@ void BlockSolver::solve_schur_impl(bool want_matrix) {
     // ... and write to HBM only what the solve path reads (Dinv, b_l), not Hll and the errors: 150 MB less to write at the
     // metric configuration; a later reader (maxDiagonal, multiplyHessian, chi2 without a linearisation, inspection) has them
     // recomputed by ensure_ll()
-    static const int schur_abl = getenv("G2OHIP_SCHUR_ABL") ? atoi(getenv("G2OHIP_SCHUR_ABL")) & ~1 : 0;   // (timing experiments only)
+    static const int schur_abl = getenv("G2OHIP_SCHUR_ABL") ? atoi(getenv("G2OHIP_SCHUR_ABL")) & ~1 : 0;
+    // (timing experiments only, the result is meaningless -- 2: no destination loop, 4: the destination loop without its Pd / Pr
+    // stores, 8: no observation is linearised)
     const auto launch = [&](auto g, auto cls) {
       constexpr int GG = g;
       constexpr bool CLS = cls;
