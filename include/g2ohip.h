@@ -744,6 +744,38 @@ int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t
  * per handle, sharded solves, the g2o plugin adapter. */
 int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info,
                              const double* cov);
+/* ---- ... the pose-pose edges of a multi-sensor rig: relative poses measured between sensor frames mounted off the body -----
+ * ONE second pose-pose set of the same handle beside the set of g2ohip_pg_set_edges, in an "offset slot" of its own: independent
+ * of the landmark slot, the prior slot and the GICP slot; a later call replaces the binding.
+ *   type 18 = EdgeSE2Offset over two VertexSE2 (g2o/types/slam2d/edge_se2_offset.cpp:96-100 computeError,
+ *             parameter_se2_offset.cpp:76-86), beside a type-1 pose set only: e = (D.t, D.angle), D = Z^-1 (Xi Pi)^-1 (Xj Pj) with
+ *             SE2's products and normalize_theta as se2.h; meas [n][3] = (x, y, theta), info [n][3x3], offsets [n_params][3] =
+ *             (x, y, theta).  DELIBERATE DEVIATION: the reference defines no Jacobian for this edge and differentiates
+ *             numerically (base_binary_edge.hpp:132-201, delta = 1e-9); the device writes the exact derivative with respect to
+ *             VertexSE2::oplusImpl, as for type 7: with si = ti + R(thi) pi, sj = tj + R(thj) pj, M = R(thz + thi + ai)',
+ *             J = [0 -1; 1 0]: d e_t/d ti = -M, d e_t/d tj = M, d e_t/d thi = -J M (sj - si) - M J R(thi) pi, d e_t/d thj =
+ *             M J R(thj) pj, d e_th/d thi = -1, d e_th/d thj = 1;
+ *   type 19 = EdgeSE3Offset over two VertexSE3 (g2o/types/slam3d/edge_se3_offset.cpp:100-130, parameter_se3_offset.cpp:44-50),
+ *             beside a type-2 pose set only: e = toVectorMQT(Z^-1 (Xi Pi)^-1 (Xj Pj)) in the convention of type 2, Jacobians
+ *             the full computeEdgeSE3Gradient (isometry3d_gradients.h:86-192, its non-__clang__ branch) with A = Z^-1 Pi^-1,
+ *             B = Xi^-1 Xj, C = Pj; meas isometries [n][12] = R (column-major) | t, info [n][6x6], offsets [n_params][12].
+ * Edge set `set` was added as a binary set with error_dim 3 / 6 and both vertex dimensions 3 / 6 over the poses' hessian indices
+ * (-1 = fixed); vi / vj index the pose table of g2ohip_pg_set_estimates; param_from[k] / param_to[k] name the rows of `offsets`
+ * that are the sensor frame on vertex 0 / vertex 1 of edge k.  n = 0 is legal (the edge arrays may then be NULL); many edges on
+ * one vertex pair are legal, and so is a pair in both orders.
+ * Call after g2ohip_build_structure and g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).  G2OHIP_ERR_ARG: a wrong pairing of
+ * type and pose set, a set of other dimensions or a unary one, a set already bound in another slot, a null array with n > 0,
+ * n_params < 1 or a null offsets table, a parameter index outside [0, n_params), a vertex index outside the pose table, a
+ * hessian index that differs from the set's, a non-finite value (for type 19 that covers the columns of every rotation part)
+ * -- validated before anything is committed: a rejected call leaves the previous binding usable.  While a set is bound the
+ * other g2ohip_pg_set_* entries refuse its set id and g2ohip_pg_set_edges refuses pose types that do not fit.
+ * g2ohip_pg_set_estimates with changed tables validates the set again; update / push / pop / discard_top are not concerned (the
+ * set owns no vertices); robust kernels and chi2 as for any set; g2ohip_clear_edge_sets drops the binding; a set grown by
+ * g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.
+ * The kernels are timed under the "pg_landmark_linearize" slot.  Not covered: more than one offset set per handle, sharded
+ * solves, the g2o plugin adapter, EdgeSE2PointXYOffset, bearing edges. */
+int g2ohip_pg_set_offset_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const int32_t* param_from,
+                               const int32_t* param_to, const double* meas, const double* info, int n_params, const double* offsets);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -64,7 +64,7 @@ EXPORTS = [
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
-    "g2ohip_pg_set_cam_edges",
+    "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -175,6 +175,7 @@ def load():
     L.g2ohip_pg_set_cam_project_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_gicp_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_offset_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -547,6 +548,7 @@ class HipBlockSolver:
         self._set_sizes = {}
         self.gicp_set = None                # (the library drops every front-end binding)
         self.cam_set = self.scale_set = None
+        self.offset_set = None
         self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
@@ -567,6 +569,7 @@ class HipBlockSolver:
             if set_id in getattr(self, "_pg_owner_sets", ()):     # growth of the pose-pose or landmark set drops the whole front end
                 self.gicp_set = None
                 self.cam_set = self.scale_set = None
+                self.offset_set = None
                 self._pg_owner_sets = set()
         return True
 
@@ -894,6 +897,28 @@ class HipBlockSolver:
         _check(self.L.g2ohip_pg_set_gicp_edges(self.h, set_id, _ip(vi), _ip(vj), _dp(meas), _dp(info),
                                                None if cov is None else _dp(cov)), "pgSetGicpEdges")
         self.gicp_set = set_id
+
+    offset_set = None   # set id of the bound EdgeSE2Offset / EdgeSE3Offset set (pgSetOffsetEdges)
+
+    def pgSetOffsetEdges(self, set_id, edge_type, vi, vj, param_from, param_to, meas, info, offsets):
+        """Pose-pose edges between sensor frames mounted off the body, a second pose-pose set in a slot of its own: edge_type 18 =
+        EdgeSE2Offset beside an EdgeSE2 pose set (meas [n][3] = (x, y, theta), info [n][3x3], offsets [n_params][3]), 19 =
+        EdgeSE3Offset beside an EdgeSE3 pose set (isometries: meas [n][12], info [n][6x6], offsets [n_params][12]).  vi / vj index
+        the table of pgSetEstimates, param_from / param_to the rows of `offsets` (the sensor frame on vertex 0 / vertex 1).  The set
+        is a binary one with error_dim 3 / 6 (addEdgeSet(d, hidx[vi], hidx[vj])).  After pgSetEdges."""
+        if edge_type not in (18, 19):
+            raise ValueError("pgSetOffsetEdges: edge_type is 18 (EdgeSE2Offset) or 19 (EdgeSE3Offset)")
+        vi, vj, pf, pt, meas, info = _i32(vi), _i32(vj), _i32(param_from), _i32(param_to), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        d, ms = (3, 3) if edge_type == 18 else (6, 12)
+        if len(vi) != n or len(vj) != n or len(pf) != n or len(pt) != n or meas.size != n * ms or info.size != n * d * d:
+            raise ValueError("pgSetOffsetEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        table = _f64(offsets)
+        if table.ndim != 2 or table.shape[1] != ms or len(table) < 1:
+            raise ValueError("pgSetOffsetEdges: offsets is [n_params][%d], n_params >= 1" % ms)
+        _check(self.L.g2ohip_pg_set_offset_edges(self.h, set_id, edge_type, _ip(vi), _ip(vj), _ip(pf), _ip(pt), _dp(meas), _dp(info),
+                                                 len(table), _dp(table)), "pgSetOffsetEdges")
+        self.offset_set = set_id
 
     cam_set = scale_set = None     # set ids of the bound EdgeSBACam / EdgeSBAScale sets (pgSetCamEdges)
 

@@ -148,6 +148,13 @@ class HipBlockSolver {
   bool pgSetCamEdges(int set, int type, const int32_t* vi, const int32_t* vj, const double* meas, const double* info) {
     return ok(g2ohip_pg_set_cam_edges(h_, set, type, vi, vj, meas, info), "pgSetCamEdges");
   }
+  // Sensor-offset pose-pose edges (g2ohip_pg_set_offset_edges), a second pose-pose set in a slot of its own: type 18 =
+  // EdgeSE2Offset beside an EdgeSE2 set (meas [n][3], info [n][3x3], offsets [nParams][3]), 19 = EdgeSE3Offset beside an EdgeSE3
+  // set (meas [n][12], info [n][6x6], offsets [nParams][12]); paramFrom / paramTo name the rows of the offsets table
+  bool pgSetOffsetEdges(int set, int type, const int32_t* vi, const int32_t* vj, const int32_t* paramFrom, const int32_t* paramTo,
+                        const double* meas, const double* info, int nParams, const double* offsets) {
+    return ok(g2ohip_pg_set_offset_edges(h_, set, type, vi, vj, paramFrom, paramTo, meas, info, nParams, offsets), "pgSetOffsetEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -103,6 +103,8 @@ class BlockSolver {
                                 const double* info, int n_cams, const double* intrinsics);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov);
+  void pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to, const double* meas,
+                           const double* info, int n_params, const double* offsets);
   void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -511,6 +513,14 @@ class BlockSolver {
     DevBuf<int> gi, gj;
     std::vector<int> h_gi, h_gj;   // host copies: index validation (pg_validate)
     DevBuf<double> gicp_meas, gicp_cov;
+    // ONE second pose-pose set `off_set` of sensor-offset edges, independent of the landmark, prior and GICP slots: off_type 18 =
+    // EdgeSE2Offset beside type 1 (measurements and offsets (x, y, theta)), 19 = EdgeSE3Offset beside type 2 (isometries [12]).
+    // oi / oj index `poses`, opf / opt the rows of off_table [off_params][3 | 12] (the sensor frame on vertex 0 / vertex 1).
+    // The set owns no vertices either (pg_offset.inc).
+    int off_set = -1, off_type = 0, off_params = 0;
+    DevBuf<int> oi, oj, opf, opt;
+    std::vector<int> h_oi, h_oj;   // host copies: index validation (pg_validate)
+    DevBuf<double> off_meas, off_table;
     // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
     // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
     // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.

@@ -2312,6 +2312,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_cam_project.inc"
 #include "pg_sbacam_edge.inc"
 #include "pg_gicp.inc"
+#include "pg_offset.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
@@ -2573,7 +2574,8 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
     // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
-    // (pg_set_gicp_edges again) or a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again)
+    // (pg_set_gicp_edges again), a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again) or a grown sensor-offset set
+    // (pg_set_offset_edges again)
     if (set == pg_.set || set == pg_.lm_set) {
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -3294,7 +3296,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
   const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
-                             set == pg_.cam_set || set == pg_.scale_set;
+                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5980,6 +5982,9 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (type != 12 && (pg_.cam_set >= 0 || pg_.scale_set >= 0))
     throw ArgFailure("pg_set_edges: an EdgeSBACam (16) or EdgeSBAScale (17) set is bound: it stands beside a VertexCam set (12) only");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (pg_.off_set >= 0 && type != pg_.off_type - 17)
+    throw ArgFailure("pg_set_edges: a sensor-offset set is bound: EdgeSE2Offset (18) stands beside an EdgeSE2 pose set (1) only, EdgeSE3Offset (19) beside EdgeSE3 (2)");
+  if (set == pg_.off_set) throw ArgFailure("pg_set_edges: the set is bound as the sensor-offset set");
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
@@ -6055,6 +6060,7 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
     if (pg_.gicp_set >= 0) pg_validate(*sets_[pg_.gicp_set], pg_.h_gi.data(), pg_.h_gj.data(), pg_.h_gi.size(), hidx, nv);
     if (pg_.cam_set >= 0) pg_validate(*sets_[pg_.cam_set], pg_.h_ci.data(), pg_.h_cj.data(), pg_.h_ci.size(), hidx, nv);
     if (pg_.scale_set >= 0) pg_validate(*sets_[pg_.scale_set], pg_.h_si.data(), pg_.h_sj.data(), pg_.h_si.size(), hidx, nv);
+    if (pg_.off_set >= 0) pg_validate(*sets_[pg_.off_set], pg_.h_oi.data(), pg_.h_oj.data(), pg_.h_oi.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -6157,6 +6163,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
   if (set == pg_.gicp_set) throw ArgFailure(w + ": the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure(w + ": the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (set == pg_.off_set) throw ArgFailure(w + ": the set is bound as the sensor-offset set");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -6213,6 +6220,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (set == pg_.lm_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the landmark set");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (set == pg_.off_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the sensor-offset set");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -6267,6 +6275,7 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   if (set == pg_.lm_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the landmark set");
   if (set == pg_.pr_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the prior set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (set == pg_.off_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the sensor-offset set");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6309,6 +6318,71 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
+// ---- ... the pose-pose edges of a multi-sensor rig: EdgeSE2Offset (type 18) beside an EdgeSE2 set, EdgeSE3Offset (type 19) beside
+// an EdgeSE3 set, ONE set in a slot of its own (pg_offset.inc).  Every edge names two rows of the offsets table [n_params][3 | 12].
+// The contract of the GICP entry: validate everything, then commit; a later call replaces the slot's set and clears the data of
+// the set that leaves it; n = 0 is legal; the set owns no vertices.
+void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to,
+                                      const double* meas, const double* info, int n_params, const double* offsets) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_offset_edges: call pg_set_edges first (the pose-pose set the sensor-offset set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (type != 18 && type != 19) throw ArgFailure("pg_set_offset_edges: type must be 18 (EdgeSE2Offset) or 19 (EdgeSE3Offset)");
+  if (pg_.type != type - 17) throw ArgFailure("pg_set_offset_edges: EdgeSE2Offset (18) goes with an EdgeSE2 pose set (1), EdgeSE3Offset (19) with EdgeSE3 (2)");
+  if (set == pg_.set) throw ArgFailure("pg_set_offset_edges: the set is bound as the pose-pose set");
+  if (set == pg_.lm_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the landmark set");
+  if (set == pg_.pr_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the prior set");
+  if (set == pg_.gicp_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the GICP set");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  EdgeSet& es = *sets_[set];
+  const int d = type == 18 ? 3 : 6;
+  if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d || p_ != d)
+    throw ArgFailure("pg_set_offset_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 3, 3) or (6, 6, 6)");
+  const size_t n = (size_t)es.n, ms = type == 18 ? 3 : 12;
+  if (n_params < 1 || !offsets) throw ArgFailure("pg_set_offset_edges: no offsets table (n_params >= 1 rows of (x, y, theta) or isometries [12])");
+  if (n > 0 && (!vi || !vj || !param_from || !param_to || !meas || !info)) throw ArgFailure("pg_set_offset_edges: null array");
+  for (size_t i = 0; i < ms * (size_t)n_params; ++i)
+    if (!std::isfinite(offsets[i])) throw ArgFailure("pg_set_offset_edges: non-finite value in row " + std::to_string(i / ms) + " of the offsets table");
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0) throw ArgFailure("pg_set_offset_edges: negative vertex index in edge " + std::to_string(k));
+    if (param_from[k] < 0 || param_from[k] >= n_params || param_to[k] < 0 || param_to[k] >= n_params)
+      throw ArgFailure("pg_set_offset_edges: parameter index of edge " + std::to_string(k) + " outside the offsets table");
+    for (size_t i = 0; i < ms; ++i)   // (type 19: the columns of the rotation part and the translation)
+      if (!std::isfinite(meas[ms * k + i])) throw ArgFailure("pg_set_offset_edges: non-finite measurement in edge " + std::to_string(k));
+    for (int i = 0; i < d * d; ++i)
+      if (!std::isfinite(info[(size_t)(d * d) * k + i])) throw ArgFailure("pg_set_offset_edges: non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  if (pg_.off_set >= 0 && pg_.off_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
+    EdgeSet& old = *sets_[pg_.off_set];
+    old.has_data = old.has_err = false;
+  }
+  pg_.off_set = set;
+  pg_.off_type = type;
+  pg_.off_params = n_params;
+  pg_.h_oi.assign(vi, vi + n);
+  pg_.h_oj.assign(vj, vj + n);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.oi.upload(vi, n, st_);
+  pg_.oj.upload(vj, n, st_);
+  pg_.opf.upload(param_from, n, st_);
+  pg_.opt.upload(param_to, n, st_);
+  pg_.off_meas.upload(meas, n * ms, st_);
+  pg_.off_table.upload(offsets, ms * (size_t)n_params, st_);
+  es.own_omega.upload(info, n * d * d, st_);
+  es.own_J0.alloc(n * d * d);
+  es.own_J1.alloc(n * d * d);
+  es.own_err.alloc(n * d);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
 // ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
 // own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
 // validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
@@ -6326,6 +6400,7 @@ void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* 
   if (set == pg_.lm_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the landmark set");
   if (set == pg_.pr_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the prior set");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the GICP set");
+  if (set == pg_.off_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the sensor-offset set");
   if (set == (cam ? pg_.scale_set : pg_.cam_set))
     throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
   EdgeSet& es = *sets_[set];
@@ -6424,7 +6499,11 @@ void BlockSolver::pg_linearize(bool jacobians) {
   EdgeSet* esc = pg_.scale_set >= 0 ? sets_[pg_.scale_set].get() : nullptr;
   if ((ec && (int)pg_.h_ci.size() != ec->n) || (esc && (int)pg_.h_si.size() != esc->n))
     throw StateFailure("pg_linearize: the EdgeSBACam / EdgeSBAScale edge set has grown since pg_set_cam_edges (g2ohip_update_structure): call pg_set_cam_edges again");
+  EdgeSet* eo = pg_.off_set >= 0 ? sets_[pg_.off_set].get() : nullptr;
+  if (eo && (int)pg_.h_oi.size() != eo->n)
+    throw StateFailure("pg_linearize: the sensor-offset edge set has grown since pg_set_offset_edges (g2ohip_update_structure): call pg_set_offset_edges again");
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
+    if (jacobians && eo) eo->has_data = true;
     if (jacobians) es.has_data = true;
     if (jacobians && el) el->has_data = true;
     if (jacobians && ep) ep->has_data = true;
@@ -6456,9 +6535,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
     }
   }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
-  const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0;
+  const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0, off_launch = eo && eo->n > 0;
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                        pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
@@ -6532,7 +6611,19 @@ void BlockSolver::pg_linearize(bool jacobians) {
   if (scale_launch)   // EdgeSBAScale
     hipLaunchKernelGGL(pg_sbascale_linearize_kernel, dim3(grid_for(esc->n)), dim3(kThreads), 0, st_, esc->n, pg_.poses.val.p,
                        pg_.poses.hidx.p, pg_.si.p, pg_.sj.p, pg_.scale_meas.p, esc->own_J0.p, esc->own_J1.p, esc->own_err.p, jac);
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (off_launch) {   // EdgeSE2Offset / EdgeSE3Offset -- pg_offset.inc
+    const dim3 grid(grid_for(eo->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      if (pg_.off_type == 18)
+        hipLaunchKernelGGL(pg_se2_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, pg_.oi.p, pg_.oj.p, pg_.opf.p,
+                           pg_.opt.p, pg_.off_meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
+      else
+        hipLaunchKernelGGL(pg_se3_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, pg_.oi.p, pg_.oj.p, pg_.opf.p,
+                           pg_.opt.p, pg_.off_meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
+    });
+  }
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
@@ -6548,7 +6639,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
     eg->has_err = true;
     if (jacobians) eg->has_data = true;
   }
-  for (EdgeSet* e : {ec, esc})
+  for (EdgeSet* e : {ec, esc, eo})
     if (e) {
       e->has_err = true;
       if (jacobians) e->has_data = true;

@@ -68,7 +68,14 @@ def read_g2o(path):
     cam_scale_meas [n] / cam_scale_info [n]; a file without these tags gives none of these keys.
     A file with EDGE_V_V_GICP lines (i j pos0 normal0 pos1 normal1: Edge_V_V_GICP::read, g2o/types/icp/types_icp.cpp:124-160) over
     VERTEX_SE3:QUAT also gives gicp_vi / gicp_vj (pose-table indices), gicp_meas [m][6] = (pos0, pos1) and gicp_normal0 /
-    gicp_normal1 [m][3] (gicp_problem turns them into a problem dict); a file without them gives none of these keys."""
+    gicp_normal1 [m][3] (gicp_problem turns them into a problem dict); a file without them gives none of these keys.
+    A file with EDGE_SE2_OFFSET (i j paramFrom paramTo x y th + 6: EdgeSE2Offset::read, g2o/types/slam2d/edge_se2_offset.cpp:58-84)
+    or EDGE_SE3_OFFSET lines (i j paramFrom paramTo x y z qx qy qz qw + 21, the quaternion normalised: EdgeSE3Offset::read,
+    g2o/types/slam3d/edge_se3_offset.cpp:58-87) also gives off_vi / off_vj (pose-table indices), off_from / off_to (the parameter
+    IDS as written), off_meas [m][3 | 7], off_info [m][d][d] and off_kind ("se2" | "se3"); PARAMS_SE2OFFSET lines (id x y theta:
+    ParameterSE2Offset::read) give offsets2 {id: (x y theta)}.  An edge that names a parameter id the file does not define, or a
+    file that mixes the two edge tags, raises ValueError (offset_problem turns the keys into a problem dict); a file without
+    these tags gives none of these keys."""
     from . import sim3 as S3
     g_i, g_j, g_vals = [], [], []
     sim3_extras = []
@@ -79,6 +86,7 @@ def read_g2o(path):
     pid, pest, lp, ll, lmeas, linfo, lparam, offsets = [], [], [], [], [], [], [], {}
     lkind, cameras = [], {}
     qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
+    o_i, o_j, o_from, o_to, o_meas, o_info, o_kind, offsets2 = [], [], [], [], [], [], None, {}
     kind = None
     with open(path) as f:
         for line in f:
@@ -86,7 +94,24 @@ def read_g2o(path):
             if not t:
                 continue
             tag = t[0]
-            if tag == "VERTEX_SE2":
+            if tag in ("EDGE_SE2_OFFSET", "EDGE_SE3_OFFSET"):
+                k3 = tag == "EDGE_SE3_OFFSET"
+                if o_kind is not None and o_kind != ("se3" if k3 else "se2"):
+                    raise ValueError("%s mixes EDGE_SE2_OFFSET and EDGE_SE3_OFFSET" % path)
+                o_kind = "se3" if k3 else "se2"
+                o_i.append(int(t[1]))
+                o_j.append(int(t[2]))
+                o_from.append(int(t[3]))
+                o_to.append(int(t[4]))
+                nm, dd = (7, 6) if k3 else (3, 3)
+                v = np.asarray([float(x) for x in t[5:5 + nm]])
+                if k3:
+                    v[3:] /= np.linalg.norm(v[3:])
+                o_meas.append(v)
+                o_info.append(_upper_to_full([float(x) for x in t[5 + nm:5 + nm + dd * (dd + 1) // 2]], dd))
+            elif tag == "PARAMS_SE2OFFSET":
+                offsets2[int(t[1])] = np.asarray([float(x) for x in t[2:5]])
+            elif tag == "VERTEX_SE2":
                 kind = kind or "se2"
                 vid.append(int(t[1]))
                 vest.append([float(x) for x in t[2:5]])
@@ -256,6 +281,16 @@ def read_g2o(path):
     if qv:
         out.update(pr_v=np.asarray([lut[a] for a in qv], np.int32), pr_kind=qkind, pr_meas=qmeas, pr_info=qinfo,
                    pr_param=np.asarray(qparam, np.int32), offsets=offsets)
+    if offsets2:
+        out["offsets2"] = offsets2
+    if o_i:
+        table = offsets if o_kind == "se3" else offsets2
+        for a in o_from + o_to:
+            if a not in table:
+                raise ValueError("%s: an offset edge names the parameter id %d, which the file does not define" % (path, a))
+        out.update(off_vi=np.asarray([lut[a] for a in o_i], np.int32), off_vj=np.asarray([lut[a] for a in o_j], np.int32),
+                   off_from=np.asarray(o_from, np.int32), off_to=np.asarray(o_to, np.int32), off_meas=np.asarray(o_meas, np.float64),
+                   off_info=np.asarray(o_info, np.float64), off_kind=o_kind, offsets=offsets)
     return out
 
 
@@ -430,6 +465,67 @@ def gicp_problem(rd, fixed=None, plane_to_plane=False, epsilon=0.01):
                 omega=np.asarray(rd["info"], np.float64).reshape(-1, 36), gi=rd["gicp_vi"], gj=rd["gicp_vj"], gmeas=rd["gicp_meas"],
                 ginfo=np.stack([G.read_information(a).T.reshape(9) for a in n0]), gcov=gcov, normal0=n0, normal1=n1,
                 plane_to_plane=bool(plane_to_plane))
+
+
+def write_g2o_offset(path, prob, ids=None, param_ids=None):
+    """make_offset_rig-style problem -> `.g2o` text: PARAMS_SE2OFFSET / PARAMS_SE3OFFSET lines for the rows of prob["offsets"]
+    (ids param_ids, default 0, 1, ...), VERTEX_SE2 / VERTEX_SE3:QUAT lines, a FIX line for the poses of hessian index -1, the
+    odometry as EDGE_SE2 / EDGE_SE3:QUAT and the offset edges as EDGE_SE2_OFFSET / EDGE_SE3_OFFSET "i j paramFrom paramTo
+    measurement upper-triangle".  %.17g: a read gives the written doubles back (SE3 rotations up to the quaternion round trip)."""
+    se3 = prob["kind"] == "se3"
+    ms, d = (12, 6) if se3 else (3, 3)
+    X = np.asarray(prob["poses"], np.float64).reshape(-1, ms)
+    n = len(X)
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    table = np.asarray(prob["offsets"], np.float64).reshape(-1, ms)
+    param_ids = np.arange(len(table)) if param_ids is None else np.asarray(param_ids)
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    qt = (lambda A: np.concatenate([A[:, 9:12], _R_to_quat(A[:, 0:9].reshape(-1, 3, 3).transpose(0, 2, 1))], axis=1)) if se3 else (lambda A: A)
+    upper = lambda M: fmt(M[i, j] for i in range(d) for j in range(i, d))
+    vtag, etag, otag, ptag = (("VERTEX_SE3:QUAT", "EDGE_SE3:QUAT", "EDGE_SE3_OFFSET", "PARAMS_SE3OFFSET") if se3 else
+                              ("VERTEX_SE2", "EDGE_SE2", "EDGE_SE2_OFFSET", "PARAMS_SE2OFFSET"))
+    with open(path, "w") as f:
+        for k, v in enumerate(qt(table)):
+            f.write("%s %d %s\n" % (ptag, param_ids[k], fmt(v)))
+        for k, v in enumerate(qt(X)):
+            f.write("%s %d %s\n" % (vtag, ids[k], fmt(v)))
+        fixed = [ids[k] for k in range(n) if prob["hidx"][k] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(int(i)) for i in fixed))
+        Z = qt(np.asarray(prob["Z"], np.float64).reshape(-1, ms))
+        om = np.asarray(prob["omega"], np.float64).reshape(-1, d, d)
+        for e in range(len(Z)):
+            f.write("%s %d %d %s %s\n" % (etag, ids[prob["vi"][e]], ids[prob["vj"][e]], fmt(Z[e]), upper(om[e])))
+        Zo = qt(np.asarray(prob["omeas"], np.float64).reshape(-1, ms))
+        oo = np.asarray(prob["oinfo"], np.float64).reshape(-1, d, d)
+        for e in range(len(Zo)):
+            f.write("%s %d %d %d %d %s %s\n" % (otag, ids[prob["oi"][e]], ids[prob["oj"][e]], param_ids[prob["opf"][e]],
+                                                param_ids[prob["opt"][e]], fmt(Zo[e]), upper(oo[e])))
+
+
+def offset_problem(rd, fixed=None):
+    """read_g2o result of a VERTEX_SE2 / VERTEX_SE3:QUAT file with EDGE_SE2_OFFSET / EDGE_SE3_OFFSET lines -> the problem dict of
+    synthetic.make_offset_rig (what lm.setup_device_pose_graph(offset_edges=...) takes).  The parameter ids the file defines are
+    mapped to rows of the offsets table in ascending order of id (param_ids holds the id of every row); SE3 values become
+    isometries [12].  fixed: indices into the pose table (default: the file's FIX lines; a file without any gets pose 0 fixed as
+    the gauge)."""
+    if "off_vi" not in rd or rd.get("kind") != rd["off_kind"]:
+        raise ValueError("offset_problem: not a VERTEX_SE2 file with EDGE_SE2_OFFSET lines or a VERTEX_SE3:QUAT file with EDGE_SE3_OFFSET lines")
+    se3 = rd["kind"] == "se3"
+    conv = _iso_from_qt if se3 else (lambda a: np.asarray(a, np.float64).reshape(-1, 3))
+    d, ms = (6, 12) if se3 else (3, 3)
+    params = rd["offsets"] if se3 else rd["offsets2"]
+    param_ids = np.asarray(sorted(params), np.int64)
+    row = {int(p): k for k, p in enumerate(param_ids)}
+    n = len(rd["estimates"])
+    fixed = (rd["fixed"] or [0]) if fixed is None else fixed
+    hidx, nP = hessian_index(n, fixed)
+    return dict(kind=rd["kind"], n=n, nP=nP, poses=conv(rd["estimates"]), hidx=hidx, vi=rd["vi"], vj=rd["vj"],
+                Z=conv(rd["meas"]) if len(rd["vi"]) else np.zeros((0, ms)), omega=np.asarray(rd["info"], np.float64).reshape(-1, d * d),
+                offset_type=19 if se3 else 18, oi=rd["off_vi"], oj=rd["off_vj"],
+                opf=np.asarray([row[int(a)] for a in rd["off_from"]], np.int32), opt=np.asarray([row[int(a)] for a in rd["off_to"]], np.int32),
+                omeas=conv(rd["off_meas"]), oinfo=np.asarray(rd["off_info"], np.float64).reshape(-1, d * d),
+                offsets=conv(np.stack([params[int(p)] for p in param_ids])), param_ids=param_ids)
 
 
 def hessian_index(n_vertices, fixed):

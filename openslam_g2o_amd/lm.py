@@ -375,7 +375,7 @@ PG_POSE_DIM = {1: 3, 2: 6, 10: 7}       # EdgeSE2, EdgeSE3, EdgeSim3 (g2ohip_pg_
 
 
 def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0, priors=None,
-                            fix_scale=False, options=None):
+                            fix_scale=False, options=None, offset_edges=None):
     """HipBlockSolver for a pose graph with estimates, errors and Jacobians on the device.
     edge_type 1: EdgeSE2 (estimates / measurements (x, y, theta), information [n][9]);
     edge_type 2: EdgeSE3 (isometries [12] = R column-major | t, information [n][36]).
@@ -384,7 +384,10 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     hidx[v] = hessian index of vertex v or -1 (fixed); BlockSolver_3_2 / BlockSolver_6_3 semantics, no Schur.
     options: g2ohip_set_option pairs that have to be in place before buildStructure.
     priors: (type, vq, zq, omega_q, offset) -- unary priors on the poses vq, type 7 = EdgeSE2Prior, 8 = EdgeSE2XYPrior
-    (edge_type 1), 9 = EdgeSE3Prior with its ParameterSE3Offset or None (edge_type 2); solver.prior_set = their set id."""
+    (edge_type 1), 9 = EdgeSE3Prior with its ParameterSE3Offset or None (edge_type 2); solver.prior_set = their set id.
+    offset_edges: (type, vi, vj, pfrom, pto, meas, info, offsets) -- pose-pose edges between sensor frames, type 18 =
+    EdgeSE2Offset (edge_type 1), 19 = EdgeSE3Offset (edge_type 2), pfrom / pto rows of the offsets table (g2ohip_pg_set_offset_edges);
+    solver.offset_set = their set id."""
     import numpy as np
     from . import capi
     d = PG_POSE_DIM[edge_type]
@@ -396,6 +399,9 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     if priors is not None:
         ptype, vq, zq, omega_q, offset = priors
         kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[np.asarray(vq)], None)
+    if offset_edges is not None:
+        otype, oi, oj, opf, opt, omeas, oinfo, otable = offset_edges
+        ko = s.addEdgeSet(d, hidx[np.asarray(oi, np.int64)], hidx[np.asarray(oj, np.int64)])
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
     if edge_type == 10:
@@ -405,6 +411,8 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     if priors is not None:
         s.pgSetPriorEdges(kq, ptype, vq, zq, omega_q, offset)
         s.prior_set = kq
+    if offset_edges is not None:
+        s.pgSetOffsetEdges(ko, otype, oi, oj, opf, opt, omeas, oinfo, otable)
     return s, DevicePoseGraph(s)
 
 

@@ -917,3 +917,92 @@ def make_gicp(n_scans, pts_per_pair, pairs=None, plane_to_plane=False, seed=0, o
                 hidx=(np.arange(n_scans, dtype=np.int32) - 1).astype(np.int32), vi=vi, vj=vj, Z=Z, omega=omega, gi=gi, gj=gj,
                 gmeas=np.concatenate([pos0, pos1], axis=1), ginfo=ginfo, gcov=gcov, normal0=normal0, normal1=normal1,
                 plane_to_plane=bool(plane_to_plane), pairs=pairs)
+
+
+def _se2_mul(a, b):
+    """SE2 products of rows (x, y, theta), the angle wrapped into [-pi, pi)."""
+    c, s = np.cos(a[:, 2]), np.sin(a[:, 2])
+    th = (a[:, 2] + b[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
+    return np.stack([a[:, 0] + c * b[:, 0] - s * b[:, 1], a[:, 1] + s * b[:, 0] + c * b[:, 1], th], axis=1)
+
+
+def _se2_inv(a):
+    c, s = np.cos(a[:, 2]), np.sin(a[:, 2])
+    th = (-a[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
+    return np.stack([-(c * a[:, 0] + s * a[:, 1]), s * a[:, 0] - c * a[:, 1], th], axis=1)
+
+
+def _iso_mul(A, B):
+    (Ra, ta), (Rb, tb) = A, B
+    return Ra @ Rb, np.einsum("nij,nj->ni", Ra, tb) + ta
+
+
+def _iso_inv(A):
+    Rt = A[0].transpose(0, 2, 1)
+    return Rt, -np.einsum("nij,nj->ni", Rt, A[1])
+
+
+def make_offset_rig(kind="se3", n_poses=12, n_sensors=2, edges_per_pose=3, seed=0, noise=(0.02, 0.01), perturb=(0.2, 0.08),
+                    offsets=None):
+    """A multi-sensor rig with EdgeSE2Offset / EdgeSE3Offset edges (what g2o_simulator3d's pose sensor with offset writes): n_poses
+    poses on a winding trajectory with odometry between consecutive poses (type 1 / 2), n_sensors frames mounted on the body with
+    distinct, non-trivial offsets (`offsets` [n_sensors][3 | 12] replaces the built-in ones), and n_poses * edges_per_pose offset
+    edges.  Edge e of pose k runs from sensor (k + e) % n_sensors on pose k to sensor (k + 2 e + 1) % n_sensors on pose k + 1 + e
+    (past the end: wrapped to the first poses), so the list holds edges with from != to parameter (and, with one sensor or where
+    the two coincide, from == to) and edges from and to the fixed pose 0; the LAST edge is edge 0 reversed, pose 1 -> pose 0 with
+    the parameters swapped: a vertex pair in both orders.  Measurement = (Xi Pi)^-1 (Xj Pj) of the true poses times a motion of
+    noise[0] * N(0, 1) in t and noise[1] * N(0, 1) in the rotation (vector); information diag(1 / noise^2).  Initial poses: the true
+    ones times a motion of perturb[0] / perturb[1]; pose 0 is fixed at its true pose.  Deterministic from seed.
+    Returns kind, n, nP, poses, poses_true, hidx, vi, vj, Z, omega (odometry), offset_type (18 | 19), oi, oj, opf, opt, omeas,
+    oinfo, offsets."""
+    if kind not in ("se2", "se3") or n_poses < 3 or n_sensors < 1 or edges_per_pose < 1 or edges_per_pose > n_poses - 2:
+        raise ValueError("make_offset_rig: kind se2 | se3, n_poses >= 3, n_sensors >= 1, 1 <= edges_per_pose <= n_poses - 2")
+    se3 = kind == "se3"
+    rng = CounterRng(seed + 1)
+    n, d, ms = n_poses, (6 if se3 else 3), (12 if se3 else 3)
+    s = np.arange(n, dtype=np.float64)
+    k = np.repeat(np.arange(n), edges_per_pose)
+    e = np.tile(np.arange(edges_per_pose), n)
+    oi, oj = k.astype(np.int32), ((k + 1 + e) % n).astype(np.int32)
+    opf, opt = ((k + e) % n_sensors).astype(np.int32), ((k + 2 * e + 1) % n_sensors).astype(np.int32)
+    oi[-1], oj[-1], opf[-1], opt[-1] = oj[0], oi[0], opt[0], opf[0]
+    vi, vj = np.arange(n - 1, dtype=np.int32), np.arange(1, n, dtype=np.int32)
+    m = len(oi)
+    q = np.arange(n_sensors, dtype=np.float64)
+
+    def motion(stream, count, scale):
+        return np.concatenate([scale[0] * np.stack([rng.normal(stream + c, count) for c in range(3 if se3 else 2)], axis=1),
+                               scale[1] * np.stack([rng.normal(stream + 3 + c, count) for c in range(3 if se3 else 1)], axis=1)], axis=1)
+
+    if se3:
+        X = (_exp_so3(np.stack([0.3 * np.sin(0.9 * s), 0.25 * np.sin(0.37 * s), 0.6 * np.sin(0.21 * s)], axis=1))[0],
+             np.stack([0.5 * s, np.sin(0.3 * s), 0.2 * np.cos(0.2 * s)], axis=1))
+        if offsets is None:
+            P = (_exp_so3(np.stack([0.4 + 0.5 * q, -0.3 + 0.35 * q, 0.9 - 0.7 * q], axis=1))[0],
+                 np.stack([0.3 + 0.1 * q, -0.2 + 0.15 * q, 0.1 + 0.05 * q * q], axis=1))
+        else:
+            T = np.asarray(offsets, np.float64).reshape(n_sensors, 12)
+            P = (T[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1), T[:, 9:])
+        take = lambda A, idx: (A[0][idx], A[1][idx])
+        expm = lambda v: (_exp_so3(v[:, 3:])[0], v[:, :3])
+        Z0 = _iso_mul(_iso_mul(_iso_inv(take(X, vi)), take(X, vj)), expm(motion(10, n - 1, noise)))
+        Zo = _iso_mul(_iso_mul(_iso_inv(_iso_mul(take(X, oi), take(P, opf))), _iso_mul(take(X, oj), take(P, opt))), expm(motion(20, m, noise)))
+        step = motion(30, n, perturb)
+        step[0] = 0.0
+        Xe = _iso_mul(X, expm(step))
+        pack = lambda A: _iso_pack(A[0], A[1])
+    else:
+        X = np.stack([0.5 * s, np.sin(0.3 * s), 0.4 * np.sin(0.21 * s) + 0.05 * s], axis=1)
+        X[:, 2] = (X[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
+        P = np.stack([0.3 + 0.1 * q, -0.2 + 0.15 * q, 0.7 - 1.1 * q], axis=1) if offsets is None else np.asarray(offsets, np.float64).reshape(n_sensors, 3)
+        Z0 = _se2_mul(_se2_mul(_se2_inv(X[vi]), X[vj]), motion(10, n - 1, noise))
+        Zo = _se2_mul(_se2_mul(_se2_inv(_se2_mul(X[oi], P[opf])), _se2_mul(X[oj], P[opt])), motion(20, m, noise))
+        step = motion(30, n, perturb)
+        step[0] = 0.0
+        Xe = _se2_mul(X, step)
+        pack = lambda A: A
+    nt = 3 if se3 else 2
+    w = np.diag([1.0 / noise[0] ** 2] * nt + [1.0 / noise[1] ** 2] * (d - nt))
+    return dict(kind=kind, n=n, nP=n - 1, poses=pack(Xe), poses_true=pack(X), hidx=(np.arange(n, dtype=np.int32) - 1).astype(np.int32),
+                vi=vi, vj=vj, Z=pack(Z0), omega=np.tile(w.reshape(1, d * d), (n - 1, 1)), offset_type=19 if se3 else 18, oi=oi, oj=oj,
+                opf=opf, opt=opt, omeas=pack(Zo), oinfo=np.tile(w.reshape(1, d * d), (m, 1)), offsets=pack(P).reshape(n_sensors, ms).copy())
