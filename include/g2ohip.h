@@ -773,9 +773,42 @@ int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const
  * set owns no vertices); robust kernels and chi2 as for any set; g2ohip_clear_edge_sets drops the binding; a set grown by
  * g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.
  * The kernels are timed under the "pg_landmark_linearize" slot.  Not covered: more than one offset set per handle, sharded
- * solves, the g2o plugin adapter, EdgeSE2PointXYOffset, bearing edges. */
+ * solves, the g2o plugin adapter, EdgeSE2PointXYOffset. */
 int g2ohip_pg_set_offset_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const int32_t* param_from,
                                const int32_t* param_to, const double* meas, const double* info, int n_params, const double* offsets);
+/* ---- ... bearing-only observations of 2-D point landmarks: what g2o_simulator2d's bearing sensor writes ---------------------
+ * ONE set of EdgeSE2PointXYBearing (type 20; tag EDGE_BEARING_SE2_XY, g2o/types/slam2d/edge_se2_pointxy_bearing.h:43-50
+ * computeError, edge_se2_pointxy_bearing.cpp:56-66 read / write) over a VertexSE2 and a VertexPointXY, beside a type-1 pose set
+ * only, in a "bearing slot" of its own: independent of the prior and offset slots, and WITH OR WITHOUT an EdgeSE2PointXY set
+ * (type 3) in the landmark slot -- both sets index the one landmark table of g2ohip_pg_set_landmark_estimates.  A later call
+ * replaces the binding.  With pose (x, y, th), landmark (lx, ly), c = cos th, s = sin th, dx = lx - x, dy = ly - y:
+ *   deltax = c dx + s dy,  deltay = -s dx + c dy,  e = normalize_theta(z - atan2(deltay, deltax))     (error dimension 1)
+ * DELIBERATE DEVIATION: the reference defines no linearizeOplus for this edge and differentiates numerically
+ * (base_binary_edge.hpp:132-201, central difference, delta = 1e-9), which across the +-pi wrap of the error is wrong by
+ * 2 pi / (2 delta); the device writes the exact derivative with respect to VertexSE2::oplusImpl (t += u[0:2], th += u[2]) and
+ * VertexPointXY::oplusImpl, as for types 7 and 18: with r2 = dx dx + dy dy
+ *   J0 = (-dy / r2, dx / r2, 1)  [1 x 3],   J1 = (dy / r2, -dx / r2)  [1 x 2].
+ * Like the reference there is no guard for a landmark on top of the pose (r2 == 0): infinities / NaNs.
+ * Edge set `set` was added as a binary set with error_dim 1 over the poses' and the landmarks' hessian indices (-1 = fixed) on a
+ * handle of (pose, landmark) dimensions (3, 2); pose_vertex indexes the table of g2ohip_pg_set_estimates, point_vertex the table
+ * of g2ohip_pg_set_landmark_estimates; meas [n][1] the measured angles, info [n][1].  n = 0 is legal (the arrays may then be
+ * NULL) and replaces the binding.
+ * Call after g2ohip_build_structure and g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).  G2OHIP_ERR_ARG: a pose set of a type
+ * other than 1, a set of other dimensions or a unary one, a set already bound in another slot, a null array with n > 0, an index
+ * outside the pose or landmark table, a hessian index that differs from the set's, a non-finite value -- validated before
+ * anything is committed: a rejected call leaves the previous binding usable.  While a set is bound the other g2ohip_pg_set_*
+ * entries refuse its set id and g2ohip_pg_set_edges refuses pose types other than 1.  g2ohip_pg_set_estimates and
+ * g2ohip_pg_set_landmark_estimates with changed tables validate the set again; g2ohip_pg_linearize without a landmark table
+ * returns G2OHIP_ERR_STATE; update / push / pop / discard_top move the landmark table as for a type-3 set; robust kernels, chi2,
+ * do_schur 0 / 1 as for any set; g2ohip_clear_edge_sets drops the binding; a set grown by g2ohip_update_structure makes
+ * g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.
+ * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: EdgeSE2PointXYOffset (in the reference its
+ * computeError reads the cache's w2lMatrix, the inverse of the vertex estimate WITHOUT the offset, while its linearizeOplus mixes
+ * the offset's rotation into one column, parameter_se2_offset.cpp:87-96: which of the two is meant has to be decided first),
+ * EdgeSE2PointXYCalib, more than one bearing set per handle, sharded solves, the g2o plugin adapter, a 3-D counterpart (the
+ * reference has none). */
+int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex,
+                                const double* meas, const double* info);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -64,7 +64,7 @@ EXPORTS = [
     "g2ohip_pg_set_landmark_edges", "g2ohip_pg_set_landmark_estimates", "g2ohip_pg_get_landmark_estimates",
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
-    "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges",
+    "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges", "g2ohip_pg_set_bearing_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -176,6 +176,7 @@ def load():
     L.g2ohip_pg_set_prior_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_gicp_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_offset_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
+    L.g2ohip_pg_set_bearing_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -549,6 +550,7 @@ class HipBlockSolver:
         self.gicp_set = None                # (the library drops every front-end binding)
         self.cam_set = self.scale_set = None
         self.offset_set = None
+        self.bearing_set = None
         self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
@@ -570,6 +572,7 @@ class HipBlockSolver:
                 self.gicp_set = None
                 self.cam_set = self.scale_set = None
                 self.offset_set = None
+                self.bearing_set = None
                 self._pg_owner_sets = set()
         return True
 
@@ -919,6 +922,20 @@ class HipBlockSolver:
         _check(self.L.g2ohip_pg_set_offset_edges(self.h, set_id, edge_type, _ip(vi), _ip(vj), _ip(pf), _ip(pt), _dp(meas), _dp(info),
                                                  len(table), _dp(table)), "pgSetOffsetEdges")
         self.offset_set = set_id
+
+    bearing_set = None   # set id of the bound EdgeSE2PointXYBearing set (pgSetBearingEdges)
+
+    def pgSetBearingEdges(self, set_id, pose_vertex, point_vertex, meas, info):
+        """Bearing-only observations of 2-D point landmarks (EdgeSE2PointXYBearing, type 20) beside an EdgeSE2 pose set, in a slot of
+        its own with or without an EdgeSE2PointXY set: pose_vertex indexes the table of pgSetEstimates, point_vertex the table of
+        pgSetLandmarkEstimates, meas [n] the measured angles, info [n].  The set is a binary one with error_dim 1
+        (addEdgeSet(1, hidx[pose_vertex], pt_hidx[point_vertex])).  After pgSetEdges."""
+        vpp, vll, meas, info = _i32(pose_vertex), _i32(point_vertex), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        if len(vpp) != n or len(vll) != n or meas.size != n or info.size != n:
+            raise ValueError("pgSetBearingEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        _check(self.L.g2ohip_pg_set_bearing_edges(self.h, set_id, _ip(vpp), _ip(vll), _dp(meas), _dp(info)), "pgSetBearingEdges")
+        self.bearing_set = set_id
 
     cam_set = scale_set = None     # set ids of the bound EdgeSBACam / EdgeSBAScale sets (pgSetCamEdges)
 

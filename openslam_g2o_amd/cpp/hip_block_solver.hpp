@@ -155,6 +155,12 @@ class HipBlockSolver {
                         const double* meas, const double* info, int nParams, const double* offsets) {
     return ok(g2ohip_pg_set_offset_edges(h_, set, type, vi, vj, paramFrom, paramTo, meas, info, nParams, offsets), "pgSetOffsetEdges");
   }
+  // Bearing-only observations of 2-D point landmarks (g2ohip_pg_set_bearing_edges): EdgeSE2PointXYBearing beside an EdgeSE2 set, in
+  // a slot of its own with or without an EdgeSE2PointXY set; poseVertex / pointVertex index the pose and landmark tables, meas [n]
+  // the measured angles, info [n]
+  bool pgSetBearingEdges(int set, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas, const double* info) {
+    return ok(g2ohip_pg_set_bearing_edges(h_, set, poseVertex, pointVertex, meas, info), "pgSetBearingEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

@@ -105,6 +105,7 @@ class BlockSolver {
   void pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov);
   void pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to, const double* meas,
                            const double* info, int n_params, const double* offsets);
+  void pg_set_bearing_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info);
   void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -521,6 +522,13 @@ class BlockSolver {
     DevBuf<int> oi, oj, opf, opt;
     std::vector<int> h_oi, h_oj;   // host copies: index validation (pg_validate)
     DevBuf<double> off_meas, off_table;
+    // ONE set `br_set` of bearing-only observations EdgeSE2PointXYBearing (type 20, error 1) beside type 1, in a slot of its own
+    // with or without a type-3 set in the landmark slot: bp indexes `poses`, bl the SAME landmark table `points`, br_meas [n] the
+    // measured angles (pg_bearing.inc).  The estimates, the update and push / pop are those of the landmark half.
+    int br_set = -1;
+    DevBuf<int> bp, bl;
+    std::vector<int> h_bp, h_bl;   // host copies: index validation (pg_validate_landmarks)
+    DevBuf<double> br_meas;
     // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
     // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
     // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.

@@ -2313,6 +2313,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_sbacam_edge.inc"
 #include "pg_gicp.inc"
 #include "pg_offset.inc"
+#include "pg_bearing.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
@@ -2574,8 +2575,8 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
     // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
-    // (pg_set_gicp_edges again), a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again) or a grown sensor-offset set
-    // (pg_set_offset_edges again)
+    // (pg_set_gicp_edges again), a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again), a grown sensor-offset set
+    // (pg_set_offset_edges again) or a grown bearing set (pg_set_bearing_edges again)
     if (set == pg_.set || set == pg_.lm_set) {
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -3296,7 +3297,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
   const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
-                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set;
+                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5985,6 +5986,9 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (pg_.off_set >= 0 && type != pg_.off_type - 17)
     throw ArgFailure("pg_set_edges: a sensor-offset set is bound: EdgeSE2Offset (18) stands beside an EdgeSE2 pose set (1) only, EdgeSE3Offset (19) beside EdgeSE3 (2)");
   if (set == pg_.off_set) throw ArgFailure("pg_set_edges: the set is bound as the sensor-offset set");
+  if (pg_.br_set >= 0 && type != 1)
+    throw ArgFailure("pg_set_edges: an EdgeSE2PointXYBearing set (20) is bound: it stands beside an EdgeSE2 pose set (1) only");
+  if (set == pg_.br_set) throw ArgFailure("pg_set_edges: the set is bound as the bearing set");
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
@@ -6061,6 +6065,9 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
     if (pg_.cam_set >= 0) pg_validate(*sets_[pg_.cam_set], pg_.h_ci.data(), pg_.h_cj.data(), pg_.h_ci.size(), hidx, nv);
     if (pg_.scale_set >= 0) pg_validate(*sets_[pg_.scale_set], pg_.h_si.data(), pg_.h_sj.data(), pg_.h_si.size(), hidx, nv);
     if (pg_.off_set >= 0) pg_validate(*sets_[pg_.off_set], pg_.h_oi.data(), pg_.h_oj.data(), pg_.h_oi.size(), hidx, nv);
+    if (pg_.br_set >= 0)
+      pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), hidx, nv, pg_.points.h_hidx.data(),
+                            pg_.points.n);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -6164,6 +6171,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (set == pg_.gicp_set) throw ArgFailure(w + ": the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure(w + ": the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure(w + ": the set is bound as the sensor-offset set");
+  if (set == pg_.br_set) throw ArgFailure(w + ": the set is bound as the bearing set");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -6221,6 +6229,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the sensor-offset set");
+  if (set == pg_.br_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the bearing set");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -6276,6 +6285,7 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   if (set == pg_.pr_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the prior set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the sensor-offset set");
+  if (set == pg_.br_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the bearing set");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6335,6 +6345,7 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
   if (set == pg_.pr_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the prior set");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (set == pg_.br_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the bearing set");
   EdgeSet& es = *sets_[set];
   const int d = type == 18 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d || p_ != d)
@@ -6383,6 +6394,57 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
+// ---- ... bearing-only observations of 2-D point landmarks: EdgeSE2PointXYBearing (type 20) beside an EdgeSE2 set, ONE set in a
+// slot of its own (pg_bearing.inc), with or without an EdgeSE2PointXY set (type 3) in the landmark slot: both index the landmark
+// table of pg_set_landmark_estimates.  The contract of the sensor-offset entry: validate everything, then commit; a later call
+// replaces the slot's set and clears the data of the set that leaves it; n = 0 is legal.
+void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_bearing_edges: call pg_set_edges first (the pose-pose set the bearing set stands beside)");
+  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (pg_.type != 1) throw ArgFailure("pg_set_bearing_edges: EdgeSE2PointXYBearing (20) goes with an EdgeSE2 pose set (1)");
+  if (set == pg_.set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the pose-pose set");
+  if (set == pg_.lm_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the landmark set");
+  if (set == pg_.pr_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the prior set");
+  if (set == pg_.gicp_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the GICP set");
+  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
+  if (set == pg_.off_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the sensor-offset set");
+  EdgeSet& es = *sets_[set];
+  // (a set of zero edges has no vertex classes: build_structure gives it pose dimensions on both sides)
+  if (es.unary || es.d != 1 || p_ != 3 || l_ != 2 || (es.n > 0 && (es.dim0 != 3 || es.dim1 != 2)))
+    throw ArgFailure("pg_set_bearing_edges: the set must be a binary pose-landmark set with (error, pose, landmark) dimensions (1, 3, 2)");
+  const size_t n = (size_t)es.n;
+  if (n > 0 && (!pose_vertex || !point_vertex || !meas || !info)) throw ArgFailure("pg_set_bearing_edges: null array");
+  for (size_t k = 0; k < n; ++k) {
+    if (!std::isfinite(meas[k])) throw ArgFailure("pg_set_bearing_edges: non-finite measurement in edge " + std::to_string(k));
+    if (!std::isfinite(info[k])) throw ArgFailure("pg_set_bearing_edges: non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  if (pg_.br_set >= 0 && pg_.br_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
+    EdgeSet& old = *sets_[pg_.br_set];
+    old.has_data = old.has_err = false;
+  }
+  pg_.br_set = set;
+  pg_.h_bp.assign(pose_vertex, pose_vertex + n);
+  pg_.h_bl.assign(point_vertex, point_vertex + n);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.bp.upload(pose_vertex, n, st_);
+  pg_.bl.upload(point_vertex, n, st_);
+  pg_.br_meas.upload(meas, n, st_);
+  es.own_omega.upload(info, n, st_);
+  es.own_J0.alloc(n * 3);
+  es.own_J1.alloc(n * 2);
+  es.own_err.alloc(n);
+  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  es.external = false;
+  es.has_data = false;
+  es.has_err = false;
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
 // ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
 // own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
 // validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
@@ -6401,6 +6463,7 @@ void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* 
   if (set == pg_.pr_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the prior set");
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the GICP set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the sensor-offset set");
+  if (set == pg_.br_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the bearing set");
   if (set == (cam ? pg_.scale_set : pg_.cam_set))
     throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
   EdgeSet& es = *sets_[set];
@@ -6464,6 +6527,9 @@ void BlockSolver::pg_set_landmark_estimates(int n_points, const double* points, 
     if (pg_.lm_set >= 0)
       pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), pg_.poses.h_hidx.data(), pg_.poses.n,
                             hidx, n_points);
+    if (pg_.br_set >= 0)   // (with or without a set in the landmark slot)
+      pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), pg_.poses.h_hidx.data(), pg_.poses.n,
+                            hidx, n_points);
     invalidate_graphs();
   }
   pg_.err_valid = pg_.jac_valid = false;
@@ -6502,8 +6568,15 @@ void BlockSolver::pg_linearize(bool jacobians) {
   EdgeSet* eo = pg_.off_set >= 0 ? sets_[pg_.off_set].get() : nullptr;
   if (eo && (int)pg_.h_oi.size() != eo->n)
     throw StateFailure("pg_linearize: the sensor-offset edge set has grown since pg_set_offset_edges (g2ohip_update_structure): call pg_set_offset_edges again");
+  EdgeSet* eb = pg_.br_set >= 0 ? sets_[pg_.br_set].get() : nullptr;
+  if (eb) {
+    if (pg_.points.n <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
+    if ((int)pg_.h_bp.size() != eb->n)
+      throw StateFailure("pg_linearize: the bearing edge set has grown since pg_set_bearing_edges (g2ohip_update_structure): call pg_set_bearing_edges again");
+  }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     if (jacobians && eo) eo->has_data = true;
+    if (jacobians && eb) eb->has_data = true;
     if (jacobians) es.has_data = true;
     if (jacobians && el) el->has_data = true;
     if (jacobians && ep) ep->has_data = true;
@@ -6536,8 +6609,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
   }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
   const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0, off_launch = eo && eo->n > 0;
+  const bool br_launch = eb && eb->n > 0;
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                        pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
@@ -6623,7 +6697,15 @@ void BlockSolver::pg_linearize(bool jacobians) {
                            pg_.opt.p, pg_.off_meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
     });
   }
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (br_launch) {   // EdgeSE2PointXYBearing -- pg_bearing.inc
+    const dim3 grid(grid_for(eb->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      hipLaunchKernelGGL(pg_se2_bearing_linearize_kernel<STAGED>, grid, block, 0, st_, eb->n, pg_.poses.val.p, pg_.points.val.p, pg_.bp.p,
+                         pg_.bl.p, pg_.br_meas.p, eb->own_J0.p, eb->own_J1.p, eb->own_err.p, jac);
+    });
+  }
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
@@ -6639,7 +6721,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
     eg->has_err = true;
     if (jacobians) eg->has_data = true;
   }
-  for (EdgeSet* e : {ec, esc, eo})
+  for (EdgeSet* e : {ec, esc, eo, eb})
     if (e) {
       e->has_err = true;
       if (jacobians) e->has_data = true;

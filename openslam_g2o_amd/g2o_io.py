@@ -75,7 +75,11 @@ def read_g2o(path):
     IDS as written), off_meas [m][3 | 7], off_info [m][d][d] and off_kind ("se2" | "se3"); PARAMS_SE2OFFSET lines (id x y theta:
     ParameterSE2Offset::read) give offsets2 {id: (x y theta)}.  An edge that names a parameter id the file does not define, or a
     file that mixes the two edge tags, raises ValueError (offset_problem turns the keys into a problem dict); a file without
-    these tags gives none of these keys."""
+    these tags gives none of these keys.
+    A file with EDGE_BEARING_SE2_XY lines (id_pose id_point z info: EdgeSE2PointXYBearing::read,
+    g2o/types/slam2d/edge_se2_pointxy_bearing.cpp:56-66) also gives br_vp / br_vl (pose-table and point-table index of every
+    bearing), br_meas [m] and br_info [m] (bearing_problem turns them into a problem dict); a file without them gives none of
+    these keys."""
     from . import sim3 as S3
     g_i, g_j, g_vals = [], [], []
     sim3_extras = []
@@ -87,6 +91,7 @@ def read_g2o(path):
     lkind, cameras = [], {}
     qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
     o_i, o_j, o_from, o_to, o_meas, o_info, o_kind, offsets2 = [], [], [], [], [], [], None, {}
+    b_p, b_l, b_meas, b_info = [], [], [], []
     kind = None
     with open(path) as f:
         for line in f:
@@ -185,6 +190,11 @@ def read_g2o(path):
                 ll.append(int(t[2]))
                 lmeas.append([float(x) for x in t[3:5]])
                 linfo.append(_upper_to_full([float(x) for x in t[5:8]], 2))
+            elif tag == "EDGE_BEARING_SE2_XY":
+                b_p.append(int(t[1]))
+                b_l.append(int(t[2]))
+                b_meas.append(float(t[3]))
+                b_info.append(float(t[4]))
             elif tag == "VERTEX_TRACKXYZ":
                 pid.append(int(t[1]))
                 pest.append([float(x) for x in t[2:5]])
@@ -262,7 +272,7 @@ def read_g2o(path):
         if cs_i:
             out.update(cam_scale_vi=np.asarray([lut[a] for a in cs_i], np.int32), cam_scale_vj=np.asarray([lut[a] for a in cs_j], np.int32),
                        cam_scale_meas=np.asarray(cs_meas, np.float64), cam_scale_info=np.asarray(cs_info, np.float64))
-    if pid or lp or offsets or cameras:
+    if pid or lp or offsets or cameras or b_p:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
         pid = pid[po]
@@ -273,6 +283,9 @@ def read_g2o(path):
                    lm_param=np.asarray(lparam, np.int32), offsets=offsets, fixed_points=[plut[f] for f in fixed if f in plut])
         if cameras or any(k != "xyz" for k in lkind):
             out.update(lm_kind=lkind, cameras=cameras)
+        if b_p:
+            out.update(br_vp=np.asarray([lut[a] for a in b_p], np.int32), br_vl=np.asarray([plut[a] for a in b_l], np.int32),
+                       br_meas=np.asarray(b_meas, np.float64), br_info=np.asarray(b_info, np.float64))
     if g_i:
         gv = np.asarray(g_vals, np.float64).reshape(-1, 12)
         out.update(gicp_vi=np.asarray([lut[a] for a in g_i], np.int32), gicp_vj=np.asarray([lut[a] for a in g_j], np.int32),
@@ -685,6 +698,32 @@ def write_g2o_landmarks(path, prob):
             zq = prob["zq"] if se2 else qt(prob["zq"])
             for e in range(len(prob["vq"])):
                 f.write("%s %d %s%s %s\n" % (tag, prob["vq"][e], "" if se2 else "1 ", fmt(zq[e]), upper(np.asarray(prob["omega_q"][e]), dq)))
+
+
+def bearing_problem(rd, fixed_poses=None, fixed_points=None):
+    """read_g2o() result of a 2-D file with EDGE_BEARING_SE2_XY lines -> the problem dict of
+    openslam_g2o_amd.synthetic.make_bearing_slam (what lm.setup_device_landmark_slam takes): landmark_problem's dict -- its
+    EDGE_SE2_XY observations may be none, bearing-only SLAM -- plus bp, bl, zb [m], omega_b [m] and B = m."""
+    if "br_vp" not in rd or rd.get("kind") != "se2":
+        raise ValueError("the file has no EDGE_BEARING_SE2_XY edges over VERTEX_SE2 / VERTEX_XY")
+    if len(rd["lm_vp"]) == 0:   # (bearing-only: the empty observation arrays in the shapes landmark_problem reads)
+        rd = dict(rd, lm_meas=np.zeros((0, 2)), lm_info=np.zeros((0, 2, 2)))
+    out = landmark_problem(rd, fixed_poses, fixed_points)
+    out.update(bp=rd["br_vp"], bl=rd["br_vl"], zb=rd["br_meas"].copy(), omega_b=rd["br_info"].copy(), B=len(rd["br_vp"]))
+    return out
+
+
+def write_g2o_bearing(path, prob):
+    """make_bearing_slam-style problem -> `.g2o` text: what write_g2o_landmarks writes for its poses, landmarks, odometry and (if
+    any) EDGE_SE2_XY observations, followed by one EDGE_BEARING_SE2_XY id_pose id_point z info line per bearing (landmark j has
+    the id n + j)."""
+    if prob["kind"] != "se2":
+        raise ValueError("write_g2o_bearing: EdgeSE2PointXYBearing belongs to kind 'se2'")
+    write_g2o_landmarks(path, prob)
+    n = len(prob["poses"])
+    with open(path, "a") as f:
+        for e in range(len(prob["bp"])):
+            f.write("EDGE_BEARING_SE2_XY %d %d %.17g %.17g\n" % (prob["bp"][e], n + prob["bl"][e], prob["zb"][e], prob["omega_b"][e]))
 
 
 # ---- bundle-adjustment tags (SURVEY.md 8f.2) --------------------------------------------------------------

@@ -424,10 +424,15 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     marginalised (schur=True).  huber_delta > 0: Huber kernel on the observation set.  Returns (solver, DevicePoseGraph);
     solver.landmark_sets = (odometry set id, observation set id).  A prob that carries `prior` ("pose" | "xy", with vq, zq,
     omega_q and -- 3-D -- prior_offset) also gets its unary prior set bound (EdgeSE2Prior / EdgeSE2XYPrior / EdgeSE3Prior):
-    solver.prior_set = its set id."""
+    solver.prior_set = its set id.  A prob of kind "se2" that carries bp, bl, zb and omega_b (synthetic.make_bearing_slam,
+    g2o_io.bearing_problem) also gets its bearing-only observations bound (EdgeSE2PointXYBearing over the same landmark table):
+    solver.bearing_set = their set id, huber_delta applies to them as well; the EdgeSE2PointXY set is then added only if
+    prob["vp"] is present and non-empty (bearing-only SLAM otherwise: solver.landmark_sets = (odometry set id, None))."""
     import numpy as np
     from . import capi
     se2 = prob["kind"] == "se2"
+    bearing = se2 and all(prob.get(k) is not None for k in ("bp", "bl", "zb", "omega_b"))
+    with_xy = not bearing or (prob.get("vp") is not None and len(prob["vp"]) > 0)
     obs = prob.get("observation", "xyz")
     if obs in ("depth", "disparity") and prob.get("kcam") is None:
         raise ValueError("setup_device_landmark_slam: observation = %r needs kcam = (fx, fy, cx, cy)" % obs)
@@ -437,7 +442,9 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
         s.setOption(name, value)
     hidx, pt_hidx = np.asarray(prob["hidx"], np.int32), np.asarray(prob["pt_hidx"], np.int32)
     k0 = s.addEdgeSet(p, hidx[prob["vi"]], hidx[prob["vj"]])
-    k1 = s.addEdgeSet(l, hidx[prob["vp"]], pt_hidx[prob["vl"]])
+    k1 = s.addEdgeSet(l, hidx[prob["vp"]], pt_hidx[prob["vl"]]) if with_xy else None
+    if bearing:
+        kb = s.addEdgeSet(1, hidx[np.asarray(prob["bp"], np.int64)], pt_hidx[np.asarray(prob["bl"], np.int64)])
     prior = prob.get("prior")
     if prior is not None:
         ptype = 9 if not se2 else (8 if prior == "xy" else 7)
@@ -448,14 +455,18 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     if obs in ("depth", "disparity"):
         s.pgSetLandmarkCameraEdges(k1, 5 if obs == "depth" else 6, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"],
                                    prob.get("offset"), prob["kcam"])
-    else:
+    elif with_xy:
         s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
+    if bearing:
+        s.pgSetBearingEdges(kb, prob["bp"], prob["bl"], prob["zb"], prob["omega_b"])
     s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
     if prior is not None:
         s.pgSetPriorEdges(kq, ptype, prob["vq"], prob["zq"], prob["omega_q"], prob.get("prior_offset"))
         s.prior_set = kq
-    if huber_delta > 0:
+    if huber_delta > 0 and with_xy:
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
+    if huber_delta > 0 and bearing:
+        s.setRobustKernel(kb, capi.KERNEL_HUBER, huber_delta)
     s.landmark_sets = (k0, k1)
     return s, DevicePoseGraph(s)
 

@@ -1006,3 +1006,60 @@ def make_offset_rig(kind="se3", n_poses=12, n_sensors=2, edges_per_pose=3, seed=
     return dict(kind=kind, n=n, nP=n - 1, poses=pack(Xe), poses_true=pack(X), hidx=(np.arange(n, dtype=np.int32) - 1).astype(np.int32),
                 vi=vi, vj=vj, Z=pack(Z0), omega=np.tile(w.reshape(1, d * d), (n - 1, 1)), offset_type=19 if se3 else 18, oi=oi, oj=oj,
                 opf=opf, opt=opt, omeas=pack(Zo), oinfo=np.tile(w.reshape(1, d * d), (m, 1)), offsets=pack(P).reshape(n_sensors, ms).copy())
+
+
+def make_bearing_slam(n_poses, n_landmarks, with_xy=False, seed=42, noise=0.02, perturb=(0.1, 0.02, 0.2), min_parallax=0.2,
+                      min_distance=0.5, **landmark_args):
+    """2-D landmark SLAM with bearing-only observations (EdgeSE2PointXYBearing, what g2o_simulator2d's bearing sensor writes), built
+    on make_landmark_slam("se2", n_poses, n_landmarks, seed=seed, perturb=perturb, **landmark_args): the same trajectory, odometry,
+    landmarks and observing pairs.  Every Cartesian observation (vp, vl) becomes a bearing (bp, bl, zb): the angle of the landmark
+    in the frame of the true pose plus noise * N(0, 1), wrapped into [-pi, pi); omega_b = 1 / noise^2.  No bearing is taken from
+    closer than min_distance, at the ground truth or at the initial estimates (the Jacobian grows like 1 / distance and the
+    reference has no guard at distance 0).
+    with_xy=True: the bearings stand beside the Cartesian observations (vp, vl, zl, omega_l unchanged: a point sensor and a
+    bearing sensor).  with_xy=False: bearing-only SLAM, the Cartesian keys are dropped (vp, vl of length 0, zl [0][2], omega_l
+    [0][4], M = 0); a bearing fixes a landmark only along one line, so every free landmark keeps at least two bearings whose
+    world-frame directions -- as lines, modulo pi -- differ by at least min_parallax, at the ground truth and at the initial
+    estimates; landmarks that cannot meet this are dropped together with their observations (otherwise their 2x2 block is
+    singular and the Schur complement has nothing to invert) and the landmark table is renumbered.
+    Returns the dict of make_landmark_slam plus bp, bl, zb [m], omega_b [m], B = m."""
+    g = make_landmark_slam("se2", n_poses, n_landmarks, seed=seed, perturb=perturb, **landmark_args)
+    rng = CounterRng(seed)
+    vp, vl = g["vp"], g["vl"]
+
+    def geometry(poses, points):
+        d = points[vl] - poses[vp, :2]
+        return np.hypot(d[:, 0], d[:, 1]), np.arctan2(d[:, 1], d[:, 0])
+    (r_t, w_t), (r_e, w_e) = geometry(g["poses_true"], g["points_true"]), geometry(g["poses"], g["points"])
+    keep = (r_t >= min_distance) & (r_e >= min_distance)
+    L = g["L"]
+    lm_keep = np.ones(L, bool)
+    if not with_xy:
+        # the kept observations of every landmark side by side (padded with NaN), then all pairs of a row at once
+        idx = np.nonzero(keep)[0]
+        idx = idx[np.argsort(vl[idx], kind="stable")]
+        count = np.bincount(vl[idx], minlength=L)
+        slot = np.arange(len(idx)) - np.repeat(np.cumsum(count) - count, count)
+        for w in (w_t, w_e):
+            a = np.full((L, max(int(count.max()), 1)), np.nan)
+            a[vl[idx], slot] = w[idx] % np.pi
+            diff = np.abs(a[:, :, None] - a[:, None, :])
+            with np.errstate(invalid="ignore"):
+                spread = np.nan_to_num(np.fmax.reduce(np.fmax.reduce(np.minimum(diff, np.pi - diff), axis=2), axis=1), nan=-1.0)
+            lm_keep &= (spread >= min_parallax) | (g["pt_hidx"] < 0)
+        keep &= lm_keep[vl]
+    bp, bl = vp[keep].astype(np.int32), vl[keep].astype(np.int32)
+    c, s = np.cos(g["poses_true"][bp, 2]), np.sin(g["poses_true"][bp, 2])
+    d = g["points_true"][bl] - g["poses_true"][bp, :2]
+    m = len(bp)
+    zb = _wrap(np.arctan2(-s * d[:, 0] + c * d[:, 1], c * d[:, 0] + s * d[:, 1]) + noise * rng.normal(270, len(vp))[keep])
+    out = dict(g)
+    if not with_xy:
+        new = np.cumsum(lm_keep) - 1
+        bl = new[bl].astype(np.int32)
+        free = lm_keep & (g["pt_hidx"] >= 0)
+        pt_hidx = np.where(free, g["nP"] + np.cumsum(free) - 1, -1)[lm_keep].astype(np.int32)
+        out.update(L=int(lm_keep.sum()), nL=int(free.sum()), points=g["points"][lm_keep], points_true=g["points_true"][lm_keep],
+                   pt_hidx=pt_hidx, vp=np.zeros(0, np.int32), vl=np.zeros(0, np.int32), zl=np.zeros((0, 2)), omega_l=np.zeros((0, 4)), M=0)
+    out.update(bp=bp, bl=bl, zb=zb, omega_b=np.full(m, 1.0 / noise ** 2), B=m)
+    return out
