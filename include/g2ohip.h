@@ -809,6 +809,45 @@ int g2ohip_pg_set_offset_edges(g2ohip_solver* s, int set, int type, const int32_
  * reference has none). */
 int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex,
                                 const double* meas, const double* info);
+/* ---- ... laser self-calibration (sclam2d): scan-match constraints that also estimate the sensor's mounting offset -----------
+ * ONE group of EdgeSE2SensorCalib (type 21; tag EDGE_SE2_CALIB, g2o/types/sclam2d/edge_se2_sensor_calib.h:45-59 computeError /
+ * setMeasurement, edge_se2_sensor_calib.cpp read / write), the edge of g2o/examples/calibration_odom_laser: a THREE-vertex edge
+ * over two VertexSE2 poses x1, x2 and the laser offset L, an ordinary VertexSE2 -- all three are rows of the one pose table of
+ * g2ohip_pg_set_estimates, so g2ohip_pg_update / push / pop / discard_top / get_estimates carry L like any pose.  Beside a type-1
+ * pose set only, in a "calibration slot" of its own: independent of the landmark, prior, offset and bearing slots; a later call
+ * replaces the binding.
+ *   e = toVector(Z^-1 * ((x1 * L)^-1 * x2 * L))          (error dimension 3, SE2's products and normalize_theta as se2.h)
+ * Z^-1 is computed per evaluation from the measurement, as _inverseMeasurement = m.inverse() would give it.
+ * DELIBERATE DEVIATION: the reference defines no linearizeOplus for this edge and differentiates numerically
+ * (base_multi_edge.hpp:63-116, central difference, delta = 1e-9); the device writes the exact derivative with respect to
+ * VertexSE2::oplusImpl (t += u[0:2], th += u[2]), as for types 7, 18 and 20: with Q = R(-(thz + th1 + thl)), J = [0 -1; 1 0],
+ * tA = t1 + R(th1) tl, tB = t2 + R(th2) tl
+ *   d e_t / d t1 = -Q                     d e_t / d th1 = -J Q (tB - tA) - Q J R(th1) tl     d e_th / d th1 = -1
+ *   d e_t / d t2 =  Q                     d e_t / d th2 =  Q J R(th2) tl                     d e_th / d th2 =  1
+ *   d e_t / d tl =  Q (R(th2) - R(th1))   d e_t / d thl = -J Q (tB - tA)                     d e_th / d thl =  0
+ * The Jacobian block of a fixed vertex (hessian index -1) is written as zeros.
+ * The edge is the three binary sets g2ohip_set_edge_set_parts documents for three vertices, added by the caller with error_dim 3
+ * over the vertices' hessian indices (-1 = fixed), all of the same edge count, on a handle of pose dimension 3:
+ *   set_ij  (i, j)  parts 0
+ *   set_il  (i, l)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_VERTEX1 | G2OHIP_PART_NO_CHI2
+ *   set_jl  (j, l)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_CHI2
+ * They are bound and released as one group and share Jacobians, information and errors on the device (as the sets of
+ * g2ohip_ba_set_inverse_depth_edges do).  vi / vj / vl index the pose table; meas [n][3] = (x, y, theta); info [n][3x3], NULL =
+ * identity.  Robust kernels: set the same kernel on all three sets.  L is a neighbour of every edge: the Hessian gets a dense
+ * block row, and one diagonal block receives a term from every edge.
+ * G2OHIP_ERR_STATE: a call before g2ohip_build_structure or before g2ohip_pg_set_edges, a set that carries per-edge robust
+ * kernels.  G2OHIP_ERR_ARG: a bad or repeated set id, a pose set of a type other than 1, wrong dimensions, parts or edge
+ * counts, a unary set, a set already bound in another slot, null vi / vj / vl / meas, a non-finite value, an index outside the
+ * pose table, a hessian index that differs from the sets' own, vl[k] == vi[k], vl[k] == vj[k] or vi[k] == vj[k] -- validated
+ * before anything is committed: a rejected call leaves the previous binding usable.  While the group is bound the other
+ * g2ohip_pg_set_* entries refuse its set ids and g2ohip_pg_set_edges refuses pose types other than 1.
+ * g2ohip_pg_set_estimates with changed tables validates the group again; g2ohip_clear_edge_sets drops the binding, and so does a
+ * g2ohip_update_structure that grows one of the three sets or the pose set (bind again after growth).
+ * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: EdgeSE2OdomDifferentialCalib and
+ * VertexOdomDifferentialParams (a vertex with a different oplus in the SE2 table: a change of its own), more than one calibration
+ * group per handle, sharded solves, the g2o plugin adapter. */
+int g2ohip_pg_set_sensor_calib_edges(g2ohip_solver* s, int set_ij, int set_il, int set_jl, const int32_t* vi, const int32_t* vj,
+                                     const int32_t* vl, const double* meas, const double* info);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -161,6 +161,13 @@ class HipBlockSolver {
   bool pgSetBearingEdges(int set, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas, const double* info) {
     return ok(g2ohip_pg_set_bearing_edges(h_, set, poseVertex, pointVertex, meas, info), "pgSetBearingEdges");
   }
+  // Laser self-calibration (g2ohip_pg_set_sensor_calib_edges): three-vertex EdgeSE2SensorCalib edges beside an EdgeSE2 set, as the
+  // three binary sets (i, j), (i, l), (j, l) with their parts; vi / vj / vl index the pose table (vl = the laser offset), meas
+  // [n][3], info [n][3x3] or null (identity)
+  bool pgSetSensorCalibEdges(int setIJ, int setIL, int setJL, const int32_t* vi, const int32_t* vj, const int32_t* vl, const double* meas,
+                             const double* info) {
+    return ok(g2ohip_pg_set_sensor_calib_edges(h_, setIJ, setIL, setJL, vi, vj, vl, meas, info), "pgSetSensorCalibEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

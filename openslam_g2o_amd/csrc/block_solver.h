@@ -106,6 +106,8 @@ class BlockSolver {
   void pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to, const double* meas,
                            const double* info, int n_params, const double* offsets);
   void pg_set_bearing_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info);
+  void pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, const int* vi, const int* vj, const int* vl, const double* meas,
+                                 const double* info);
   void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -372,6 +374,9 @@ class BlockSolver {
   void pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv, const int* pt_hidx,
                              int np) const;
   void pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const;
+  void pg_validate_calib(const int* vi, const int* vj, const int* vl, size_t n, const int* hidx, int nv) const;
+  void pg_cal_alias();
+  void pg_cal_release();
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                               const double* info, const double* offset, const double* kcam, int n_cams = 0);
   // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
@@ -529,6 +534,16 @@ class BlockSolver {
     DevBuf<int> bp, bl;
     std::vector<int> h_bp, h_bl;   // host copies: index validation (pg_validate_landmarks)
     DevBuf<double> br_meas;
+    // ONE group of EdgeSE2SensorCalib (type 21, error 3, THREE vertices: pose, pose, laser offset -- all rows of `poses`) beside
+    // type 1, in a slot of its own: the three binary sets cal_ij (i, j), cal_il (i, l), cal_jl (j, l) of
+    // g2ohip_set_edge_set_parts are bound and released together and share Jacobians, information and errors: J_i / J_j /
+    // information / errors live in cal_ij's buffers, J_l in cal_jl's own_J1, every other pointer of the three aliases one of
+    // those (pg_cal_alias).  cal_vi / cal_vj / cal_vl index `poses`, cal_meas [n][3] = (x, y, theta) (pg_calib.inc).
+    int cal_ij = -1, cal_il = -1, cal_jl = -1;
+    DevBuf<int> cal_vi, cal_vj, cal_vl;
+    std::vector<int> h_cal_vi, h_cal_vj, h_cal_vl;   // host copies: index validation (pg_validate)
+    DevBuf<double> cal_meas;
+    bool in_cal(int set) const { return set >= 0 && (set == cal_ij || set == cal_il || set == cal_jl); }
     // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
     // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
     // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.

@@ -2314,6 +2314,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_gicp.inc"
 #include "pg_offset.inc"
 #include "pg_bearing.inc"
+#include "pg_calib.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
@@ -2576,8 +2577,11 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
     // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
     // (pg_set_gicp_edges again), a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again), a grown sensor-offset set
-    // (pg_set_offset_edges again) or a grown bearing set (pg_set_bearing_edges again)
+    // (pg_set_offset_edges again) or a grown bearing set (pg_set_bearing_edges again); an EdgeSE2SensorCalib group goes as one
+    // when one of its three sets grows (pg_set_sensor_calib_edges again), its sets keep no pointer into each other's buffers
+    if (pg_.in_cal(set)) pg_cal_release();
     if (set == pg_.set || set == pg_.lm_set) {
+      pg_cal_release();
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
       pg_.fix_scale = fix_scale;
@@ -3297,7 +3301,7 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
   const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
-                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set;
+                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set || pg_.in_cal(set);
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5989,6 +5993,9 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (pg_.br_set >= 0 && type != 1)
     throw ArgFailure("pg_set_edges: an EdgeSE2PointXYBearing set (20) is bound: it stands beside an EdgeSE2 pose set (1) only");
   if (set == pg_.br_set) throw ArgFailure("pg_set_edges: the set is bound as the bearing set");
+  if (pg_.cal_ij >= 0 && type != 1)
+    throw ArgFailure("pg_set_edges: an EdgeSE2SensorCalib group (21) is bound: it stands beside an EdgeSE2 pose set (1) only");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_edges: the set is bound in the EdgeSE2SensorCalib group");
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
@@ -6068,6 +6075,7 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
     if (pg_.br_set >= 0)
       pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), hidx, nv, pg_.points.h_hidx.data(),
                             pg_.points.n);
+    if (pg_.cal_ij >= 0) pg_validate_calib(pg_.h_cal_vi.data(), pg_.h_cal_vj.data(), pg_.h_cal_vl.data(), pg_.h_cal_vi.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
@@ -6172,6 +6180,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure(w + ": the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure(w + ": the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure(w + ": the set is bound as the bearing set");
+  if (pg_.in_cal(set)) throw ArgFailure(w + ": the set is bound in the EdgeSE2SensorCalib group");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -6230,6 +6239,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the bearing set");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_prior_edges: the set is bound in the EdgeSE2SensorCalib group");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -6286,6 +6296,7 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the bearing set");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_gicp_edges: the set is bound in the EdgeSE2SensorCalib group");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6346,6 +6357,7 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the bearing set");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_offset_edges: the set is bound in the EdgeSE2SensorCalib group");
   EdgeSet& es = *sets_[set];
   const int d = type == 18 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d || p_ != d)
@@ -6410,6 +6422,7 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the GICP set");
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the sensor-offset set");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_bearing_edges: the set is bound in the EdgeSE2SensorCalib group");
   EdgeSet& es = *sets_[set];
   // (a set of zero edges has no vertex classes: build_structure gives it pose dimensions on both sides)
   if (es.unary || es.d != 1 || p_ != 3 || l_ != 2 || (es.n > 0 && (es.dim0 != 3 || es.dim1 != 2)))
@@ -6445,6 +6458,135 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
+// ---- ... laser self-calibration: EdgeSE2SensorCalib (type 21), a THREE-vertex edge over two poses and the laser offset L, all
+// rows of the one pose table, beside an EdgeSE2 set (pg_calib.inc).  The edge is the three binary sets g2ohip_set_edge_set_parts
+// documents for three vertices, all of the same edge count, error dimension 3 and vertex dimensions (3, 3):
+//   set_ij  (i, j)  parts 0                                  terms of i and j, H(i, j), chi2
+//   set_il  (i, l)  parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  H(i, l)
+//   set_jl  (j, l)  parts NO_VERTEX0 | NO_CHI2               terms of l, H(j, l)
+// They occupy the calibration slot as ONE group (the PSI2UV sets of ba_set_inverse_depth_edges are the precedent): pg_linearize
+// writes J_i / J_j / information / errors into set_ij's buffers and J_l into set_jl's own_J1, and every other pointer of the three
+// aliases one of those (27 + 3 doubles per edge leave the producer, not 54 + 9).  Robust kernels: the caller sets the same kernel
+// on all three sets (the generic assembly weighs each set by its own).  Validate, then commit; a later call releases the previous
+// group (pg_cal_release).
+void BlockSolver::pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, const int* vi, const int* vj, const int* vl,
+                                            const double* meas, const double* info) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0)
+    throw StateFailure("pg_set_sensor_calib_edges: call pg_set_edges first (the pose-pose set the calibration group stands beside)");
+  const int ids[3] = {set_ij, set_il, set_jl};
+  for (int id : ids)
+    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (set_ij == set_il || set_ij == set_jl || set_il == set_jl) throw ArgFailure("pg_set_sensor_calib_edges: the three sets must differ");
+  if (pg_.type != 1) throw ArgFailure("pg_set_sensor_calib_edges: EdgeSE2SensorCalib (21) goes with an EdgeSE2 pose set (1)");
+  for (int id : ids)
+    if (id == pg_.set || id == pg_.lm_set || id == pg_.pr_set || id == pg_.gicp_set || id == pg_.cam_set || id == pg_.scale_set ||
+        id == pg_.off_set || id == pg_.br_set)
+      throw ArgFailure("pg_set_sensor_calib_edges: set " + std::to_string(id) + " is bound in another slot");
+  EdgeSet &es = *sets_[set_ij], &ea = *sets_[set_il], &ec = *sets_[set_jl];
+  for (const EdgeSet* e : {&es, &ea, &ec})
+    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
+      throw ArgFailure("pg_set_sensor_calib_edges: the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
+  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
+    throw ArgFailure("pg_set_sensor_calib_edges: parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
+  if (ea.n != es.n || ec.n != es.n) throw ArgFailure("pg_set_sensor_calib_edges: the three sets must hold the same number of edges");
+  if (!vi || !vj || !vl || !meas) throw ArgFailure("pg_set_sensor_calib_edges: null array");
+  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
+    throw StateFailure("pg_set_sensor_calib_edges: a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0 || vl[k] < 0) throw ArgFailure("pg_set_sensor_calib_edges: negative vertex index in edge " + std::to_string(k));
+    if (vi[k] == vj[k] || vi[k] == vl[k] || vj[k] == vl[k])
+      throw ArgFailure("pg_set_sensor_calib_edges: edge " + std::to_string(k) + " names one vertex twice");
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure("pg_set_sensor_calib_edges: non-finite measurement in edge " + std::to_string(k));
+    if (info)
+      for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_sensor_calib_edges: non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ea, vi, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ec, vj, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  // commit: the previous group leaves the slot, with the data the device wrote for it
+  std::vector<double> identity;
+  if (!info) {   // information().setIdentity()
+    identity.assign(n * 9, 0.0);
+    for (size_t k = 0; k < n; ++k) identity[9 * k] = identity[9 * k + 4] = identity[9 * k + 8] = 1.0;
+    info = identity.data();
+  }
+  pg_cal_release();
+  pg_.cal_ij = set_ij;
+  pg_.cal_il = set_il;
+  pg_.cal_jl = set_jl;
+  pg_.h_cal_vi.assign(vi, vi + n);
+  pg_.h_cal_vj.assign(vj, vj + n);
+  pg_.h_cal_vl.assign(vl, vl + n);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.cal_vi.upload(vi, n, st_);
+  pg_.cal_vj.upload(vj, n, st_);
+  pg_.cal_vl.upload(vl, n, st_);
+  pg_.cal_meas.upload(meas, n * 3, st_);
+  es.own_omega.upload(info, n * 9, st_);
+  es.own_J0.alloc(n * 9);
+  es.own_J1.alloc(n * 9);
+  es.own_err.alloc(n * 3);
+  ec.own_J1.alloc(n * 9);
+  pg_cal_alias();
+  for (EdgeSet* e : {&es, &ea, &ec}) {
+    e->external = false;
+    e->has_data = false;   // becomes valid with the first pg_linearize
+    e->has_err = false;
+  }
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));   // (the identity staging buffer is read by the upload)
+}
+
+// the pointers of the three sets of a calibration group onto the buffers two of them own; a pointer that had to be repaired
+// (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences
+void BlockSolver::pg_cal_alias() {
+  EdgeSet &es = *sets_[pg_.cal_ij], &ea = *sets_[pg_.cal_il], &ec = *sets_[pg_.cal_jl];
+  const double *ji = es.own_J0.p, *jj = es.own_J1.p, *jl = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
+  const double* want[3][2] = {{ji, jj}, {ji, jl}, {jj, jl}};
+  EdgeSet* g[3] = {&es, &ea, &ec};
+  bool changed = false;
+  for (int i = 0; i < 3; ++i) {
+    EdgeSet& e = *g[i];
+    changed = changed || e.J0 != want[i][0] || e.J1 != want[i][1] || e.omega != om || e.err != er || e.external;
+    e.J0 = want[i][0];
+    e.J1 = want[i][1];
+    e.omega = om;
+    e.err = er;
+    e.external = false;
+  }
+  if (changed) drop_graph_segments();
+}
+
+// a calibration group leaves its slot: its sets keep no device-written data and no pointer into each other's buffers
+// (set_edge_data is their next source; build_system refuses them until then, unless they are empty)
+void BlockSolver::pg_cal_release() {
+  if (pg_.cal_ij < 0) return;
+  for (int id : {pg_.cal_ij, pg_.cal_il, pg_.cal_jl}) {
+    if (id < 0 || id >= (int)sets_.size()) continue;
+    EdgeSet& e = *sets_[id];
+    e.has_data = e.has_err = false;
+    e.J0 = e.J1 = e.omega = e.err = nullptr;
+  }
+  pg_.cal_ij = pg_.cal_il = pg_.cal_jl = -1;
+  pg_.h_cal_vi.clear();
+  pg_.h_cal_vj.clear();
+  pg_.h_cal_vl.clear();
+  pg_.err_valid = pg_.jac_valid = false;
+}
+
+// the three sets of a calibration group against a pose table
+void BlockSolver::pg_validate_calib(const int* vi, const int* vj, const int* vl, size_t n, const int* hidx, int nv) const {
+  pg_validate(*sets_[pg_.cal_ij], vi, vj, n, hidx, nv);
+  pg_validate(*sets_[pg_.cal_il], vi, vl, n, hidx, nv);
+  pg_validate(*sets_[pg_.cal_jl], vj, vl, n, hidx, nv);
+}
+
 // ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
 // own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
 // validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
@@ -6464,6 +6606,7 @@ void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* 
   if (set == pg_.gicp_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the GICP set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the bearing set");
+  if (pg_.in_cal(set)) throw ArgFailure("pg_set_cam_edges: the set is bound in the EdgeSE2SensorCalib group");
   if (set == (cam ? pg_.scale_set : pg_.cam_set))
     throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
   EdgeSet& es = *sets_[set];
@@ -6574,7 +6717,17 @@ void BlockSolver::pg_linearize(bool jacobians) {
     if ((int)pg_.h_bp.size() != eb->n)
       throw StateFailure("pg_linearize: the bearing edge set has grown since pg_set_bearing_edges (g2ohip_update_structure): call pg_set_bearing_edges again");
   }
+  EdgeSet* const ecal[3] = {pg_.cal_ij >= 0 ? sets_[pg_.cal_ij].get() : nullptr, pg_.cal_ij >= 0 ? sets_[pg_.cal_il].get() : nullptr,
+                            pg_.cal_ij >= 0 ? sets_[pg_.cal_jl].get() : nullptr};
+  if (ecal[0]) {
+    for (EdgeSet* e : ecal)
+      if ((int)pg_.h_cal_vi.size() != e->n)
+        throw StateFailure("pg_linearize: an EdgeSE2SensorCalib edge set has grown since pg_set_sensor_calib_edges: call it again");
+    pg_cal_alias();   // (before err_valid / jac_valid are read: a repaired pointer drops the captured launch sequences)
+  }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
+    for (EdgeSet* e : ecal)
+      if (jacobians && e) e->has_data = true;
     if (jacobians && eo) eo->has_data = true;
     if (jacobians && eb) eb->has_data = true;
     if (jacobians) es.has_data = true;
@@ -6609,9 +6762,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
   }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
   const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0, off_launch = eo && eo->n > 0;
-  const bool br_launch = eb && eb->n > 0;
+  const bool br_launch = eb && eb->n > 0, cal_launch = ecal[0] && ecal[0]->n > 0;
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                        pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
@@ -6705,7 +6858,16 @@ void BlockSolver::pg_linearize(bool jacobians) {
                          pg_.bl.p, pg_.br_meas.p, eb->own_J0.p, eb->own_J1.p, eb->own_err.p, jac);
     });
   }
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (cal_launch) {   // EdgeSE2SensorCalib -- pg_calib.inc
+    const dim3 grid(grid_for(ecal[0]->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      hipLaunchKernelGGL(pg_se2_calib_linearize_kernel<STAGED>, grid, block, 0, st_, ecal[0]->n, pg_.poses.val.p, pg_.poses.hidx.p, pg_.cal_vi.p,
+                         pg_.cal_vj.p, pg_.cal_vl.p, pg_.cal_meas.p, ecal[0]->own_J0.p, ecal[0]->own_J1.p, ecal[2]->own_J1.p, ecal[0]->own_err.p,
+                         jac);
+    });
+  }
+  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
   es.has_err = true;
   if (jacobians) es.has_data = true;
@@ -6721,7 +6883,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
     eg->has_err = true;
     if (jacobians) eg->has_data = true;
   }
-  for (EdgeSet* e : {ec, esc, eo, eb})
+  for (EdgeSet* e : {ec, esc, eo, eb, ecal[0], ecal[1], ecal[2]})
     if (e) {
       e->has_err = true;
       if (jacobians) e->has_data = true;

@@ -716,6 +716,10 @@ int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_v
                                 const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_bearing_edges(set, pose_vertex, point_vertex, meas, info); });
 }
+int g2ohip_pg_set_sensor_calib_edges(g2ohip_solver* s, int set_ij, int set_il, int set_jl, const int32_t* vi, const int32_t* vj,
+                                     const int32_t* vl, const double* meas, const double* info) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_sensor_calib_edges(set_ij, set_il, set_jl, vi, vj, vl, meas, info); });
+}
 int g2ohip_pg_set_cam_edges(g2ohip_solver* s, int set, int type, const int32_t* vi, const int32_t* vj, const double* meas,
                             const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_cam_edges(set, type, vi, vj, meas, info); });

@@ -79,8 +79,12 @@ def read_g2o(path):
     A file with EDGE_BEARING_SE2_XY lines (id_pose id_point z info: EdgeSE2PointXYBearing::read,
     g2o/types/slam2d/edge_se2_pointxy_bearing.cpp:56-66) also gives br_vp / br_vl (pose-table and point-table index of every
     bearing), br_meas [m] and br_info [m] (bearing_problem turns them into a problem dict); a file without them gives none of
-    these keys."""
+    these keys.
+    A file with EDGE_SE2_CALIB lines (i j l x y theta + 6: EdgeSE2SensorCalib::read, g2o/types/sclam2d/edge_se2_sensor_calib.cpp; the
+    laser offset l is a plain VERTEX_SE2) also gives cal_vi / cal_vj / cal_vl (pose-table indices), cal_meas [m][3] and cal_info
+    [m][3][3] (calib_problem turns them into a problem dict); a file without them gives none of these keys."""
     from . import sim3 as S3
+    c_i, c_j, c_l, c_meas, c_info = [], [], [], [], []
     g_i, g_j, g_vals = [], [], []
     sim3_extras = []
     spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
@@ -116,6 +120,12 @@ def read_g2o(path):
                 o_info.append(_upper_to_full([float(x) for x in t[5 + nm:5 + nm + dd * (dd + 1) // 2]], dd))
             elif tag == "PARAMS_SE2OFFSET":
                 offsets2[int(t[1])] = np.asarray([float(x) for x in t[2:5]])
+            elif tag == "EDGE_SE2_CALIB":
+                c_i.append(int(t[1]))
+                c_j.append(int(t[2]))
+                c_l.append(int(t[3]))
+                c_meas.append([float(x) for x in t[4:7]])
+                c_info.append(_upper_to_full([float(x) for x in t[7:13]], 3))
             elif tag == "VERTEX_SE2":
                 kind = kind or "se2"
                 vid.append(int(t[1]))
@@ -304,6 +314,10 @@ def read_g2o(path):
         out.update(off_vi=np.asarray([lut[a] for a in o_i], np.int32), off_vj=np.asarray([lut[a] for a in o_j], np.int32),
                    off_from=np.asarray(o_from, np.int32), off_to=np.asarray(o_to, np.int32), off_meas=np.asarray(o_meas, np.float64),
                    off_info=np.asarray(o_info, np.float64), off_kind=o_kind, offsets=offsets)
+    if c_i:
+        out.update(cal_vi=np.asarray([lut[a] for a in c_i], np.int32), cal_vj=np.asarray([lut[a] for a in c_j], np.int32),
+                   cal_vl=np.asarray([lut[a] for a in c_l], np.int32), cal_meas=np.asarray(c_meas, np.float64).reshape(-1, 3),
+                   cal_info=np.asarray(c_info, np.float64).reshape(-1, 3, 3))
     return out
 
 
@@ -539,6 +553,43 @@ def offset_problem(rd, fixed=None):
                 opf=np.asarray([row[int(a)] for a in rd["off_from"]], np.int32), opt=np.asarray([row[int(a)] for a in rd["off_to"]], np.int32),
                 omeas=conv(rd["off_meas"]), oinfo=np.asarray(rd["off_info"], np.float64).reshape(-1, d * d),
                 offsets=conv(np.stack([params[int(p)] for p in param_ids])), param_ids=param_ids)
+
+
+def write_g2o_calib(path, prob, ids=None):
+    """make_calib_rig-style problem -> `.g2o` text: VERTEX_SE2 lines for every row of prob["poses"] (the laser offset is one of
+    them), a FIX line for the rows of hessian index -1, the odometry as EDGE_SE2 and the calibration edges as EDGE_SE2_CALIB
+    "i j l x y theta upper-triangle" (EdgeSE2SensorCalib::write).  %.17g: a read gives the written doubles back."""
+    X = np.asarray(prob["poses"], np.float64).reshape(-1, 3)
+    n = len(X)
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    upper = lambda M: fmt(M[i, j] for i in range(3) for j in range(i, 3))
+    with open(path, "w") as f:
+        for k in range(n):
+            f.write("VERTEX_SE2 %d %s\n" % (ids[k], fmt(X[k])))
+        fixed = [ids[k] for k in range(n) if prob["hidx"][k] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(int(i)) for i in fixed))
+        Z, om = np.asarray(prob["Z"], np.float64).reshape(-1, 3), np.asarray(prob["omega"], np.float64).reshape(-1, 3, 3)
+        for e in range(len(Z)):
+            f.write("EDGE_SE2 %d %d %s %s\n" % (ids[prob["vi"][e]], ids[prob["vj"][e]], fmt(Z[e]), upper(om[e])))
+        Zc, oc = np.asarray(prob["cmeas"], np.float64).reshape(-1, 3), np.asarray(prob["cinfo"], np.float64).reshape(-1, 3, 3)
+        for e in range(len(Zc)):
+            f.write("EDGE_SE2_CALIB %d %d %d %s %s\n" % (ids[prob["ci"][e]], ids[prob["cj"][e]], ids[prob["cl"][e]], fmt(Zc[e]), upper(oc[e])))
+
+
+def calib_problem(rd, fixed=None):
+    """read_g2o result of a VERTEX_SE2 file with EDGE_SE2_CALIB lines -> the problem dict of synthetic.make_calib_rig (what
+    lm.setup_device_pose_graph(1, ..., calib_edges=dict(vi=ci, vj=cj, vl=cl, meas=cmeas, info=cinfo)) takes).  fixed: indices into
+    the pose table (default: the file's FIX lines; a file without any gets pose 0 fixed as the gauge)."""
+    if "cal_vi" not in rd or rd.get("kind") != "se2":
+        raise ValueError("calib_problem: not a VERTEX_SE2 file with EDGE_SE2_CALIB lines")
+    n = len(rd["estimates"])
+    fixed = (rd["fixed"] or [0]) if fixed is None else fixed
+    hidx, nP = hessian_index(n, fixed)
+    return dict(kind="se2", n=n, nP=nP, poses=np.asarray(rd["estimates"], np.float64).reshape(-1, 3), hidx=hidx, vi=rd["vi"], vj=rd["vj"],
+                Z=np.asarray(rd["meas"], np.float64).reshape(-1, 3), omega=np.asarray(rd["info"], np.float64).reshape(-1, 9),
+                ci=rd["cal_vi"], cj=rd["cal_vj"], cl=rd["cal_vl"], cmeas=rd["cal_meas"], cinfo=rd["cal_info"].reshape(-1, 9))
 
 
 def hessian_index(n_vertices, fixed):

@@ -375,7 +375,7 @@ PG_POSE_DIM = {1: 3, 2: 6, 10: 7}       # EdgeSE2, EdgeSE3, EdgeSim3 (g2ohip_pg_
 
 
 def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim=None, device=0, priors=None,
-                            fix_scale=False, options=None, offset_edges=None):
+                            fix_scale=False, options=None, offset_edges=None, calib_edges=None, huber_delta=0.0):
     """HipBlockSolver for a pose graph with estimates, errors and Jacobians on the device.
     edge_type 1: EdgeSE2 (estimates / measurements (x, y, theta), information [n][9]);
     edge_type 2: EdgeSE3 (isometries [12] = R column-major | t, information [n][36]).
@@ -387,7 +387,11 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     (edge_type 1), 9 = EdgeSE3Prior with its ParameterSE3Offset or None (edge_type 2); solver.prior_set = their set id.
     offset_edges: (type, vi, vj, pfrom, pto, meas, info, offsets) -- pose-pose edges between sensor frames, type 18 =
     EdgeSE2Offset (edge_type 1), 19 = EdgeSE3Offset (edge_type 2), pfrom / pto rows of the offsets table (g2ohip_pg_set_offset_edges);
-    solver.offset_set = their set id."""
+    solver.offset_set = their set id.
+    calib_edges: dict(vi, vj, vl, meas, info) -- three-vertex EdgeSE2SensorCalib scan-match edges (edge_type 1 only): vi / vj the
+    two poses, vl the laser offset, all rows of `estimates`; meas [n][3], info [n][9] or None (identity).  The three binary sets
+    (i, j), (i, l), (j, l) are added with their parts and bound as one group (g2ohip_pg_set_sensor_calib_edges);
+    solver.calib_sets = their ids; huber_delta > 0 puts a Huber kernel on all three."""
     import numpy as np
     from . import capi
     d = PG_POSE_DIM[edge_type]
@@ -402,6 +406,13 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     if offset_edges is not None:
         otype, oi, oj, opf, opt, omeas, oinfo, otable = offset_edges
         ko = s.addEdgeSet(d, hidx[np.asarray(oi, np.int64)], hidx[np.asarray(oj, np.int64)])
+    if calib_edges is not None:
+        ci, cj, cl = (np.asarray(calib_edges[key], np.int64) for key in ("vi", "vj", "vl"))
+        parts = (0, capi.PART_NO_VERTEX0 | capi.PART_NO_VERTEX1 | capi.PART_NO_CHI2, capi.PART_NO_VERTEX0 | capi.PART_NO_CHI2)
+        kc = []
+        for (a, b), pt in zip(((ci, cj), (ci, cl), (cj, cl)), parts):
+            kc.append(s.addEdgeSet(3, hidx[a], hidx[b]))
+            s.setEdgeSetParts(kc[-1], pt)
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
     if edge_type == 10:
@@ -413,6 +424,11 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
         s.prior_set = kq
     if offset_edges is not None:
         s.pgSetOffsetEdges(ko, otype, oi, oj, opf, opt, omeas, oinfo, otable)
+    if calib_edges is not None:
+        s.pgSetSensorCalibEdges(*kc, ci, cj, cl, calib_edges["meas"], calib_edges.get("info"))
+        if huber_delta > 0:
+            for kk in kc:
+                s.setRobustKernel(kk, capi.KERNEL_HUBER, huber_delta)
     return s, DevicePoseGraph(s)
 
 

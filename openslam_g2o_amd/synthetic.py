@@ -1063,3 +1063,61 @@ def make_bearing_slam(n_poses, n_landmarks, with_xy=False, seed=42, noise=0.02, 
                    pt_hidx=pt_hidx, vp=np.zeros(0, np.int32), vl=np.zeros(0, np.int32), zl=np.zeros((0, 2)), omega_l=np.zeros((0, 4)), M=0)
     out.update(bp=bp, bl=bl, zb=zb, omega_b=np.full(m, 1.0 / noise ** 2), B=m)
     return out
+
+
+def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.1, 0.03), offset=(0.3, 0.1, 0.2), fix_offset=False,
+                   wrap_every=0, pairs=None):
+    """Simultaneous calibration, localisation and mapping in 2-D (what g2o/examples/calibration_odom_laser optimises): n_poses
+    robot poses on a trajectory that keeps turning (so that the laser's mounting offset is observable), EdgeSE2 odometry between
+    consecutive poses, and three-vertex EdgeSE2SensorCalib scan-match edges (x1, x2, L) between consecutive poses and at `loops`
+    loop closures.  The laser offset L is an ordinary VertexSE2: row n_poses of the ONE pose table [n_poses + 1][3], so every
+    calibration edge names the same row `offset_row` as its third vertex.  pairs [m][2]: the pose pairs of the calibration
+    edges instead of the built-in consecutive + loop-closure ones.
+    Odometry = X_k^-1 X_{k+1}, scan match = (X_i L)^-1 (X_j L) of the true values, each times a motion of noise[0] * N(0, 1) in t and
+    noise[1] * N(0, 1) in theta; information diag(1 / noise^2).  Initial poses: the true ones times a motion of perturb[0] /
+    perturb[1]; pose 0 is fixed at its true pose.  The true offset is `offset`, its initial guess the identity; fix_offset=True
+    holds L fixed at the truth (hessian index -1: plain scan-match SLAM through the same edges).  wrap_every = w > 0: every w-th
+    calibration edge measures an angle off by pi -/+ 1e-3 (alternating), so that its angle error lands just inside +pi or just
+    inside -pi: gross outliers on both sides of the wrap (for a robust kernel).  Deterministic from seed.
+    Returns kind ("se2"), n (rows of the pose table), n_poses, offset_row, nP, poses, poses_true, hidx, vi, vj, Z, omega
+    (odometry), ci, cj, cl, cmeas, cinfo (calibration edges), offset_true."""
+    if n_poses < 3 or loops < 0:
+        raise ValueError("make_calib_rig: n_poses >= 3, loops >= 0")
+    rng = CounterRng(seed + 1)
+    n = n_poses
+    s = np.arange(n, dtype=np.float64)
+    th = 0.35 * s + 0.3 * np.sin(0.5 * s)
+    step = 0.5 * np.stack([np.cos(th), np.sin(th)], axis=1)
+    X = np.concatenate([np.concatenate([np.zeros((1, 2)), np.cumsum(step[:-1], axis=0)]), th[:, None]], axis=1)
+    X[:, 2] = (X[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
+    Lt = np.asarray(offset, np.float64).reshape(1, 3)
+    vi, vj = np.arange(n - 1, dtype=np.int32), np.arange(1, n, dtype=np.int32)
+    if pairs is None:
+        e = np.arange(loops)
+        li = (5 * e) % (n - 2)
+        lj = li + 2 + (3 * e) % (n - li - 2)
+        ci, cj = np.concatenate([vi, li]).astype(np.int32), np.concatenate([vj, lj]).astype(np.int32)
+    else:
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        ci, cj = pairs[:, 0].copy(), pairs[:, 1].copy()
+    m = len(ci)
+
+    def motion(stream, count, scale):
+        return np.stack([scale[0] * rng.normal(stream, count), scale[0] * rng.normal(stream + 1, count), scale[1] * rng.normal(stream + 3, count)], axis=1)
+
+    Z0 = _se2_mul(_se2_mul(_se2_inv(X[vi]), X[vj]), motion(10, n - 1, noise))
+    Lm = np.repeat(Lt, m, axis=0)
+    Zc = _se2_mul(_se2_mul(_se2_inv(_se2_mul(X[ci], Lm)), _se2_mul(X[cj], Lm)), motion(20, m, noise))
+    if wrap_every > 0:
+        k = np.arange(0, m, wrap_every)
+        Zc[k, 2] += np.pi + np.where((k // wrap_every) % 2 == 0, -1e-3, 1e-3)
+        Zc[:, 2] = (Zc[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
+    dX = motion(30, n, perturb)
+    dX[0] = 0.0
+    Xe = _se2_mul(X, dX)
+    poses = np.concatenate([Xe, Lt if fix_offset else np.zeros((1, 3))])
+    hidx = np.concatenate([np.arange(n, dtype=np.int32) - 1, [-1 if fix_offset else n - 1]]).astype(np.int32)
+    w = np.diag([1.0 / noise[0] ** 2] * 2 + [1.0 / noise[1] ** 2])
+    return dict(kind="se2", n=n + 1, n_poses=n, offset_row=n, nP=n - 1 + (0 if fix_offset else 1), poses=poses,
+                poses_true=np.concatenate([X, Lt]), hidx=hidx, vi=vi, vj=vj, Z=Z0, omega=np.tile(w.reshape(1, 9), (n - 1, 1)), ci=ci, cj=cj,
+                cl=np.full(m, n, np.int32), cmeas=Zc, cinfo=np.tile(w.reshape(1, 9), (m, 1)), offset_true=Lt[0].copy())
