@@ -843,11 +843,63 @@ int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_v
  * g2ohip_pg_set_* entries refuse its set ids and g2ohip_pg_set_edges refuses pose types other than 1.
  * g2ohip_pg_set_estimates with changed tables validates the group again; g2ohip_clear_edge_sets drops the binding, and so does a
  * g2ohip_update_structure that grows one of the three sets or the pose set (bind again after growth).
- * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: EdgeSE2OdomDifferentialCalib and
- * VertexOdomDifferentialParams (a vertex with a different oplus in the SE2 table: a change of its own), more than one calibration
- * group per handle, sharded solves, the g2o plugin adapter. */
+ * The kernel is timed under the "pg_landmark_linearize" slot.  EdgeSE2OdomDifferentialCalib and VertexOdomDifferentialParams, the
+ * other half of that example's graph: g2ohip_pg_set_odom_calib_edges below, in a slot of its own beside this one.  Not covered:
+ * more than one calibration group of the same kind per handle, sharded solves, the g2o plugin adapter. */
 int g2ohip_pg_set_sensor_calib_edges(g2ohip_solver* s, int set_ij, int set_il, int set_jl, const int32_t* vi, const int32_t* vj,
                                      const int32_t* vl, const double* meas, const double* info);
+/* ---- ... odometry self-calibration (sclam2d): wheel-velocity constraints that also estimate the differential drive --------------
+ * ONE group of EdgeSE2OdomDifferentialCalib (type 22; tag EDGE_SE2_ODOM_DIFFERENTIAL_CALIB,
+ * g2o/types/sclam2d/edge_se2_odom_differential_calib.h:45-63 computeError, edge_se2_odom_differential_calib.cpp:39-61 read /
+ * write, OdomConvert::convertToMotion g2o/types/sclam2d/odometry_measurement.cpp:95-117): a THREE-vertex edge over two VertexSE2
+ * poses x1, x2 and a VertexOdomDifferentialParams p = (k_l, k_r, b) -- all three are rows of the one pose table of
+ * g2ohip_pg_set_estimates.  Beside a type-1 pose set only (which may hold ZERO edges: the graph of
+ * g2o/examples/calibration_odom_laser has no EdgeSE2), in the "odometry-calibration slot": independent of the landmark, prior,
+ * offset, bearing and type-21 calibration slots -- both calibration groups may be bound at once -- a later call replaces the binding.
+ *   vl' = vl p[0]   vr' = vr p[1]   D = vr' - vl'   S = vl' + vr'   b = p[2]
+ *   |D| > 1e-7:  Rc = b 0.5 (S / D)   th = (D / b) dt   K = SE2(Rc sin th, Rc - Rc cos th, th)
+ *   otherwise:   K = SE2(0.5 S dt, 0, 0)
+ *   e = toVector(K^-1 * x1^-1 * x2)                        (error dimension 3; b = 0 gives non-finite values, as in the reference)
+ * ADDITIVE ROWS.  VertexOdomDifferentialParams::oplusImpl is estimate += v with no angle wrap
+ * (vertex_odom_differential_params.h:43-46).  While the group is bound every row named by vp is an additive row of the table:
+ * g2ohip_pg_update adds all three components of its step; every other row moves as VertexSE2::oplusImpl.  The binding is the
+ * declaration.  A row is read one way only: the call refuses (G2OHIP_ERR_ARG) a vp row that is also a vi / vj of this group or a
+ * vertex of any set bound on the handle (pose set, prior, offset, bearing / landmark pose side, all three columns of the type-21
+ * group), and while the group is bound the other g2ohip_pg_set_* entries refuse an index that names an additive row.  Once the
+ * group is released the rows are ordinary VertexSE2 rows again.  push / pop / discard_top / get_estimates copy rows.
+ * DELIBERATE DEVIATION: the reference defines no linearizeOplus for this edge and differentiates numerically
+ * (base_multi_edge.hpp:63-116, central difference, delta = 1e-9); the device writes the exact derivative OF THE BRANCH TAKEN, as
+ * for types 7, 18, 20 and 21: with Q = R(-(th + th1)), J = [0 -1; 1 0], e_t the translational error
+ *   d e_t / d t1 = -Q     d e_t / d th1 = -J Q (t2 - t1)     d e_th / d th1 = -1
+ *   d e_t / d t2 =  Q     d e_t / d th2 = 0                  d e_th / d th2 =  1
+ *   d e_t / d q  = -R(-th) (dx/dq, dy/dq) - J e_t dth/dq     d e_th / d q   = -dth/dq            for q of (k_l, k_r, b)
+ *   turning:   dRc/dk_l = b vl vr' / D^2   dRc/dk_r = -b vr vl' / D^2   dRc/db = Rc / b
+ *              dth/dk_l = -vl dt / b       dth/dk_r = vr dt / b         dth/db = -th / b
+ *              dx/dq = sin th dRc/dq + Rc cos th dth/dq     dy/dq = (1 - cos th) dRc/dq + Rc sin th dth/dq
+ *   straight:  dx/dk_l = 0.5 vl dt   dx/dk_r = 0.5 vr dt   every other entry 0 (the column of b is zero, as the reference's
+ *              difference gives it while both probes stay inside the branch)
+ * Within 1e-9 max(|vl|, |vr|) of |D| = 1e-7 the reference's probes fall on different branches and its Jacobian is meaningless; the
+ * device's is that of the branch the estimate is on.  The Jacobian block of a fixed vertex (hessian index < 0) is zeros.
+ * The edge is the three binary sets of g2ohip_set_edge_set_parts, error_dim 3, equal edge counts, pose dimension 3:
+ *   set_ij  (i, j)  parts 0
+ *   set_ip  (i, p)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_VERTEX1 | G2OHIP_PART_NO_CHI2
+ *   set_jp  (j, p)  parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_CHI2
+ * bound and released as one group, sharing Jacobians, information and errors on the device.  vi / vj / vp index the pose table
+ * (vp is per edge: several parameter vertices, one per robot, need nothing more); meas [n][3] = (vl, vr, dt); info [n][3x3], NULL =
+ * identity.  Robust kernels: the same kernel on all three sets.  Each parameter vertex is a neighbour of every one of its edges: a
+ * dense block row, as the laser offset's.
+ * G2OHIP_ERR_STATE: a call before g2ohip_build_structure or before g2ohip_pg_set_edges, a set that carries per-edge robust
+ * kernels.  G2OHIP_ERR_ARG: a bad or repeated set id, a pose set of a type other than 1, wrong dimensions, parts or edge counts, a
+ * unary set, a set bound in another slot (the type-21 group's included; that group's entry refuses this one's), null vi / vj / vp /
+ * meas, a non-finite value, an index outside the pose table, a hessian index that differs from the sets' own, a vertex named twice
+ * in an edge, a row read both ways (above) -- validated before anything is committed: a rejected call leaves the previous binding
+ * usable.  g2ohip_pg_set_estimates with changed tables validates the group again; g2ohip_clear_edge_sets drops the binding, and so
+ * does a g2ohip_update_structure that grows one of the three sets or the pose set.  Captured launch sequences (use_graph) are
+ * dropped at binding and at release.  The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: sharded solves,
+ * the g2o plugin adapter. */
+int g2ohip_pg_set_odom_calib_edges(g2ohip_solver* s, int set_ij, int set_ip, int set_jp, const int32_t* vi, const int32_t* vj,
+                                   const int32_t* vp, const double* meas /* [n][3] = vl, vr, dt */,
+                                   const double* info /* [n][3x3], NULL = identity */);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -65,7 +65,7 @@ EXPORTS = [
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
     "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges", "g2ohip_pg_set_bearing_edges",
-    "g2ohip_pg_set_sensor_calib_edges",
+    "g2ohip_pg_set_sensor_calib_edges", "g2ohip_pg_set_odom_calib_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -179,6 +179,7 @@ def load():
     L.g2ohip_pg_set_offset_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_bearing_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_sensor_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_odom_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -554,6 +555,7 @@ class HipBlockSolver:
         self.offset_set = None
         self.bearing_set = None
         self.calib_sets = None
+        self.odom_calib_sets = None
         self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
@@ -577,9 +579,12 @@ class HipBlockSolver:
                 self.offset_set = None
                 self.bearing_set = None
                 self.calib_sets = None
+                self.odom_calib_sets = None
                 self._pg_owner_sets = set()
             if self.calib_sets is not None and set_id in self.calib_sets:   # (a calibration group goes as one)
                 self.calib_sets = None
+            if self.odom_calib_sets is not None and set_id in self.odom_calib_sets:
+                self.odom_calib_sets = None
         return True
 
     def setProfiling(self, on):
@@ -962,6 +967,27 @@ class HipBlockSolver:
         _check(self.L.g2ohip_pg_set_sensor_calib_edges(self.h, set_ij, set_il, set_jl, _ip(vi), _ip(vj), _ip(vl), _dp(meas),
                                                        None if info is None else _dp(info)), "pgSetSensorCalibEdges")
         self.calib_sets = (set_ij, set_il, set_jl)
+
+    odom_calib_sets = None   # set ids (i-j, i-p, j-p) of the bound EdgeSE2OdomDifferentialCalib group (pgSetOdomCalibEdges)
+
+    def pgSetOdomCalibEdges(self, set_ij, set_ip, set_jp, vi, vj, vp, meas, info=None):
+        """Odometry self-calibration (EdgeSE2OdomDifferentialCalib, type 22) beside an EdgeSE2 pose set: a three-vertex edge over
+        two poses vi / vj and the VertexOdomDifferentialParams vp = (k_l, k_r, b), all rows of the table of pgSetEstimates; meas
+        [n][3] = (vl, vr, dt), info [n][3x3] or None (identity).  The three sets are binary ones with error_dim 3 over (i, j),
+        (i, p), (j, p) with setEdgeSetParts 0, PART_NO_VERTEX0 | PART_NO_VERTEX1 | PART_NO_CHI2 and PART_NO_VERTEX0 |
+        PART_NO_CHI2 before buildStructure.  After pgSetEdges.  While bound, the rows of vp move by plain addition in pgUpdate and
+        no other binding may name them.  A robust kernel goes on all three sets."""
+        vi, vj, vp, meas = _i32(vi), _i32(vj), _i32(vp), _f64(meas)
+        n = self._set_sizes[set_ij]
+        if len(vi) != n or len(vj) != n or len(vp) != n or meas.size != n * 3:
+            raise ValueError("pgSetOdomCalibEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_ij, n))
+        if info is not None:
+            info = _f64(info)
+            if info.size != n * 9:
+                raise ValueError("pgSetOdomCalibEdges: info is [n][3x3]")
+        _check(self.L.g2ohip_pg_set_odom_calib_edges(self.h, set_ij, set_ip, set_jp, _ip(vi), _ip(vj), _ip(vp), _dp(meas),
+                                                     None if info is None else _dp(info)), "pgSetOdomCalibEdges")
+        self.odom_calib_sets = (set_ij, set_ip, set_jp)
 
     cam_set = scale_set = None     # set ids of the bound EdgeSBACam / EdgeSBAScale sets (pgSetCamEdges)
 

@@ -168,6 +168,13 @@ class HipBlockSolver {
                              const double* info) {
     return ok(g2ohip_pg_set_sensor_calib_edges(h_, setIJ, setIL, setJL, vi, vj, vl, meas, info), "pgSetSensorCalibEdges");
   }
+  // Odometry self-calibration (g2ohip_pg_set_odom_calib_edges): three-vertex EdgeSE2OdomDifferentialCalib edges beside an EdgeSE2
+  // set, as the three binary sets (i, j), (i, p), (j, p) with their parts; vi / vj / vp index the pose table (vp = the
+  // VertexOdomDifferentialParams row, additive while bound), meas [n][3] = (vl, vr, dt), info [n][3x3] or null (identity)
+  bool pgSetOdomCalibEdges(int setIJ, int setIP, int setJP, const int32_t* vi, const int32_t* vj, const int32_t* vp, const double* meas,
+                           const double* info) {
+    return ok(g2ohip_pg_set_odom_calib_edges(h_, setIJ, setIP, setJP, vi, vj, vp, meas, info), "pgSetOdomCalibEdges");
+  }
   double* x() { return x_.data(); }
   const double* b() const { return b_.data(); }
   size_t vectorSize() const { return x_.size(); }

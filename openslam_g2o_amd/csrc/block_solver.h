@@ -13,7 +13,11 @@
 // atomics, same summation order as the reference's serial loops.
 #pragma once
 #include <cstring>
+#include <initializer_list>
 #include <memory>
+#include <string>
+#include <utility>
+#include <vector>
 
 #include "common.h"
 #include "comm.h"
@@ -108,6 +112,8 @@ class BlockSolver {
   void pg_set_bearing_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info);
   void pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, const int* vi, const int* vj, const int* vl, const double* meas,
                                  const double* info);
+  void pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, const int* vi, const int* vj, const int* vp, const double* meas,
+                               const double* info);
   void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -377,6 +383,14 @@ class BlockSolver {
   void pg_validate_calib(const int* vi, const int* vj, const int* vl, size_t n, const int* hidx, int nv) const;
   void pg_cal_alias();
   void pg_cal_release();
+  void pg_validate_odom_calib(const int* vi, const int* vj, const int* vp, size_t n, const int* hidx, int nv) const;
+  void pg_od_alias();
+  void pg_od_release();
+  void pg_od_build_mask();
+  // a row of the SE2 pose table is read either as a VertexSE2 or as an additive row (VertexOdomDifferentialParams), never both:
+  // throws ArgFailure where one of `lists` (index arrays read as VertexSE2) names a row of `additive` (sorted)
+  static void pg_refuse_additive(const std::string& who, const std::vector<int>& additive,
+                                 std::initializer_list<std::pair<const int*, size_t>> lists);
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                               const double* info, const double* offset, const double* kcam, int n_cams = 0);
   // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
@@ -544,6 +558,16 @@ class BlockSolver {
     std::vector<int> h_cal_vi, h_cal_vj, h_cal_vl;   // host copies: index validation (pg_validate)
     DevBuf<double> cal_meas;
     bool in_cal(int set) const { return set >= 0 && (set == cal_ij || set == cal_il || set == cal_jl); }
+    // ONE group of EdgeSE2OdomDifferentialCalib (type 22, error 3, THREE vertices: pose, pose, VertexOdomDifferentialParams -- all
+    // rows of `poses`) beside type 1, in the odometry-calibration slot, independent of the type-21 slot: the binary sets od_ij (i, j),
+    // od_ip (i, p), od_jp (j, p) share buffers as the type-21 group's do (pg_od_alias).  od_vi / od_vj / od_vp index `poses`,
+    // od_meas [n][3] = (vl, vr, dt) (pg_odom_calib.inc).  While the group is bound the rows named by od_vp are ADDITIVE rows:
+    // od_rows lists them (sorted, unique), od_mask [poses.n] marks them on the device for pg_se2_update_additive_kernel.
+    int od_ij = -1, od_ip = -1, od_jp = -1;
+    DevBuf<int> od_vi, od_vj, od_vp, od_mask;
+    std::vector<int> h_od_vi, h_od_vj, h_od_vp, od_rows;
+    DevBuf<double> od_meas;
+    bool in_od(int set) const { return set >= 0 && (set == od_ij || set == od_ip || set == od_jp); }
     // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
     // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
     // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.

@@ -2079,6 +2079,20 @@ __global__ void __launch_bounds__(kThreads) pg_se2_update_kernel(int nv, double*
   p[1] += u[1];
   p[2] = pg_normalize_theta(p[2] + u[2]);
 }
+// the same table while an EdgeSE2OdomDifferentialCalib group is bound (pg_set_odom_calib_edges): the rows its vp names hold
+// VertexOdomDifferentialParams (k_l, k_r, b), whose oplusImpl is estimate += v with NO angle wrap
+// (vertex_odom_differential_params.h:43-46); additive[v] != 0 marks them.  Every other row moves as in pg_se2_update_kernel.
+__global__ void __launch_bounds__(kThreads) pg_se2_update_additive_kernel(int nv, double* __restrict__ poses, const int* __restrict__ hidx,
+                                                                        const int* __restrict__ additive, const double* __restrict__ x) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv || hidx[v] < 0) return;
+  const double* u = x + 3 * (size_t)hidx[v];
+  double* p = poses + 3 * (size_t)v;
+  p[0] += u[0];
+  p[1] += u[1];
+  const double t = p[2] + u[2];
+  p[2] = additive[v] ? t : pg_normalize_theta(t);
+}
 
 #define PG_R(T, a, b) (T)[(a) + 3 * (b)]
 __device__ __forceinline__ void pg_iso_mul(const double* A, const double* B, double* C) {
@@ -2315,6 +2329,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_offset.inc"
 #include "pg_bearing.inc"
 #include "pg_calib.inc"
+#include "pg_odom_calib.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
@@ -2580,8 +2595,10 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     // (pg_set_offset_edges again) or a grown bearing set (pg_set_bearing_edges again); an EdgeSE2SensorCalib group goes as one
     // when one of its three sets grows (pg_set_sensor_calib_edges again), its sets keep no pointer into each other's buffers
     if (pg_.in_cal(set)) pg_cal_release();
+    if (pg_.in_od(set)) pg_od_release();   // (an EdgeSE2OdomDifferentialCalib group likewise: pg_set_odom_calib_edges again)
     if (set == pg_.set || set == pg_.lm_set) {
       pg_cal_release();
+      pg_od_release();
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
       pg_.fix_scale = fix_scale;
@@ -3301,7 +3318,8 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
   const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
-                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set || pg_.in_cal(set);
+                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set || pg_.in_cal(set) ||
+                             pg_.in_od(set);
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5996,11 +6014,15 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (pg_.cal_ij >= 0 && type != 1)
     throw ArgFailure("pg_set_edges: an EdgeSE2SensorCalib group (21) is bound: it stands beside an EdgeSE2 pose set (1) only");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.od_ij >= 0 && type != 1)
+    throw ArgFailure("pg_set_edges: an EdgeSE2OdomDifferentialCalib group (22) is bound: it stands beside an EdgeSE2 pose set (1) only");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
   // type-12 set is always empty: it is the anchor of the camera table that the landmark slot needs)
   if ((n > 0 || (type != 10 && type != 12)) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
+  pg_refuse_additive("pg_set_edges", pg_.od_rows, {{vi, n}, {vj, n}});
   if (type == 12) {
     // beside a VertexCam table stands an EdgeProjectP2MC (13) or EdgeProjectP2SC (14) landmark set or nothing
     if ((pg_.lm_set >= 0 && !pg_cam_landmark(pg_.lm_type)) || pg_.pr_set >= 0)
@@ -6076,12 +6098,14 @@ void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx)
       pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), hidx, nv, pg_.points.h_hidx.data(),
                             pg_.points.n);
     if (pg_.cal_ij >= 0) pg_validate_calib(pg_.h_cal_vi.data(), pg_.h_cal_vj.data(), pg_.h_cal_vl.data(), pg_.h_cal_vi.size(), hidx, nv);
+    if (pg_.od_ij >= 0) pg_validate_odom_calib(pg_.h_od_vi.data(), pg_.h_od_vj.data(), pg_.h_od_vp.data(), pg_.h_od_vi.size(), hidx, nv);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
   pg_.has_backup = false;
   if (same) pg_.poses.set_values(poses, st_);
   else pg_.poses.commit(nv, ps, poses, hidx, st_);
+  if (!same && pg_.od_ij >= 0) pg_od_build_mask();   // (the mask of additive rows has one entry per row of the table)
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
@@ -6181,6 +6205,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (set == pg_.off_set) throw ArgFailure(w + ": the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure(w + ": the set is bound as the bearing set");
   if (pg_.in_cal(set)) throw ArgFailure(w + ": the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure(w + ": the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -6192,6 +6217,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
+  pg_refuse_additive(w, pg_.od_rows, {{pose_vertex, n}});
   if (table)   // (the kernels index the intrinsics by pose_vertex: in range also while no pose table is bound)
     for (size_t k = 0; k < n; ++k)
       if (pose_vertex[k] >= n_cams) throw ArgFailure(w + ": pose index of landmark edge " + std::to_string(k) + " outside the intrinsics table");
@@ -6240,6 +6266,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   if (set == pg_.off_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the bearing set");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_prior_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_prior_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -6249,6 +6276,7 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const size_t n = (size_t)es.n;
   pg_validate_priors(es, pose_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_refuse_additive("pg_set_prior_edges", pg_.od_rows, {{pose_vertex, n}});
   pg_.pr_set = set;
   pg_.pr_type = type;
   pg_.h_vq.assign(pose_vertex, pose_vertex + n);
@@ -6297,6 +6325,7 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   if (set == pg_.off_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the bearing set");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_gicp_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_gicp_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6358,6 +6387,7 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the bearing set");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_offset_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_offset_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   const int d = type == 18 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d || p_ != d)
@@ -6377,6 +6407,7 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
       if (!std::isfinite(info[(size_t)(d * d) * k + i])) throw ArgFailure("pg_set_offset_edges: non-finite information in edge " + std::to_string(k));
   }
   pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_refuse_additive("pg_set_offset_edges", pg_.od_rows, {{vi, n}, {vj, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   if (pg_.off_set >= 0 && pg_.off_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
     EdgeSet& old = *sets_[pg_.off_set];
@@ -6423,6 +6454,7 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
   if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
   if (set == pg_.off_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the sensor-offset set");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_bearing_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_bearing_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   // (a set of zero edges has no vertex classes: build_structure gives it pose dimensions on both sides)
   if (es.unary || es.d != 1 || p_ != 3 || l_ != 2 || (es.n > 0 && (es.dim0 != 3 || es.dim1 != 2)))
@@ -6434,6 +6466,7 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
     if (!std::isfinite(info[k])) throw ArgFailure("pg_set_bearing_edges: non-finite information in edge " + std::to_string(k));
   }
   pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
+  pg_refuse_additive("pg_set_bearing_edges", pg_.od_rows, {{pose_vertex, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   if (pg_.br_set >= 0 && pg_.br_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
     EdgeSet& old = *sets_[pg_.br_set];
@@ -6482,7 +6515,7 @@ void BlockSolver::pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, 
   if (pg_.type != 1) throw ArgFailure("pg_set_sensor_calib_edges: EdgeSE2SensorCalib (21) goes with an EdgeSE2 pose set (1)");
   for (int id : ids)
     if (id == pg_.set || id == pg_.lm_set || id == pg_.pr_set || id == pg_.gicp_set || id == pg_.cam_set || id == pg_.scale_set ||
-        id == pg_.off_set || id == pg_.br_set)
+        id == pg_.off_set || id == pg_.br_set || pg_.in_od(id))
       throw ArgFailure("pg_set_sensor_calib_edges: set " + std::to_string(id) + " is bound in another slot");
   EdgeSet &es = *sets_[set_ij], &ea = *sets_[set_il], &ec = *sets_[set_jl];
   for (const EdgeSet* e : {&es, &ea, &ec})
@@ -6508,6 +6541,7 @@ void BlockSolver::pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, 
   pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   pg_validate(ea, vi, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   pg_validate(ec, vj, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_refuse_additive("pg_set_sensor_calib_edges", pg_.od_rows, {{vi, n}, {vj, n}, {vl, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   // commit: the previous group leaves the slot, with the data the device wrote for it
   std::vector<double> identity;
@@ -6587,6 +6621,167 @@ void BlockSolver::pg_validate_calib(const int* vi, const int* vj, const int* vl,
   pg_validate(*sets_[pg_.cal_jl], vj, vl, n, hidx, nv);
 }
 
+// ---- ... odometry self-calibration: EdgeSE2OdomDifferentialCalib (type 22), a THREE-vertex edge over two poses and a
+// VertexOdomDifferentialParams (k_l, k_r, b), all rows of the one pose table, beside an EdgeSE2 set (pg_odom_calib.inc).  The
+// contract of pg_set_sensor_calib_edges, clause for clause, in a slot of its own (both groups may be bound at once: the graph of
+// g2o/examples/calibration_odom_laser):
+//   set_ij  (i, j)  parts 0                                  terms of i and j, H(i, j), chi2
+//   set_ip  (i, p)  parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  H(i, p)
+//   set_jp  (j, p)  parts NO_VERTEX0 | NO_CHI2               terms of p, H(j, p)
+// and one clause more: while the group is bound the rows its vp names are ADDITIVE rows of the table (pg_update adds all three
+// components, no angle wrap), so no other binding may read them as VertexSE2 -- refused here against everything bound, and in the
+// other pg_set_* entries against od_rows (pg_refuse_additive).  Validate, then commit.
+void BlockSolver::pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, const int* vi, const int* vj, const int* vp,
+                                          const double* meas, const double* info) {
+  invalidate_graphs();
+  require_structure();
+  if (pg_.set < 0 || pg_.type == 0)
+    throw StateFailure("pg_set_odom_calib_edges: call pg_set_edges first (the pose-pose set the calibration group stands beside)");
+  const int ids[3] = {set_ij, set_ip, set_jp};
+  for (int id : ids)
+    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  if (set_ij == set_ip || set_ij == set_jp || set_ip == set_jp) throw ArgFailure("pg_set_odom_calib_edges: the three sets must differ");
+  if (pg_.type != 1) throw ArgFailure("pg_set_odom_calib_edges: EdgeSE2OdomDifferentialCalib (22) goes with an EdgeSE2 pose set (1)");
+  for (int id : ids)
+    if (id == pg_.set || id == pg_.lm_set || id == pg_.pr_set || id == pg_.gicp_set || id == pg_.cam_set || id == pg_.scale_set ||
+        id == pg_.off_set || id == pg_.br_set || pg_.in_cal(id))
+      throw ArgFailure("pg_set_odom_calib_edges: set " + std::to_string(id) + " is bound in another slot");
+  EdgeSet &es = *sets_[set_ij], &ea = *sets_[set_ip], &ec = *sets_[set_jp];
+  for (const EdgeSet* e : {&es, &ea, &ec})
+    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
+      throw ArgFailure("pg_set_odom_calib_edges: the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
+  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
+    throw ArgFailure("pg_set_odom_calib_edges: parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
+  if (ea.n != es.n || ec.n != es.n) throw ArgFailure("pg_set_odom_calib_edges: the three sets must hold the same number of edges");
+  if (!vi || !vj || !vp || !meas) throw ArgFailure("pg_set_odom_calib_edges: null array");
+  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
+    throw StateFailure("pg_set_odom_calib_edges: a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0 || vp[k] < 0) throw ArgFailure("pg_set_odom_calib_edges: negative vertex index in edge " + std::to_string(k));
+    if (vi[k] == vj[k] || vi[k] == vp[k] || vj[k] == vp[k])
+      throw ArgFailure("pg_set_odom_calib_edges: edge " + std::to_string(k) + " names one vertex twice");
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure("pg_set_odom_calib_edges: non-finite measurement in edge " + std::to_string(k));
+    if (info)
+      for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_odom_calib_edges: non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ea, vi, vp, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ec, vj, vp, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  // the rows of vp become additive rows: none of them may be a pose of this group or a vertex of anything bound on the handle
+  std::vector<int> rows(vp, vp + n);
+  std::sort(rows.begin(), rows.end());
+  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  const auto bound = [](bool on, const std::vector<int>& v) { return std::pair<const int*, size_t>(v.data(), on ? v.size() : 0); };
+  pg_refuse_additive("pg_set_odom_calib_edges", rows,
+                     {{vi, n}, {vj, n}, bound(true, pg_.h_vi), bound(true, pg_.h_vj), bound(pg_.lm_set >= 0, pg_.h_vp),
+                      bound(pg_.pr_set >= 0, pg_.h_vq), bound(pg_.off_set >= 0, pg_.h_oi), bound(pg_.off_set >= 0, pg_.h_oj),
+                      bound(pg_.br_set >= 0, pg_.h_bp), bound(pg_.cal_ij >= 0, pg_.h_cal_vi), bound(pg_.cal_ij >= 0, pg_.h_cal_vj),
+                      bound(pg_.cal_ij >= 0, pg_.h_cal_vl)});
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  // commit: the previous group leaves the slot, with the data the device wrote for it
+  std::vector<double> identity;
+  if (!info) {   // information().setIdentity()
+    identity.assign(n * 9, 0.0);
+    for (size_t k = 0; k < n; ++k) identity[9 * k] = identity[9 * k + 4] = identity[9 * k + 8] = 1.0;
+    info = identity.data();
+  }
+  pg_od_release();
+  pg_.od_ij = set_ij;
+  pg_.od_ip = set_ip;
+  pg_.od_jp = set_jp;
+  pg_.h_od_vi.assign(vi, vi + n);
+  pg_.h_od_vj.assign(vj, vj + n);
+  pg_.h_od_vp.assign(vp, vp + n);
+  pg_.od_rows = std::move(rows);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  pg_.od_vi.upload(vi, n, st_);
+  pg_.od_vj.upload(vj, n, st_);
+  pg_.od_vp.upload(vp, n, st_);
+  pg_.od_meas.upload(meas, n * 3, st_);
+  es.own_omega.upload(info, n * 9, st_);
+  es.own_J0.alloc(n * 9);
+  es.own_J1.alloc(n * 9);
+  es.own_err.alloc(n * 3);
+  ec.own_J1.alloc(n * 9);
+  pg_od_alias();
+  for (EdgeSet* e : {&es, &ea, &ec}) {
+    e->external = false;
+    e->has_data = false;   // becomes valid with the first pg_linearize
+    e->has_err = false;
+  }
+  pg_od_build_mask();
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));   // (the identity staging buffer is read by the upload)
+}
+
+// the ONE check of row kinds: an index of `lists` (arrays a binding reads as VertexSE2) that names a row of `additive` (sorted)
+void BlockSolver::pg_refuse_additive(const std::string& who, const std::vector<int>& additive,
+                                     std::initializer_list<std::pair<const int*, size_t>> lists) {
+  if (additive.empty()) return;
+  for (const auto& l : lists)
+    for (size_t k = 0; k < l.second; ++k)
+      if (std::binary_search(additive.begin(), additive.end(), l.first[k]))
+        throw ArgFailure(who + ": row " + std::to_string(l.first[k]) + " of the pose table (entry " + std::to_string(k) +
+                         ") is both a VertexSE2 and the parameter vertex of an EdgeSE2OdomDifferentialCalib group (an additive row)");
+}
+
+// the device mask of additive rows, one entry per row of the committed pose table (none yet: built by pg_set_estimates)
+void BlockSolver::pg_od_build_mask() {
+  if (pg_.poses.n <= 0) return;
+  std::vector<int> mask((size_t)pg_.poses.n, 0);
+  for (int r : pg_.od_rows)
+    if (r < pg_.poses.n) mask[(size_t)r] = 1;
+  pg_.od_mask.upload(mask, st_);   // (pageable host memory: staged before return; both callers synchronise the stream)
+}
+
+// the pointers of the three sets of an odometry-calibration group onto the buffers two of them own (as pg_cal_alias)
+void BlockSolver::pg_od_alias() {
+  EdgeSet &es = *sets_[pg_.od_ij], &ea = *sets_[pg_.od_ip], &ec = *sets_[pg_.od_jp];
+  const double *ji = es.own_J0.p, *jj = es.own_J1.p, *jp = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
+  const double* want[3][2] = {{ji, jj}, {ji, jp}, {jj, jp}};
+  EdgeSet* g[3] = {&es, &ea, &ec};
+  bool changed = false;
+  for (int i = 0; i < 3; ++i) {
+    EdgeSet& e = *g[i];
+    changed = changed || e.J0 != want[i][0] || e.J1 != want[i][1] || e.omega != om || e.err != er || e.external;
+    e.J0 = want[i][0];
+    e.J1 = want[i][1];
+    e.omega = om;
+    e.err = er;
+    e.external = false;
+  }
+  if (changed) drop_graph_segments();
+}
+
+// an odometry-calibration group leaves its slot: its sets keep no device-written data and no pointer into each other's buffers,
+// and the rows its vp named are ordinary VertexSE2 rows again (pg_update wraps their third component)
+void BlockSolver::pg_od_release() {
+  if (pg_.od_ij < 0) return;
+  for (int id : {pg_.od_ij, pg_.od_ip, pg_.od_jp}) {
+    if (id < 0 || id >= (int)sets_.size()) continue;
+    EdgeSet& e = *sets_[id];
+    e.has_data = e.has_err = false;
+    e.J0 = e.J1 = e.omega = e.err = nullptr;
+  }
+  pg_.od_ij = pg_.od_ip = pg_.od_jp = -1;
+  pg_.h_od_vi.clear();
+  pg_.h_od_vj.clear();
+  pg_.h_od_vp.clear();
+  pg_.od_rows.clear();
+  pg_.err_valid = pg_.jac_valid = false;
+  drop_graph_segments();
+}
+
+// the three sets of an odometry-calibration group against a pose table
+void BlockSolver::pg_validate_odom_calib(const int* vi, const int* vj, const int* vp, size_t n, const int* hidx, int nv) const {
+  pg_validate(*sets_[pg_.od_ij], vi, vj, n, hidx, nv);
+  pg_validate(*sets_[pg_.od_ip], vi, vp, n, hidx, nv);
+  pg_validate(*sets_[pg_.od_jp], vj, vp, n, hidx, nv);
+}
+
 // ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
 // own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
 // validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
@@ -6607,6 +6802,7 @@ void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* 
   if (set == pg_.off_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the sensor-offset set");
   if (set == pg_.br_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the bearing set");
   if (pg_.in_cal(set)) throw ArgFailure("pg_set_cam_edges: the set is bound in the EdgeSE2SensorCalib group");
+  if (pg_.in_od(set)) throw ArgFailure("pg_set_cam_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   if (set == (cam ? pg_.scale_set : pg_.cam_set))
     throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
   EdgeSet& es = *sets_[set];
@@ -6725,8 +6921,18 @@ void BlockSolver::pg_linearize(bool jacobians) {
         throw StateFailure("pg_linearize: an EdgeSE2SensorCalib edge set has grown since pg_set_sensor_calib_edges: call it again");
     pg_cal_alias();   // (before err_valid / jac_valid are read: a repaired pointer drops the captured launch sequences)
   }
+  EdgeSet* const eod[3] = {pg_.od_ij >= 0 ? sets_[pg_.od_ij].get() : nullptr, pg_.od_ij >= 0 ? sets_[pg_.od_ip].get() : nullptr,
+                           pg_.od_ij >= 0 ? sets_[pg_.od_jp].get() : nullptr};
+  if (eod[0]) {
+    for (EdgeSet* e : eod)
+      if ((int)pg_.h_od_vi.size() != e->n)
+        throw StateFailure("pg_linearize: an EdgeSE2OdomDifferentialCalib edge set has grown since pg_set_odom_calib_edges: call it again");
+    pg_od_alias();
+  }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
     for (EdgeSet* e : ecal)
+      if (jacobians && e) e->has_data = true;
+    for (EdgeSet* e : eod)
       if (jacobians && e) e->has_data = true;
     if (jacobians && eo) eo->has_data = true;
     if (jacobians && eb) eb->has_data = true;
@@ -6741,8 +6947,9 @@ void BlockSolver::pg_linearize(bool jacobians) {
   pg_.err_valid = true;
   if (jacobians) pg_.jac_valid = true;
   chi2_valid_ = false;
-  // (a type-2 set may hold zero edges -- a pure registration, all constraints in the GICP set -- and then launches nothing)
-  if (pg_.type == 1)
+  // (a type-2 set may hold zero edges -- a pure registration, all constraints in the GICP set -- and then launches nothing; so
+  // may a type-1 set: the graph of calibration_odom_laser has no EdgeSE2, all constraints in the two calibration groups)
+  if (pg_.type == 1 && es.n > 0)
     hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
                        pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
   else if (pg_.type == 2 && es.n > 0)
@@ -6762,7 +6969,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
   }
   const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
   const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0, off_launch = eo && eo->n > 0;
-  const bool br_launch = eb && eb->n > 0, cal_launch = ecal[0] && ecal[0]->n > 0;
+  const bool br_launch = eb && eb->n > 0, cal_launch = (ecal[0] && ecal[0]->n > 0) || (eod[0] && eod[0]->n > 0);
   const int jac = jacobians ? 1 : 0;
   if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
   if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
@@ -6858,13 +7065,22 @@ void BlockSolver::pg_linearize(bool jacobians) {
                          pg_.bl.p, pg_.br_meas.p, eb->own_J0.p, eb->own_J1.p, eb->own_err.p, jac);
     });
   }
-  if (cal_launch) {   // EdgeSE2SensorCalib -- pg_calib.inc
+  if (ecal[0] && ecal[0]->n > 0) {   // EdgeSE2SensorCalib -- pg_calib.inc
     const dim3 grid(grid_for(ecal[0]->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
       hipLaunchKernelGGL(pg_se2_calib_linearize_kernel<STAGED>, grid, block, 0, st_, ecal[0]->n, pg_.poses.val.p, pg_.poses.hidx.p, pg_.cal_vi.p,
                          pg_.cal_vj.p, pg_.cal_vl.p, pg_.cal_meas.p, ecal[0]->own_J0.p, ecal[0]->own_J1.p, ecal[2]->own_J1.p, ecal[0]->own_err.p,
                          jac);
+    });
+  }
+  if (eod[0] && eod[0]->n > 0) {   // EdgeSE2OdomDifferentialCalib -- pg_odom_calib.inc
+    const dim3 grid(grid_for(eod[0]->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      hipLaunchKernelGGL(pg_se2_odom_calib_linearize_kernel<STAGED>, grid, block, 0, st_, eod[0]->n, pg_.poses.val.p, pg_.poses.hidx.p,
+                         pg_.od_vi.p, pg_.od_vj.p, pg_.od_vp.p, pg_.od_meas.p, eod[0]->own_J0.p, eod[0]->own_J1.p, eod[2]->own_J1.p,
+                         eod[0]->own_err.p, jac);
     });
   }
   if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.end(KernelProf::kPgLandmark, st_);
@@ -6883,7 +7099,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
     eg->has_err = true;
     if (jacobians) eg->has_data = true;
   }
-  for (EdgeSet* e : {ec, esc, eo, eb, ecal[0], ecal[1], ecal[2]})
+  for (EdgeSet* e : {ec, esc, eo, eb, ecal[0], ecal[1], ecal[2], eod[0], eod[1], eod[2]})
     if (e) {
       e->has_err = true;
       if (jacobians) e->has_data = true;
@@ -6895,7 +7111,10 @@ void BlockSolver::pg_update() {
   if (pg_.poses.n <= 0) throw StateFailure("pg_update before pg_set_estimates");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   pg_.err_valid = pg_.jac_valid = false;
-  if (pg_.type == 1)
+  if (pg_.type == 1 && pg_.od_ij >= 0)   // (rows of VertexOdomDifferentialParams in the table: pg_set_odom_calib_edges)
+    hipLaunchKernelGGL(pg_se2_update_additive_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
+                       pg_.poses.hidx.p, pg_.od_mask.p, d_x.p);
+  else if (pg_.type == 1)
     hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
   else if (pg_.type == 2)

@@ -82,9 +82,15 @@ def read_g2o(path):
     these keys.
     A file with EDGE_SE2_CALIB lines (i j l x y theta + 6: EdgeSE2SensorCalib::read, g2o/types/sclam2d/edge_se2_sensor_calib.cpp; the
     laser offset l is a plain VERTEX_SE2) also gives cal_vi / cal_vj / cal_vl (pose-table indices), cal_meas [m][3] and cal_info
-    [m][3][3] (calib_problem turns them into a problem dict); a file without them gives none of these keys."""
+    [m][3][3] (calib_problem turns them into a problem dict); a file without them gives none of these keys.
+    VERTEX_ODOM_DIFFERENTIAL lines (id k_l k_r b: VertexOdomDifferentialParams::read, g2o/types/sclam2d/
+    vertex_odom_differential_params.cpp) become rows of the same estimate table, listed in odom_param_rows (ADDITIVE rows: they
+    are no SE2), and EDGE_SE2_ODOM_DIFFERENTIAL_CALIB lines (i j p vl vr dt + 6: EdgeSE2OdomDifferentialCalib::read,
+    edge_se2_odom_differential_calib.cpp:39-61) give odo_vi / odo_vj / odo_vp (table indices), odo_meas [m][3] = (vl, vr, dt) and
+    odo_info [m][3][3] (odom_calib_problem turns them into a problem dict); a file without them gives none of these keys."""
     from . import sim3 as S3
     c_i, c_j, c_l, c_meas, c_info = [], [], [], [], []
+    d_i, d_j, d_p, d_meas, d_info, d_params = [], [], [], [], [], []
     g_i, g_j, g_vals = [], [], []
     sim3_extras = []
     spid, spest, sp_pt, sp_pose, sp_meas, sp_info = [], [], [], [], [], []
@@ -126,6 +132,17 @@ def read_g2o(path):
                 c_l.append(int(t[3]))
                 c_meas.append([float(x) for x in t[4:7]])
                 c_info.append(_upper_to_full([float(x) for x in t[7:13]], 3))
+            elif tag == "EDGE_SE2_ODOM_DIFFERENTIAL_CALIB":
+                d_i.append(int(t[1]))
+                d_j.append(int(t[2]))
+                d_p.append(int(t[3]))
+                d_meas.append([float(x) for x in t[4:7]])
+                d_info.append(_upper_to_full([float(x) for x in t[7:13]], 3))
+            elif tag == "VERTEX_ODOM_DIFFERENTIAL":
+                kind = kind or "se2"
+                vid.append(int(t[1]))
+                vest.append([float(x) for x in t[2:5]])
+                d_params.append(int(t[1]))
             elif tag == "VERTEX_SE2":
                 kind = kind or "se2"
                 vid.append(int(t[1]))
@@ -314,6 +331,11 @@ def read_g2o(path):
         out.update(off_vi=np.asarray([lut[a] for a in o_i], np.int32), off_vj=np.asarray([lut[a] for a in o_j], np.int32),
                    off_from=np.asarray(o_from, np.int32), off_to=np.asarray(o_to, np.int32), off_meas=np.asarray(o_meas, np.float64),
                    off_info=np.asarray(o_info, np.float64), off_kind=o_kind, offsets=offsets)
+    if d_i or d_params:
+        out.update(odo_vi=np.asarray([lut[a] for a in d_i], np.int32), odo_vj=np.asarray([lut[a] for a in d_j], np.int32),
+                   odo_vp=np.asarray([lut[a] for a in d_p], np.int32), odo_meas=np.asarray(d_meas, np.float64).reshape(-1, 3),
+                   odo_info=np.asarray(d_info, np.float64).reshape(-1, 3, 3),
+                   odom_param_rows=np.asarray(sorted(lut[a] for a in d_params), np.int32))
     if c_i:
         out.update(cal_vi=np.asarray([lut[a] for a in c_i], np.int32), cal_vj=np.asarray([lut[a] for a in c_j], np.int32),
                    cal_vl=np.asarray([lut[a] for a in c_l], np.int32), cal_meas=np.asarray(c_meas, np.float64).reshape(-1, 3),
@@ -590,6 +612,55 @@ def calib_problem(rd, fixed=None):
     return dict(kind="se2", n=n, nP=nP, poses=np.asarray(rd["estimates"], np.float64).reshape(-1, 3), hidx=hidx, vi=rd["vi"], vj=rd["vj"],
                 Z=np.asarray(rd["meas"], np.float64).reshape(-1, 3), omega=np.asarray(rd["info"], np.float64).reshape(-1, 9),
                 ci=rd["cal_vi"], cj=rd["cal_vj"], cl=rd["cal_vl"], cmeas=rd["cal_meas"], cinfo=rd["cal_info"].reshape(-1, 9))
+
+
+def write_g2o_odom_calib(path, prob, ids=None):
+    """make_calib_rig(odom_calib=True)-style problem -> `.g2o` text: VERTEX_SE2 lines for the rows of prob["poses"] that are poses
+    (the laser offset among them), VERTEX_ODOM_DIFFERENTIAL "id k_l k_r b" for the rows of prob["param_rows"], a FIX line for the
+    rows of hessian index -1, the odometry as EDGE_SE2 (there may be none), the calibration edges as EDGE_SE2_CALIB where the
+    problem has them (ci ...) and the odometry-calibration edges as EDGE_SE2_ODOM_DIFFERENTIAL_CALIB "i j p vl vr dt
+    upper-triangle" (EdgeSE2OdomDifferentialCalib::write).  %.17g: a read gives the written doubles back."""
+    X = np.asarray(prob["poses"], np.float64).reshape(-1, 3)
+    n = len(X)
+    ids = np.arange(n) if ids is None else np.asarray(ids)
+    params = set(int(r) for r in prob["param_rows"])
+    fmt = lambda v: " ".join("%.17g" % float(x) for x in v)
+    upper = lambda M: fmt(M[i, j] for i in range(3) for j in range(i, 3))
+    with open(path, "w") as f:
+        for k in range(n):
+            f.write("%s %d %s\n" % ("VERTEX_ODOM_DIFFERENTIAL" if k in params else "VERTEX_SE2", ids[k], fmt(X[k])))
+        fixed = [ids[k] for k in range(n) if prob["hidx"][k] < 0]
+        if fixed:
+            f.write("FIX %s\n" % " ".join(str(int(i)) for i in fixed))
+        Z, om = np.asarray(prob["Z"], np.float64).reshape(-1, 3), np.asarray(prob["omega"], np.float64).reshape(-1, 3, 3)
+        for e in range(len(Z)):
+            f.write("EDGE_SE2 %d %d %s %s\n" % (ids[prob["vi"][e]], ids[prob["vj"][e]], fmt(Z[e]), upper(om[e])))
+        if "ci" in prob:
+            Zc, oc = np.asarray(prob["cmeas"], np.float64).reshape(-1, 3), np.asarray(prob["cinfo"], np.float64).reshape(-1, 3, 3)
+            for e in range(len(Zc)):
+                f.write("EDGE_SE2_CALIB %d %d %d %s %s\n" % (ids[prob["ci"][e]], ids[prob["cj"][e]], ids[prob["cl"][e]], fmt(Zc[e]), upper(oc[e])))
+        M, oo = np.asarray(prob["omeas"], np.float64).reshape(-1, 3), np.asarray(prob["oinfo"], np.float64).reshape(-1, 3, 3)
+        for e in range(len(M)):
+            f.write("EDGE_SE2_ODOM_DIFFERENTIAL_CALIB %d %d %d %s %s\n" % (ids[prob["oi"][e]], ids[prob["oj"][e]], ids[prob["op"][e]], fmt(M[e]), upper(oo[e])))
+
+
+def odom_calib_problem(rd, fixed=None):
+    """read_g2o result of a file with EDGE_SE2_ODOM_DIFFERENTIAL_CALIB lines -> the problem dict of
+    synthetic.make_calib_rig(odom_calib=True) (what lm.setup_device_odom_calib_graph(poses, hidx, nP, dict(vi=oi, vj=oj, vp=op,
+    meas=omeas, info=oinfo), vi, vj, Z, omega) takes; with EDGE_SE2_CALIB lines in the file also ci ... cinfo for calib_edges=).  fixed: indices into
+    the table (default: the file's FIX lines; a file without any gets row 0 fixed as the gauge)."""
+    if "odo_vi" not in rd or rd.get("kind") != "se2":
+        raise ValueError("odom_calib_problem: not a VERTEX_SE2 file with EDGE_SE2_ODOM_DIFFERENTIAL_CALIB lines")
+    n = len(rd["estimates"])
+    fixed = (rd["fixed"] or [0]) if fixed is None else fixed
+    hidx, nP = hessian_index(n, fixed)
+    out = dict(kind="se2", n=n, nP=nP, poses=np.asarray(rd["estimates"], np.float64).reshape(-1, 3), hidx=hidx, vi=rd["vi"], vj=rd["vj"],
+               Z=np.asarray(rd["meas"], np.float64).reshape(-1, 3), omega=np.asarray(rd["info"], np.float64).reshape(-1, 9),
+               oi=rd["odo_vi"], oj=rd["odo_vj"], op=rd["odo_vp"], omeas=rd["odo_meas"], oinfo=rd["odo_info"].reshape(-1, 9),
+               param_rows=rd["odom_param_rows"])
+    if "cal_vi" in rd:
+        out.update(ci=rd["cal_vi"], cj=rd["cal_vj"], cl=rd["cal_vl"], cmeas=rd["cal_meas"], cinfo=rd["cal_info"].reshape(-1, 9))
+    return out
 
 
 def hessian_index(n_vertices, fixed):

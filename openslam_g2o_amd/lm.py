@@ -391,7 +391,26 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     calib_edges: dict(vi, vj, vl, meas, info) -- three-vertex EdgeSE2SensorCalib scan-match edges (edge_type 1 only): vi / vj the
     two poses, vl the laser offset, all rows of `estimates`; meas [n][3], info [n][9] or None (identity).  The three binary sets
     (i, j), (i, l), (j, l) are added with their parts and bound as one group (g2ohip_pg_set_sensor_calib_edges);
-    solver.calib_sets = their ids; huber_delta > 0 puts a Huber kernel on all three."""
+    solver.calib_sets = their ids; huber_delta > 0 puts a Huber kernel on all three.
+    (EdgeSE2OdomDifferentialCalib edges: setup_device_odom_calib_graph.)"""
+    return _setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim, device, priors, fix_scale,
+                                    options, offset_edges, calib_edges, huber_delta, None)
+
+
+def setup_device_odom_calib_graph(estimates, hidx, num_free, odom_calib_edges, vi=(), vj=(), meas=(), info=(), calib_edges=None,
+                                  huber_delta=0.0, options=None, device=0):
+    """setup_device_pose_graph(1, ...) for the graph of g2o/examples/calibration_odom_laser: the same arguments, and
+    odom_calib_edges: dict(vi, vj, vp, meas, info) -- three-vertex EdgeSE2OdomDifferentialCalib edges: vi / vj the two poses, vp
+    the VertexOdomDifferentialParams (k_l, k_r, b), all rows of `estimates` (the rows of vp are additive rows while the group is
+    bound); meas [n][3] = (vl, vr, dt), info [n][9] or None (identity).  Added and bound like calib_edges
+    (g2ohip_pg_set_odom_calib_edges), beside them or alone; solver.odom_calib_sets = their ids; huber_delta goes on these three
+    too.  The EdgeSE2 set vi / vj / meas / info may be empty (the default): that example's graph holds no EdgeSE2."""
+    return _setup_device_pose_graph(1, estimates, hidx, num_free, vi, vj, meas, info, None, device, None, False, options, None,
+                                    calib_edges, huber_delta, odom_calib_edges)
+
+
+def _setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, info, landmark_dim, device, priors, fix_scale, options,
+                             offset_edges, calib_edges, huber_delta, odom_calib_edges):
     import numpy as np
     from . import capi
     d = PG_POSE_DIM[edge_type]
@@ -399,7 +418,7 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
     for name, value in (options or {}).items():
         s.setOption(name, value)
     hidx = np.asarray(hidx, np.int32)
-    k = s.addEdgeSet(d, hidx[np.asarray(vi)], hidx[np.asarray(vj)])
+    k = s.addEdgeSet(d, hidx[np.asarray(vi, np.int64)], hidx[np.asarray(vj, np.int64)])
     if priors is not None:
         ptype, vq, zq, omega_q, offset = priors
         kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[np.asarray(vq)], None)
@@ -413,6 +432,13 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
         for (a, b), pt in zip(((ci, cj), (ci, cl), (cj, cl)), parts):
             kc.append(s.addEdgeSet(3, hidx[a], hidx[b]))
             s.setEdgeSetParts(kc[-1], pt)
+    if odom_calib_edges is not None:
+        qi, qj, qp = (np.asarray(odom_calib_edges[key], np.int64) for key in ("vi", "vj", "vp"))
+        parts = (0, capi.PART_NO_VERTEX0 | capi.PART_NO_VERTEX1 | capi.PART_NO_CHI2, capi.PART_NO_VERTEX0 | capi.PART_NO_CHI2)
+        kq3 = []
+        for (a, b), pt in zip(((qi, qj), (qi, qp), (qj, qp)), parts):
+            kq3.append(s.addEdgeSet(3, hidx[a], hidx[b]))
+            s.setEdgeSetParts(kq3[-1], pt)
     s.buildStructure(num_free, 0, False)
     s.pgSetEdges(k, edge_type, vi, vj, meas, info)
     if edge_type == 10:
@@ -428,6 +454,11 @@ def setup_device_pose_graph(edge_type, estimates, hidx, num_free, vi, vj, meas, 
         s.pgSetSensorCalibEdges(*kc, ci, cj, cl, calib_edges["meas"], calib_edges.get("info"))
         if huber_delta > 0:
             for kk in kc:
+                s.setRobustKernel(kk, capi.KERNEL_HUBER, huber_delta)
+    if odom_calib_edges is not None:
+        s.pgSetOdomCalibEdges(*kq3, qi, qj, qp, odom_calib_edges["meas"], odom_calib_edges.get("info"))
+        if huber_delta > 0:
+            for kk in kq3:
                 s.setRobustKernel(kk, capi.KERNEL_HUBER, huber_delta)
     return s, DevicePoseGraph(s)
 

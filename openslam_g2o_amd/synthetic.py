@@ -1066,7 +1066,7 @@ def make_bearing_slam(n_poses, n_landmarks, with_xy=False, seed=42, noise=0.02, 
 
 
 def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.1, 0.03), offset=(0.3, 0.1, 0.2), fix_offset=False,
-                   wrap_every=0, pairs=None):
+                   wrap_every=0, pairs=None, odom_calib=False, n_params=1, params=(1.06, 0.93, 1.25)):
     """Simultaneous calibration, localisation and mapping in 2-D (what g2o/examples/calibration_odom_laser optimises): n_poses
     robot poses on a trajectory that keeps turning (so that the laser's mounting offset is observable), EdgeSE2 odometry between
     consecutive poses, and three-vertex EdgeSE2SensorCalib scan-match edges (x1, x2, L) between consecutive poses and at `loops`
@@ -1079,8 +1079,17 @@ def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.
     holds L fixed at the truth (hessian index -1: plain scan-match SLAM through the same edges).  wrap_every = w > 0: every w-th
     calibration edge measures an angle off by pi -/+ 1e-3 (alternating), so that its angle error lands just inside +pi or just
     inside -pi: gross outliers on both sides of the wrap (for a robust kernel).  Deterministic from seed.
+    odom_calib=True adds the other half of that example's graph: n_params rows of VertexOdomDifferentialParams (k_l, k_r, b)
+    behind the offset row (ADDITIVE rows: estimate += step, no angle wrap) and one three-vertex EdgeSE2OdomDifferentialCalib per
+    consecutive pose pair (edge k names parameter row k % n_params: n_params robots taking turns).  The trajectory is then built
+    from arcs of length 0.5 held for dt = 0.8 + 0.1 (k % 5), every fifth one STRAIGHT, so that the true motions are exactly what
+    OdomConvert::convertToMotion produces; the wheel velocities are those of the noisy motion (translation noise alone on the
+    straight segments) by OdomConvert::convertToVelocity (wheel base 1), rescaled to a robot of the true parameters `params`
+    (+ 0.04 r (1, -1, 2) for robot r), as sclam_helpers.cpp:93-94 generates them.  Initial estimate (1, 1, 1), as setToOriginImpl.
+    The default arguments produce the arrays they always did.
     Returns kind ("se2"), n (rows of the pose table), n_poses, offset_row, nP, poses, poses_true, hidx, vi, vj, Z, omega
-    (odometry), ci, cj, cl, cmeas, cinfo (calibration edges), offset_true."""
+    (odometry), ci, cj, cl, cmeas, cinfo (calibration edges), offset_true; with odom_calib also oi, oj, op, omeas, oinfo
+    (odometry-calibration edges), param_rows, params_true."""
     if n_poses < 3 or loops < 0:
         raise ValueError("make_calib_rig: n_poses >= 3, loops >= 0")
     rng = CounterRng(seed + 1)
@@ -1089,6 +1098,19 @@ def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.
     th = 0.35 * s + 0.3 * np.sin(0.5 * s)
     step = 0.5 * np.stack([np.cos(th), np.sin(th)], axis=1)
     X = np.concatenate([np.concatenate([np.zeros((1, 2)), np.cumsum(step[:-1], axis=0)]), th[:, None]], axis=1)
+    if odom_calib:
+        if n_params < 1:
+            raise ValueError("make_calib_rig: n_params >= 1")
+        from . import odom_calib as OC
+        dth = np.diff(th)
+        dth[np.arange(n - 1) % 5 == 4] = 0.0
+        dts = 0.8 + 0.1 * (np.arange(n - 1) % 5)
+        vtrue = np.stack([[(0.5 - 0.5 * a) / t, (0.5 + 0.5 * a) / t, t] for a, t in zip(dth, dts)])   # S dt / 2 = 0.5, D dt = dth
+        M = np.stack([OC.convert_to_motion(OC.FP64, v, 1.0) for v in vtrue])
+        X = np.zeros((n, 3))
+        X[0, 2] = th[0]
+        for k in range(n - 1):
+            X[k + 1] = _se2_mul(X[k:k + 1], M[k:k + 1])[0]
     X[:, 2] = (X[:, 2] + np.pi) % (2.0 * np.pi) - np.pi
     Lt = np.asarray(offset, np.float64).reshape(1, 3)
     vi, vj = np.arange(n - 1, dtype=np.int32), np.arange(1, n, dtype=np.int32)
@@ -1118,6 +1140,27 @@ def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.
     poses = np.concatenate([Xe, Lt if fix_offset else np.zeros((1, 3))])
     hidx = np.concatenate([np.arange(n, dtype=np.int32) - 1, [-1 if fix_offset else n - 1]]).astype(np.int32)
     w = np.diag([1.0 / noise[0] ** 2] * 2 + [1.0 / noise[1] ** 2])
+    if odom_calib:
+        nz = motion(40, n - 1, noise)
+        straight = dth == 0.0
+        nz[straight, 1:] = 0.0
+        Mn = _se2_mul(M, nz)
+        ptrue = np.stack([np.asarray(params, np.float64) + 0.04 * r * np.array([1.0, -1.0, 2.0]) for r in range(n_params)])
+        op = (n + 1 + np.arange(n - 1) % n_params).astype(np.int32)
+        omeas = np.zeros((n - 1, 3))
+        for k in range(n - 1):
+            v1 = OC.convert_to_velocity(OC.FP64, Mn[k], dts[k])
+            kl, kr, b = ptrue[k % n_params]
+            S1, D1 = v1[0] + v1[1], v1[1] - v1[0]
+            omeas[k] = [0.5 * (S1 - b * D1) / kl, 0.5 * (S1 + b * D1) / kr, dts[k]]
+        free = n - 1 + (0 if fix_offset else 1)
+        return dict(kind="se2", n=n + 1 + n_params, n_poses=n, offset_row=n, nP=free + n_params,
+                    poses=np.concatenate([poses, np.ones((n_params, 3))]), poses_true=np.concatenate([X, Lt, ptrue]),
+                    hidx=np.concatenate([hidx, free + np.arange(n_params)]).astype(np.int32), vi=vi, vj=vj, Z=Z0,
+                    omega=np.tile(w.reshape(1, 9), (n - 1, 1)), ci=ci, cj=cj, cl=np.full(m, n, np.int32), cmeas=Zc,
+                    cinfo=np.tile(w.reshape(1, 9), (m, 1)), offset_true=Lt[0].copy(), oi=vi.copy(), oj=vj.copy(), op=op, omeas=omeas,
+                    oinfo=np.tile(w.reshape(1, 9), (n - 1, 1)), param_rows=np.arange(n + 1, n + 1 + n_params, dtype=np.int32),
+                    params_true=ptrue)
     return dict(kind="se2", n=n + 1, n_poses=n, offset_row=n, nP=n - 1 + (0 if fix_offset else 1), poses=poses,
                 poses_true=np.concatenate([X, Lt]), hidx=hidx, vi=vi, vj=vj, Z=Z0, omega=np.tile(w.reshape(1, 9), (n - 1, 1)), ci=ci, cj=cj,
                 cl=np.full(m, n, np.int32), cmeas=Zc, cinfo=np.tile(w.reshape(1, 9), (m, 1)), offset_true=Lt[0].copy())
