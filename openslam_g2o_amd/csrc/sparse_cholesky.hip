@@ -14,6 +14,10 @@ namespace g2ohip {
 
 constexpr int kGatherLdsOff = 3 * 64 * 65 + 64 + 128;   // gather table of a front in LDS (kGatherInts): behind the level launch's own regions (doubles)
 constexpr int kFactorThreadsGlobal = 512;
+// front_factor_kernel on a scratch-slab front (one workgroup per front) stages the front's assembly list in LDS only up to this
+// many ints (32 KB; a launch may ask for 64 KiB without a raised limit); a longer list -- a pivot panel of block size 3 under
+// 350 block rows has 5 500 entries of 2 ints, 7 with the virtual source -- is read from global memory where it is used
+constexpr int kGlbIdxStageInts = 8192;
 constexpr int kLdsMfma = (4 << 16) | 96;          // LDS fronts with at least (low 16 bits) boundary rows and (high bits) pivot blocks: pivot steps update
                                                   // the panel only, ONE MFMA rank-npiv update of the trailing matrix afterwards (CholPlanDev::lds_mfma)
 constexpr int kWideFrontDoubles = 5000;           // launches whose largest LDS front has this many packed doubles (100 rows) use 512 threads per front
@@ -349,16 +353,19 @@ __global__ void __launch_bounds__(NTC, (USE_LDS && NTC <= 256) ? (NTC == 128 ? G
 #endif
     // ---- stage the index tables in LDS, zero the front meanwhile.  The four tables are contiguous in LDS
     // (q | pos | cmap | tri); all their loads are issued before the first wait: one memory round trip.
-    {
-      const int n1 = na, n2 = 2 * na, n3 = USE_LDS ? n2 + rec.cmap_cnt : n2, n5 = USE_LDS ? n3 + rec.tri_cnt : n2;
-      const int n4 = USE_LDS ? n5 + rec.crel_cnt : n2;   // (q | pos | cmap | tri | crel | v)
-      const int n6 = VIRT ? n4 + kVirtInts * na : n4;    // virtual source: (count, 3 partial slots, first list index) per entry
-      const int* g_q = (VIRT ? P.asm_vq : P.asm_q) + rec.asm_off;
-      const int* g_pos = (VIRT ? P.asm_vpos : P.asm_pos) + rec.asm_off - n1;
+    const int n1 = na, n2 = 2 * na, n3 = USE_LDS ? n2 + rec.cmap_cnt : n2, n5 = USE_LDS ? n3 + rec.tri_cnt : n2;
+    const int n4 = USE_LDS ? n5 + rec.crel_cnt : n2;   // (q | pos | cmap | tri | crel | v)
+    const int n6 = VIRT ? n4 + kVirtInts * na : n4;    // virtual source: (count, 3 partial slots, first list index) per entry
+    const int* g_q = (VIRT ? P.asm_vq : P.asm_q) + rec.asm_off;
+    const int* g_pos = (VIRT ? P.asm_vpos : P.asm_pos) + rec.asm_off - n1;
+    const int* g_v = P.asm_v + (size_t)kVirtInts * rec.asm_off - n4;
+    // scratch-slab fronts: (q | pos | v) staged only if it fits the launch's room (kGlbIdxStageInts), read in place otherwise
+    const bool staged = USE_LDS || n6 <= kGlbIdxStageInts;
+    auto idx_at = [&](int i) { return (USE_LDS || staged) ? s_q[i] : (i < n1 ? g_q : (i < n2 ? g_pos : g_v))[i]; };
+    if (staged) {
       const int* g_cmap = P.cmap + rec.cmap_off - n2;
       const int* g_tri = P.tri - n3;
       const int* g_crel = P.crel + rec.crel_off - n5;
-      const int* g_v = P.asm_v + (size_t)kVirtInts * rec.asm_off - n4;
       constexpr int SU = 4;
       for (int base = tid; base < n6; base += SU * NT) {
         int v[SU];
@@ -439,7 +446,7 @@ __global__ void __launch_bounds__(NTC, (USE_LDS && NTC <= 256) ? (NTC == 128 ? G
       // partial blocks, subtracted in list order -- the Schur complement's reduction pass folded into this load
       // (same operations in the same order as the stand-alone reduction: identical bits).
       const int nA = na * BB;
-      const int* s_v = s_q + (USE_LDS ? 2 * na + rec.cmap_cnt + rec.tri_cnt + rec.crel_cnt : 2 * na);
+      const int iv0 = n4;   // first int of the per-entry records of the virtual source in the staged tables
       const double lam0 = P.vlam[0];
       constexpr int UA = 4, HB = BS / 2;
       const bool vsplit = P.vsplit != 0;
@@ -461,17 +468,17 @@ __global__ void __launch_bounds__(NTC, (USE_LDS && NTC <= 256) ? (NTC == 128 ? G
           if (t < nA) {
             const int e = t / BB, rc = t - e * BB;
             const int r = rc % BS, c = rc / BS;
-            const int q = s_q[e], pos = s_pos[e];
+            const int q = idx_at(e), pos = idx_at(n1 + e);
             const int lr = pos & 0x7fff, lc = (pos >> 15) & 0x7fff, tr = (pos >> 30) & 1;
             const int rr = tr ? c : r, cc = tr ? r : c;               // element of the stored (upper) block
             const int rp = (vsplit && rr >= HB) ? 1 : 0, nrp = vsplit ? HB : BS;
             pe[u] = rp * (nrp * BS) + (rr - rp * nrp) + nrp * cc;     // partial layout [row part][column][row in part]
-            const int* sv = s_v + kVirtInts * e;
-            nn[u] = sv[0];
-            sv3[u] = kVirtInts * e;
+            const int sv = iv0 + kVirtInts * e;
+            nn[u] = idx_at(sv);
+            sv3[u] = sv;
             if (q >= 0) a[u] = P.vbase[(size_t)q * BB + rr + BS * cc];
-            p0[u] = P.vparts[(size_t)sv[1] * BB + pe[u]];
-            p1[u] = P.vparts[(size_t)sv[2] * BB + pe[u]];
+            p0[u] = P.vparts[(size_t)idx_at(sv + 1) * BB + pe[u]];
+            p1[u] = P.vparts[(size_t)idx_at(sv + 2) * BB + pe[u]];
             dl[u] = (pos < 0) && rr == cc;                            // (bit 31: diagonal block)
             dst[u] = blk_off(lr, lc) + r + cs * c;
           }
@@ -484,9 +491,9 @@ __global__ void __launch_bounds__(NTC, (USE_LDS && NTC <= 256) ? (NTC == 128 ? G
             if (nn[u] > 0) v -= p0[u];
             if (nn[u] > 1) v -= p1[u];
             if (nn[u] > 2) {
-              const int* sv = s_v + sv3[u];
-              v -= P.vparts[(size_t)sv[3] * BB + pe[u]];
-              for (int k = sv[4] + 3, kend = sv[4] + nn[u]; k < kend; k += 8) {   // (long lists: eight partials per round trip, list order kept)
+              const int sv = sv3[u], l0 = idx_at(sv + 4);
+              v -= P.vparts[(size_t)idx_at(sv + 3) * BB + pe[u]];
+              for (int k = l0 + 3, kend = l0 + nn[u]; k < kend; k += 8) {   // (long lists: eight partials per round trip, list order kept)
                 int sl[8];
                 double pv[8];
 #pragma unroll
@@ -515,7 +522,7 @@ __global__ void __launch_bounds__(NTC, (USE_LDS && NTC <= 256) ? (NTC == 128 ? G
             if (t < nA) {
               const int e = t / BB, rc = t - e * BB;
               const int r = rc % BS, c = rc / BS;
-              const int q = s_q[e], pos = s_pos[e];
+              const int q = idx_at(e), pos = idx_at(n1 + e);
               const int lr = pos & 0x7fff, lc = (pos >> 15) & 0x7fff, tr = (pos >> 30) & 1;
               v[u] = tr ? A[(size_t)q * BB + c + BS * r] : A[(size_t)q * BB + r + BS * c];
               dst[u] = blk_off(lr, lc) + r + cs * c;
@@ -3047,7 +3054,9 @@ void launch_factor_level(const CholPlanDev& P, const LevelLaunch& LL, const Fact
     G2OHIP_LAUNCH_CHECK("big_front_update_kernel");
   } else if (glb_count > 0) {
     const int idx_off = 2 * (BS * BS + BS);
-    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(LL.glb_idx_ints + 4) * sizeof(int);
+    // (the plan counts 2 + kVirtInts ints per assembly entry; the plain source stages 2 of them; lists beyond kGlbIdxStageInts are not staged)
+    const int idx_ints = LL.glb_idx_ints / (2 + kVirtInts) * (VIRT ? 2 + kVirtInts : 2);
+    size_t sh = (size_t)idx_off * sizeof(double) + (size_t)(std::min(idx_ints, kGlbIdxStageInts) + 4) * sizeof(int);
     hipLaunchKernelGGL((front_factor_kernel<BS, false, kFactorThreadsGlobal, VIRT>), dim3(glb_count), dim3(kFactorThreadsGlobal), sh, st, P, glb_begin, A.dA,
                        d_scratch, d_scratch_off + glb_begin, idx_off, 0, (const double*)nullptr, (double*)nullptr, 0);
     G2OHIP_LAUNCH_CHECK("front_factor_kernel");

@@ -40,6 +40,19 @@ def test_band_kernel_matches_the_general_kernel_and_the_oracle(P, L, fold):
     assert relerr(x1, o.x()) < tol
 
 
+def test_band_kernel_on_the_folded_source_equals_the_materialised_one_bit_for_bit():
+    """The (257, 2600) pair above: the band kernel fed by Hpp and the tiles' partial blocks (the virtual source,
+    fuse_schur_reduce = 1) against the same kernel on a materialised Hschur: the same operations in the same order, as
+    test_schur_reduction_folded_into_factorisation shows at 300 cameras.  This ties the virtual-source instantiations to the
+    plain-source kernels that tests/test_gpu_cholesky_solve.py holds to its reference."""
+    pr = ba_case(257, 2600)
+    ok1, x1, st1 = _solve(pr, 25.0, {"band_kernel": 1, "fuse_schur_reduce": 1})
+    ok0, x0, st0 = _solve(pr, 25.0, {"band_kernel": 1, "fuse_schur_reduce": 0})
+    assert ok1 and ok0
+    assert st1["bandChains"] > 0 and st0["bandChains"] == st1["bandChains"]
+    assert np.array_equal(x1, x0)
+
+
 def test_band_kernel_is_bit_repeatable_and_flags_a_non_positive_pivot():
     pr = ba_case(900, 9000)
     s = hip_ba(pr)
