@@ -198,6 +198,13 @@ class HostStagedComm(TorchComm):
                 t.copy_(c)
 
 
+class LocalStatus:
+    """What a phase generator yields where the collective is the ranks' verdict instead of a sum of buffers."""
+
+    def __init__(self, ok, device):
+        self.ok, self.device = ok, device
+
+
 class ShardedBlockSolver:
     def __init__(self, pose_dim, landmark_dim, rank=0, world=1, device=0, local=None, comm=None, force_exchange=False,
                  mode="auto", x_exchange="halo"):
@@ -399,28 +406,47 @@ class ShardedBlockSolver:
                 self._native = True
         return self._native
 
+    def _drive(self, phases):
+        """Run a phase generator (solve_phases and the three below): all-reduce what it yields, return what it returns."""
+        item, answer = None, None
+        while True:
+            try:                                       # (only the generator's own end is caught here, not the comm's errors)
+                item = next(phases) if item is None else phases.send(answer)
+            except StopIteration as done:
+                return done.value
+            if isinstance(item, LocalStatus):          # the one collective that is a host scalar: "did every rank succeed"
+                answer = self.comm.all_ok(item.ok, item.device)
+            else:
+                self.comm.all_reduce_sum(item)
+                answer = None
+
+    def _phases_native_halo(self):
+        """The native sequence of _solve_subtree_halo as a generator: yields the list of device tensors of every collective
+        and resumes once the caller has summed them over the ranks; returns the status of the solve."""
+        L = self.local
+        for _ in range(3):                    # (REPEAT: the status word is a sum over the ranks, every rank loops alike)
+            L.solveSchur()
+            if len(self.boundary) or len(self.bposes):
+                L.exchangePack(1)
+                yield [self._nbuf1]
+                L.exchangeUnpack(1)
+            L.solveReducedLocal()
+            yield [self._nxbuf]
+            L.solveReducedShared()
+            L.solveReducedFinishAsync()
+            L.exchangePack(3)
+            yield [self._nbuf3]
+            L.exchangeUnpack(3)
+            L.solveBackSubstitute()           # (harmless after a failed factorisation: the caller discards x)
+            ok = L.exchangeStatus()
+            if ok is True or ok is False:
+                return ok
+        return False
+
     def _solve_subtree_halo(self):
         """Three latency-sized collectives: boundary Hschur blocks + boundary b_p | subtree roots | halo x_p + status."""
         if self._native_exchange():
-            L = self.local
-            for _ in range(3):                    # (REPEAT: the status word is a sum over the ranks, every rank loops alike)
-                L.solveSchur()
-                if len(self.boundary) or len(self.bposes):
-                    L.exchangePack(1)
-                    self.comm.all_reduce_sum([self._nbuf1])
-                    L.exchangeUnpack(1)
-                L.solveReducedLocal()
-                self.comm.all_reduce_sum([self._nxbuf])
-                L.solveReducedShared()
-                L.solveReducedFinishAsync()
-                L.exchangePack(3)
-                self.comm.all_reduce_sum([self._nbuf3])
-                L.exchangeUnpack(3)
-                L.solveBackSubstitute()           # (harmless after a failed factorisation: the caller discards x)
-                ok = L.exchangeStatus()
-                if ok is True or ok is False:
-                    return ok
-            return False
+            return self._drive(self._phases_native_halo())
         import torch
         t = self._subtree_tensors()
         p = self.p
@@ -464,27 +490,58 @@ class ShardedBlockSolver:
         self.comm.all_reduce_sum([t])
         return t.cpu().numpy()
 
-    def _solve_subtree(self):
-        if self.x_exchange == "halo":
-            return self._solve_subtree_halo()
+    def _phases_subtree_full(self):
+        """_solve_subtree with x_exchange="full" as a generator (see _phases_native_halo); the last collective is a
+        LocalStatus, answered with the all-ranks verdict."""
         t = self._subtree_tensors()
         self.local.solveSchur()
         if len(self.boundary):
             buf = t["H"].index_select(0, t["idx"])
-            self.comm.all_reduce_sum([buf])
+            yield [buf]
             t["H"].index_copy_(0, t["idx"], buf * t["hkeep"])
-        self.comm.all_reduce_sum([t["b"]])
+        yield [t["b"]]
         t["b2"].mul_(t["bkeep_all"])
         self.local.solveReducedLocal()          # own subtrees: factor + forward sweep, pack the roots
-        self.comm.all_reduce_sum([t["xbuf"]])
+        yield [t["xbuf"]]
         self.local.solveReducedShared()         # shared top, then back down the own subtrees; x_p masked
-        self.comm.all_reduce_sum([t["xp"]])
+        yield [t["xp"]]
         ok = self.local.solveReducedFinish()
-        ok = self.comm.all_ok(ok, t["b"].device)
+        ok = yield LocalStatus(ok, t["b"].device)
         if not ok:
             return False
         self.local.solveBackSubstitute()
         return True
+
+    def _phases_replicated(self):
+        """The replicated branch of solve() as a generator: one all-reduce of Hschur and bschur."""
+        self.local.solveSchur()
+        yield self._reduced_tensors()
+        ok = self.local.solveReduced()
+        if not ok:
+            return False
+        self.local.solveBackSubstitute()
+        return True
+
+    def solve_phases(self):
+        """The phase generator of this solver's solve(), for the three schedules whose collectives are plain sums of device
+        buffers: subtree / halo with the native exchange, subtree / full, replicated with an exchange.  A caller that holds
+        every rank in one process steps one generator per rank side by side and sums what they yield.  Nothing in the package
+        calls this method or reads LocalStatus from outside: they are there for tests/test_gpu_sharded_phases.py, so that the
+        test runs the product's sequence instead of restating it."""
+        if getattr(self, "_lib_comm", None):
+            raise RuntimeError("solve_phases: a library communicator is attached, solve() runs inside the library")
+        if self.mode == "subtree" and self.x_exchange == "halo" and self._native_exchange():
+            return self._phases_native_halo()
+        if self.mode == "subtree" and self.x_exchange == "full":
+            return self._phases_subtree_full()
+        if self.mode == "replicated" and self.exchange:
+            return self._phases_replicated()
+        raise RuntimeError("solve_phases: this schedule has collectives that are not sums of device buffers")
+
+    def _solve_subtree(self):
+        if self.x_exchange == "halo":
+            return self._solve_subtree_halo()
+        return self._drive(self._phases_subtree_full())
 
     def _solve_pcg(self):
         """LinearSolverPCG's iteration (linear_solver_pcg.hpp:79-196, block-Jacobi, relative tolerance) on the reduced system
@@ -603,13 +660,7 @@ class ShardedBlockSolver:
             return self._solve_subtree()
         if not self.exchange:
             return self.local.solve()     # one rank: the solver may fold the Schur reduction into the factorisation
-        self.local.solveSchur()
-        self.comm.all_reduce_sum(self._reduced_tensors())
-        ok = self.local.solveReduced()
-        if not ok:
-            return False
-        self.local.solveBackSubstitute()
-        return True
+        return self._drive(self._phases_replicated())
 
     def chi2(self):
         if getattr(self, "_lib_comm", None):
