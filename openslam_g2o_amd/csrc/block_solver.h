@@ -362,8 +362,16 @@ class BlockSolver {
                          const int* pt_hidx, int np) const;
   void ba_validate_psi_edges(const EdgeSet& a, const EdgeSet& b, const EdgeSet& c, const int* cam_v, const int* anchor_v, const int* pt_v,
                              size_t n, const int* cam_hidx, int nc, const int* pt_hidx, int np) const;
-  void ba_psi_release();
-  void ba_psi_alias();
+  // Three binary sets that stand for ONE three-vertex edge (g2ohip_set_edge_set_parts): ids = (a-b, a-c, b-c).  The first owns the
+  // Jacobians of a and b (own_J0, own_J1), the information and the errors, the third the Jacobian of c (own_J1); every other J0 /
+  // J1 / omega / err pointer of the three aliases one of those.  alias_triple points them there; a pointer that had to be repaired
+  // (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences.  release_triple:
+  // the sets keep no device-written data and no pointer into each other's buffers (set_edge_data is their next source;
+  // build_system refuses them until then, unless they are empty).  Used by the inverse-depth group of the BA front end and by the
+  // two calibration groups of the pose-graph front end; what else a group owns is released by its caller.
+  void alias_triple(const int ids[3]);
+  void release_triple(const int ids[3]);
+  void ba_psi_release();   // (release_triple of it, and its anchors)
   bool ba_recompute_ok() const;
   bool ba_skip_hpl_ok() const;
   bool ba_fuse_ll_ok() const;
@@ -380,19 +388,36 @@ class BlockSolver {
   void pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv, const int* pt_hidx,
                              int np) const;
   void pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const;
-  void pg_validate_calib(const int* vi, const int* vj, const int* vl, size_t n, const int* hidx, int nv) const;
-  void pg_cal_alias();
-  void pg_cal_release();
-  void pg_validate_odom_calib(const int* vi, const int* vj, const int* vp, size_t n, const int* hidx, int nv) const;
-  void pg_od_alias();
-  void pg_od_release();
-  void pg_od_build_mask();
   // a row of the SE2 pose table is read either as a VertexSE2 or as an additive row (VertexOdomDifferentialParams), never both:
   // throws ArgFailure where one of `lists` (index arrays read as VertexSE2) names a row of `additive` (sorted)
   static void pg_refuse_additive(const std::string& who, const std::vector<int>& additive,
-                                 std::initializer_list<std::pair<const int*, size_t>> lists);
+                                 const std::vector<std::pair<const int*, size_t>>& lists);
   void pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                               const double* info, const double* offset, const double* kcam, int n_cams = 0);
+  // ---- the table of slots (PgSlotId, PgSlot below) and the helpers that loop over it, each written once ----
+  enum PgSlotId : int;
+  int pg_slot_of(int set) const;   // the slot that holds the set id, -1: none
+  // What every bind entry starts with, in this order: invalidate_graphs, require_structure, "call pg_set_edges first"
+  // (StateFailure; not for the pose slot itself), the range of the ids, and ownership -- a set may be bound again in its own slot,
+  // an id another slot holds is an ArgFailure.  `who` starts every message (the landmark slot has four entries).
+  void pg_begin_bind(const char* who, PgSlotId slot, std::initializer_list<int> sets);
+  // What every bind entry ends with, after its LAST check: the set that leaves the slot gives up the data the device wrote for it (a
+  // group: pg_release_group), the slot takes the ids, the type, the index arrays (host copy and device) and the measurements
+  // [n][meas_stride]; the first set gets the information [n][d x d] and buffers for J0 [n][d x d0], J1 [n][d x d1] (d1 = 0: a
+  // unary set), errors [n][d] -- a group: the third set its J1, then alias_triple; the pointers of the sets are their own
+  // (external = false), no data and no errors until the first pg_linearize, the cached evaluation and chi2 are dropped; the stream
+  // is synchronised (every array handed in has been read).
+  void pg_commit(PgSlotId slot, std::initializer_list<int> sets, int type, std::initializer_list<const int*> idx, size_t n,
+                 const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info);
+  // a bound slot against candidate estimate tables (the descriptor says which validator: pose pairs, pose-landmark pairs, priors,
+  // or the three pairs of a group)
+  void pg_validate_slot(PgSlotId slot, const int* hidx, int nv, const int* pt_hidx, int np) const;
+  // what the entries of the two calibration groups check alike, up to the index validation against the pose table
+  void pg_check_group(const std::string& who, const int ids[3], const int* vi, const int* vj, const int* vx, const double* meas,
+                      const double* info) const;
+  void pg_release_group(PgSlotId slot);   // a group leaves its slot: release_triple, the host index copies, the cached evaluation
+  void pg_od_release();                   // ... the odometry group: its additive rows are VertexSE2 rows again, the captured launches go
+  void pg_od_build_mask();
   // One table of vertex estimates on the device, as both front ends keep them (ba_.cams / ba_.pts, pg_.poses / pg_.points): the
   // values, their backup (an estimate stack of depth one) and every vertex's index in the system (-1: fixed).
   // Validate, then commit: every committed (edge binding, table) pair has been validated against each other when the later of
@@ -474,107 +499,123 @@ class BlockSolver {
     // The projection slot bound to EdgeProjectPSI2UV (ba_set_inverse_depth_edges, ba_psi.inc): `set` is the (point, pose) set,
     // psi_pa the (point, anchor) set, psi_ca the (pose, anchor) set -- one group, bound and released together.  anchor_v indexes
     // `cams` like cam_v.  `set` owns J_point (own_J0), J_pose (own_J1), information and errors, psi_ca owns J_anchor (own_J1); every
-    // other J0 / J1 / omega / err pointer of the three aliases one of those (ba_psi_alias).  Always the generic path.
+    // other J0 / J1 / omega / err pointer of the three aliases one of those (alias_triple).  Always the generic path.
     bool psi = false;
     int psi_pa = -1, psi_ca = -1;
     DevBuf<int> anchor_v;
     std::vector<int> h_anchor_v;   // host copy: index validation (ba_validate_psi_edges)
   } ba_;
-  // Pose-graph front end: type 1 = EdgeSE2 (x, y, theta), 2 = EdgeSE3 (isometries T[12]) on edge set `set`, and -- optional, beside
-  // it on the same handle -- ONE set of pose-landmark observations `lm_set`: lm_type 3 = EdgeSE2PointXY (beside type 1, landmarks
-  // (x, y)), 4 = EdgeSE3PointXYZ with one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one ParameterCamera
-  // (offset + Kcam; beside type 2, bound by pg_set_landmark_camera_edges), 11 = EdgeSim3ProjectXYZ (beside type 10, landmarks (x, y, z),
-  // one (fx, fy, cx, cy) per entry of the pose table; bound by pg_set_sim3_project_edges), 13 = EdgeProjectP2MC, 14 =
-  // EdgeProjectP2SC (beside type 12 = the VertexCam table, whose pose-pose set holds zero edges; landmarks (x, y, z), one (fx, fy,
-  // cx, cy, baseline) per entry of the pose table; bound by pg_set_cam_project_edges).  Vertex 0 of an observation
-  // is the pose (index vp into `poses`), vertex 1 the landmark (index vl into `points`); points.hidx[v] is the landmark's index in
-  // the whole system (num_poses + its landmark number) or -1 when it is fixed.  pg_linearize fills the own_* arrays of both
-  // sets, pg_update moves both estimate arrays, push / pop / discard_top treat them as one level.
+  // Pose-graph front end: ONE table of slots beside the two estimate tables `poses` and `points`.  Every slot holds one edge set
+  // (or one group of three) bound by its entry; pg_linearize fills the own_* arrays of every bound set, pg_update moves both
+  // estimate tables, push / pop / discard_top treat them as one level.  The sets other than the pose-pose and the landmark set own
+  // no vertices: nothing but pg_linearize knows of them.  Validate, then commit: a later call of an entry replaces what its slot
+  // held; n = 0 is legal where the entry says so.
   // Schur on (landmarks marginalised) is the configuration the front end is meant for.  With do_schur = 0 and landmarks in the
   // structure the solver does what it does for any such system: H and b are assembled in full (Hpp, Hpl, Hll, b_p, b_l), solve()
   // factorises Hpp ALONE and writes x_p = Hpp^-1 b_p (what BlockSolver hands its linear solver without Schur, and what
   // OracleSolver(schur=False) computes); the landmark part of x keeps the zeros of build_structure, so pg_update leaves the
   // landmarks where they are.  The front end adds nothing of its own to that path.
-  struct PgFrontEnd {
-    int set = -1, type = 0;
-    DevBuf<int> vi, vj;
-    std::vector<int> h_vi, h_vj;   // host copies: index validation (pg_validate)
+  enum PgSlotId : int {
+    // The pose-pose set every other slot stands beside (pg_set_edges): type 1 = EdgeSE2 over (x, y, theta), 2 = EdgeSE3 over
+    // isometries T[12], 10 = EdgeSim3 over VertexSim3Expmap (qx, qy, qz, qw, tx, ty, tz, s) -- no prior set and no landmark set
+    // other than type 11 beside it --, 12 = the VertexCam table (tx, ty, tz, qx, qy, qz, qw), whose set holds zero edges -- no
+    // prior set and no landmark set other than 13 / 14 beside it.  v[0] / v[1] index `poses`, meas [n][stride of the type].
+    kPose,
+    // ONE set of pose-landmark observations: type 3 = EdgeSE2PointXY (beside type 1, landmarks (x, y)), 4 = EdgeSE3PointXYZ with
+    // one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one
+    // ParameterCamera (offset + Kcam; beside type 2, pg_set_landmark_camera_edges), 11 = EdgeSim3ProjectXYZ (beside type 10, one
+    // (fx, fy, cx, cy) per entry of the pose table; pg_set_sim3_project_edges), 13 = EdgeProjectP2MC, 14 = EdgeProjectP2SC
+    // (beside type 12, one (fx, fy, cx, cy, baseline) per entry of the pose table; pg_set_cam_project_edges).  Vertex 0 of an
+    // observation is the pose (v[0] into `poses`), vertex 1 the landmark (v[1] into `points`); points.hidx[v] is the landmark's
+    // index in the whole system (num_poses + its landmark number) or -1 when it is fixed.
+    kLandmark,
+    // ONE unary set of pose priors, independent of the landmark slot: type 7 = EdgeSE2Prior (measurement (x, y, theta)), 8 =
+    // EdgeSE2XYPrior ((x, y)) beside type 1, 9 = EdgeSE3Prior (isometry [12], one ParameterSE3Offset pr_offset) beside type 2.
+    // v[0] indexes `poses`; pg_linearize fills the set's own_J0 / own_err.
+    kPrior,
+    // ONE second pose-pose set of Edge_V_V_GICP (type 15) beside a type-2 set: v[0] / v[1] index `poses`, meas [n][6] = (pos0,
+    // pos1), gicp_cov [n][18] = (cov0, cov1) with gicp_plpl (plane-to-plane: pg_linearize rewrites the set's own_omega on every
+    // evaluation) (pg_gicp.inc).
+    kGicp,
+    // Beside a type-12 pose set, each in a slot of its own and independent of the projection set: EdgeSBACam (type 16, error 6;
+    // meas [n][7] = the INVERSE measurements, computed once at binding) and EdgeSBAScale (type 17, error 1; meas [n]).  v[0] /
+    // v[1] index `poses` (pg_sbacam_edge.inc).
+    kCam,
+    kScale,
+    // ONE second pose-pose set of sensor-offset edges: type 18 = EdgeSE2Offset beside type 1 (measurements and offsets (x, y,
+    // theta)), 19 = EdgeSE3Offset beside type 2 (isometries [12]).  v[0] / v[1] index `poses`, opf / opt the rows of off_table
+    // [off_params][3 | 12] (the sensor frame on vertex 0 / vertex 1) (pg_offset.inc).
+    kOffset,
+    // ONE set of bearing-only observations EdgeSE2PointXYBearing (type 20, error 1) beside type 1, with or without a type-3 set in
+    // the landmark slot: v[0] indexes `poses`, v[1] the SAME landmark table `points`, meas [n] the measured angles
+    // (pg_bearing.inc).  The estimates, the update and push / pop are those of the landmark slot.
+    kBearing,
+    // ONE group of EdgeSE2SensorCalib (type 21, error 3, THREE vertices: pose, pose, laser offset -- all rows of `poses`) beside
+    // type 1: the three binary sets (i, j), (i, l), (j, l) of g2ohip_set_edge_set_parts are bound and released together and share
+    // Jacobians, information and errors (alias_triple).  v[0] / v[1] / v[2] index `poses`, meas [n][3] = (x, y, theta)
+    // (pg_calib.inc).
+    kCalib,
+    // ONE group of EdgeSE2OdomDifferentialCalib (type 22, error 3, THREE vertices: pose, pose, VertexOdomDifferentialParams -- all
+    // rows of `poses`) beside type 1, independent of the type-21 slot: the binary sets (i, j), (i, p), (j, p) share buffers as
+    // the type-21 group's do.  meas [n][3] = (vl, vr, dt) (pg_odom_calib.inc).  While the group is bound the rows named by v[2]
+    // are ADDITIVE rows: od_rows lists them (sorted, unique), od_mask [poses.n] marks them on the device for
+    // pg_se2_update_additive_kernel.
+    kOdom,
+    kPgSlots
+  };
+  struct PgSlot {
+    int set[3] = {-1, -1, -1};   // single-set slots use set[0]; groups use (ij, il | ip, jl | jp)
+    int type = 0;                // the edge type bound (PgSlotId above)
+    std::vector<int> h_v[3];     // host copies of the index arrays: validation against the estimate tables
+    DevBuf<int> v[3];
     DevBuf<double> meas;
-    EstimateTable poses;           // (x, y, theta), T[12] or -- type 10 = EdgeSim3 over VertexSim3Expmap: no prior set and no
-                                   // landmark set other than type 11 beside it -- (qx, qy, qz, qw, tx, ty, tz, s) per pose
-                                   // or -- type 12 = VertexCam: no prior set and no landmark set other than 13 / 14 beside it
-                                   // -- (tx, ty, tz, qx, qy, qz, qw) per camera
+    bool bound() const { return set[0] >= 0; }
+    bool holds(int id) const { return id >= 0 && (id == set[0] || id == set[1] || id == set[2]); }
+    size_t n() const { return h_v[0].size(); }   // edges at binding
+  };
+  // what the loops over the table need to know of a slot
+  struct PgSlotDesc {
+    const char* words;    // the slot in messages
+    const char* entry;    // the entry that binds it ("... has grown since <entry>: call <entry> again")
+    int sets, arrays;     // sets (1, or the 3 of a group) and index arrays
+    bool points[3];       // per index array: a row of `points` (else of `poses`)
+    bool clears_leaving;  // a set another call replaces in the slot gives up the data the device wrote for it (the entries of the
+                          // four oldest slots never did, and their replaced sets keep theirs)
+  };
+  static constexpr PgSlotDesc kPgSlotDesc[kPgSlots] = {
+      {"the pose-pose set", "pg_set_edges", 1, 2, {false, false, false}, false},
+      {"the landmark set", "pg_set_landmark_edges", 1, 2, {false, true, false}, false},
+      {"the prior set", "pg_set_prior_edges", 1, 1, {false, false, false}, false},
+      {"the GICP set", "pg_set_gicp_edges", 1, 2, {false, false, false}, false},
+      {"the EdgeSBACam set", "pg_set_cam_edges", 1, 2, {false, false, false}, true},
+      {"the EdgeSBAScale set", "pg_set_cam_edges", 1, 2, {false, false, false}, true},
+      {"the sensor-offset set", "pg_set_offset_edges", 1, 2, {false, false, false}, true},
+      {"the bearing set", "pg_set_bearing_edges", 1, 2, {false, true, false}, true},
+      {"the EdgeSE2SensorCalib group", "pg_set_sensor_calib_edges", 3, 3, {false, false, false}, true},
+      {"the EdgeSE2OdomDifferentialCalib group", "pg_set_odom_calib_edges", 3, 3, {false, false, false}, true},
+  };
+  struct PgFrontEnd {
+    PgSlot slot[kPgSlots];
+    int pose_type() const { return slot[kPose].type; }   // 0: no pose-pose set bound
+    EstimateTable poses;           // one row per pose of the bound pose type (PgSlotId::kPose)
+    EstimateTable points;          // (x, y) or (x, y, z) per landmark
     bool fix_scale = false;        // VertexSim3Expmap::_fix_scale of the whole table (pg_set_sim3_fix_scale)
     bool has_backup = false;
     bool err_valid = false, jac_valid = false;
-    int lm_set = -1, lm_type = 0;
-    DevBuf<int> vp, vl;
-    std::vector<int> h_vp, h_vl;   // host copies: index validation (pg_validate_landmarks)
-    DevBuf<double> lm_meas;
-    EstimateTable points;          // (x, y) or (x, y, z) per landmark
+    // the landmark slot
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
     double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
     DevBuf<double> cam_k;          // type 11: (fx, fy, cx, cy) of every entry of `poses` (VertexSim3Expmap::_focal_length,
     int n_cams = 0;                // _principle_point), n_cams entries: == poses.n whenever both are bound; types 13 / 14: (fx,
                                    // fy, cx, cy, baseline) (SBACam::Kcam, baseline)
-    // ONE unary set of pose priors `pr_set`, independent of the landmark slot: pr_type 7 = EdgeSE2Prior (measurement (x, y, theta)),
-    // 8 = EdgeSE2XYPrior ((x, y)) beside type 1, 9 = EdgeSE3Prior (isometry [12], one ParameterSE3Offset pr_offset) beside type 2.
-    // vq indexes `poses`.  Priors own no vertices: pg_linearize fills the set's own_J0 / own_err, nothing else knows of them.
-    int pr_set = -1, pr_type = 0;
-    DevBuf<int> vq;
-    std::vector<int> h_vq;         // host copy: index validation (pg_validate_priors)
-    DevBuf<double> pr_meas;
-    double pr_offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    // ONE second pose-pose set `gicp_set` of Edge_V_V_GICP (type 15) beside a type-2 set, independent of the landmark and prior
-    // slots: gi / gj index `poses`, gicp_meas [n][6] = (pos0, pos1), gicp_cov [n][18] = (cov0, cov1) with gicp_plpl (plane-to-plane:
-    // pg_linearize rewrites the set's own_omega on every evaluation).  The set owns no vertices either.
-    int gicp_set = -1;
+    double pr_offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // the prior slot: ParameterSE3Offset of a type-9 set
+    DevBuf<double> gicp_cov;       // the GICP slot
     bool gicp_plpl = false;
-    DevBuf<int> gi, gj;
-    std::vector<int> h_gi, h_gj;   // host copies: index validation (pg_validate)
-    DevBuf<double> gicp_meas, gicp_cov;
-    // ONE second pose-pose set `off_set` of sensor-offset edges, independent of the landmark, prior and GICP slots: off_type 18 =
-    // EdgeSE2Offset beside type 1 (measurements and offsets (x, y, theta)), 19 = EdgeSE3Offset beside type 2 (isometries [12]).
-    // oi / oj index `poses`, opf / opt the rows of off_table [off_params][3 | 12] (the sensor frame on vertex 0 / vertex 1).
-    // The set owns no vertices either (pg_offset.inc).
-    int off_set = -1, off_type = 0, off_params = 0;
-    DevBuf<int> oi, oj, opf, opt;
-    std::vector<int> h_oi, h_oj;   // host copies: index validation (pg_validate)
-    DevBuf<double> off_meas, off_table;
-    // ONE set `br_set` of bearing-only observations EdgeSE2PointXYBearing (type 20, error 1) beside type 1, in a slot of its own
-    // with or without a type-3 set in the landmark slot: bp indexes `poses`, bl the SAME landmark table `points`, br_meas [n] the
-    // measured angles (pg_bearing.inc).  The estimates, the update and push / pop are those of the landmark half.
-    int br_set = -1;
-    DevBuf<int> bp, bl;
-    std::vector<int> h_bp, h_bl;   // host copies: index validation (pg_validate_landmarks)
-    DevBuf<double> br_meas;
-    // ONE group of EdgeSE2SensorCalib (type 21, error 3, THREE vertices: pose, pose, laser offset -- all rows of `poses`) beside
-    // type 1, in a slot of its own: the three binary sets cal_ij (i, j), cal_il (i, l), cal_jl (j, l) of
-    // g2ohip_set_edge_set_parts are bound and released together and share Jacobians, information and errors: J_i / J_j /
-    // information / errors live in cal_ij's buffers, J_l in cal_jl's own_J1, every other pointer of the three aliases one of
-    // those (pg_cal_alias).  cal_vi / cal_vj / cal_vl index `poses`, cal_meas [n][3] = (x, y, theta) (pg_calib.inc).
-    int cal_ij = -1, cal_il = -1, cal_jl = -1;
-    DevBuf<int> cal_vi, cal_vj, cal_vl;
-    std::vector<int> h_cal_vi, h_cal_vj, h_cal_vl;   // host copies: index validation (pg_validate)
-    DevBuf<double> cal_meas;
-    bool in_cal(int set) const { return set >= 0 && (set == cal_ij || set == cal_il || set == cal_jl); }
-    // ONE group of EdgeSE2OdomDifferentialCalib (type 22, error 3, THREE vertices: pose, pose, VertexOdomDifferentialParams -- all
-    // rows of `poses`) beside type 1, in the odometry-calibration slot, independent of the type-21 slot: the binary sets od_ij (i, j),
-    // od_ip (i, p), od_jp (j, p) share buffers as the type-21 group's do (pg_od_alias).  od_vi / od_vj / od_vp index `poses`,
-    // od_meas [n][3] = (vl, vr, dt) (pg_odom_calib.inc).  While the group is bound the rows named by od_vp are ADDITIVE rows:
-    // od_rows lists them (sorted, unique), od_mask [poses.n] marks them on the device for pg_se2_update_additive_kernel.
-    int od_ij = -1, od_ip = -1, od_jp = -1;
-    DevBuf<int> od_vi, od_vj, od_vp, od_mask;
-    std::vector<int> h_od_vi, h_od_vj, h_od_vp, od_rows;
-    DevBuf<double> od_meas;
-    bool in_od(int set) const { return set >= 0 && (set == od_ij || set == od_ip || set == od_jp); }
-    // Beside a type-12 pose set, each in a slot of its own and independent of the projection slot: `cam_set` of EdgeSBACam (type
-    // 16, error 6; cam_zinv [n][7] = the INVERSE measurements, computed once at binding) and `scale_set` of EdgeSBAScale (type 17,
-    // error 1; scale_meas [n]).  ci / cj and si / sj index `poses`.  The sets own no vertices.
-    int cam_set = -1, scale_set = -1;
-    DevBuf<int> ci, cj, si, sj;
-    std::vector<int> h_ci, h_cj, h_si, h_sj;   // host copies: index validation (pg_validate)
-    DevBuf<double> cam_zinv, scale_meas;
+    DevBuf<int> opf, opt;          // the sensor-offset slot
+    DevBuf<double> off_table;
+    int off_params = 0;
+    std::vector<int> od_rows;      // the odometry-calibration slot
+    DevBuf<int> od_mask;
   } pg_;
   EventTimer tq_, ts_, tn_, tl_, tb_, tfe_;
   void require_structure() const;

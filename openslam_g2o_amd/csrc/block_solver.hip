@@ -2589,15 +2589,15 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     es.J0 = es.J1 = es.omega = es.err = nullptr;
     es.external = false;
     // a device front end bound to the set holds vi / vj / measurements and the own_* arrays for the OLD edge count:
-    // drop the binding (pg_set_edges / ba_set_edges again after growth), pg_linearize refuses until then; a grown prior set
-    // keeps the rest of the binding and is refused by its edge count (pg_set_prior_edges again), and so is a grown GICP set
-    // (pg_set_gicp_edges again), a grown EdgeSBACam / EdgeSBAScale set (pg_set_cam_edges again), a grown sensor-offset set
-    // (pg_set_offset_edges again) or a grown bearing set (pg_set_bearing_edges again); an EdgeSE2SensorCalib group goes as one
-    // when one of its three sets grows (pg_set_sensor_calib_edges again), its sets keep no pointer into each other's buffers
-    if (pg_.in_cal(set)) pg_cal_release();
-    if (pg_.in_od(set)) pg_od_release();   // (an EdgeSE2OdomDifferentialCalib group likewise: pg_set_odom_calib_edges again)
-    if (set == pg_.set || set == pg_.lm_set) {
-      pg_cal_release();
+    // the pose-pose or the landmark set: the whole binding goes (pg_set_edges / ba_set_edges again after growth), pg_linearize
+    // refuses until then; a group goes as one when one of its three sets grows, and its sets keep no pointer into each other's
+    // buffers (its entry again); the set of any other slot keeps the rest of the binding and is refused by its edge count in
+    // pg_linearize until its entry is called again
+    const int slot = pg_slot_of(set);
+    if (slot == kCalib) pg_release_group(kCalib);
+    if (slot == kOdom) pg_od_release();
+    if (slot == kPose || slot == kLandmark) {
+      pg_release_group(kCalib);
       pg_od_release();
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -3317,9 +3317,8 @@ void BlockSolver::set_edge_data(int set, const double* J0, const double* J1, con
   }
   // (a set bound to a device front end holds that front end's evaluations: host arrays uploaded into it replace them, the cached
   // err_valid / jac_valid flags must go -- the full invalidation)
-  const bool front_end_set = set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || set == pg_.set || set == pg_.lm_set || set == pg_.pr_set || set == pg_.gicp_set ||
-                             set == pg_.cam_set || set == pg_.scale_set || set == pg_.off_set || set == pg_.br_set || pg_.in_cal(set) ||
-                             pg_.in_od(set);
+  const bool front_end_set =
+      set == ba_.set || set == ba_.pose_set || (ba_.psi && (set == ba_.psi_pa || set == ba_.psi_ca)) || pg_slot_of(set) >= 0;
   if (had && !on_device && !front_end_set && pJ0 == es.J0 && pJ1 == es.J1 && pO == es.omega && pE == es.err) chi2_valid_ = false;
   else invalidate_graphs();
   es.has_data = true;
@@ -5555,7 +5554,7 @@ void BlockSolver::ba_set_inverse_depth_edges(int set_pp, int set_pa, int set_ca,
   es.own_J1.alloc(n * 12);
   es.own_err.alloc(n * 2);
   ec.own_J1.alloc(n * 12);
-  ba_psi_alias();
+  alias_triple(ids);
   for (EdgeSet* e : {&es, &ea, &ec}) {
     e->external = false;
     e->has_data = false;   // becomes valid with the first ba_linearize
@@ -5565,12 +5564,11 @@ void BlockSolver::ba_set_inverse_depth_edges(int set_pp, int set_pa, int set_ca,
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
-// the pointers of the three sets of an inverse-depth binding onto the buffers two of them own; a pointer that had to be repaired
-// (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences
-void BlockSolver::ba_psi_alias() {
-  EdgeSet &es = *sets_[ba_.set], &ea = *sets_[ba_.psi_pa], &ec = *sets_[ba_.psi_ca];
-  const double *jp = es.own_J0.p, *jc = es.own_J1.p, *ja = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
-  const double* want[3][2] = {{jp, jc}, {jp, ja}, {jc, ja}};
+// the pointers of three sets that stand for one three-vertex edge onto the buffers two of them own (block_solver.h)
+void BlockSolver::alias_triple(const int ids[3]) {
+  EdgeSet &es = *sets_[ids[0]], &ea = *sets_[ids[1]], &ec = *sets_[ids[2]];
+  const double *ja = es.own_J0.p, *jb = es.own_J1.p, *jc = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
+  const double* want[3][2] = {{ja, jb}, {ja, jc}, {jb, jc}};
   EdgeSet* g[3] = {&es, &ea, &ec};
   bool changed = false;
   for (int i = 0; i < 3; ++i) {
@@ -5585,16 +5583,21 @@ void BlockSolver::ba_psi_alias() {
   if (changed) drop_graph_segments();
 }
 
-// an inverse-depth binding leaves the projection slot: its sets keep no device-written data and no pointer into each other's buffers
-// (set_edge_data is their next source; build_system refuses them until then, unless they are empty)
-void BlockSolver::ba_psi_release() {
-  if (!ba_.psi) return;
-  for (int id : {ba_.set, ba_.psi_pa, ba_.psi_ca}) {
+void BlockSolver::release_triple(const int ids[3]) {
+  for (int q = 0; q < 3; ++q) {
+    const int id = ids[q];
     if (id < 0 || id >= (int)sets_.size()) continue;
     EdgeSet& e = *sets_[id];
     e.has_data = e.has_err = false;
     e.J0 = e.J1 = e.omega = e.err = nullptr;
   }
+}
+
+// an inverse-depth binding leaves the projection slot, with its anchors
+void BlockSolver::ba_psi_release() {
+  if (!ba_.psi) return;
+  const int ids[3] = {ba_.set, ba_.psi_pa, ba_.psi_ca};
+  release_triple(ids);
   ba_.psi = false;
   ba_.psi_pa = ba_.psi_ca = -1;
   ba_.anchor_v.release();
@@ -5853,7 +5856,10 @@ void BlockSolver::ba_linearize(bool jacobians) {
     if (jacobians && ep) ep->has_data = true;
     return;
   }
-  if (ba_.psi) ba_psi_alias();   // (before err_valid / jac_valid are set: a repaired pointer drops the captured launch sequences)
+  if (ba_.psi) {   // (before err_valid / jac_valid are set: a repaired pointer drops the captured launch sequences)
+    const int ids[3] = {ba_.set, ba_.psi_pa, ba_.psi_ca};
+    alias_triple(ids);
+  }
   if (need_jac && (es.own_J0.n < (size_t)es.n * es.d * 3 || es.own_J1.n < (size_t)es.n * es.d * 6)) {   // (left out by ba_set_edges on the fused path)
     es.own_J0.alloc((size_t)es.n * es.d * 3);
     es.own_J1.alloc((size_t)es.n * es.d * 6);
@@ -5987,10 +5993,127 @@ static void pg_validate_cams(const char* who, const double* v, size_t n) {
   }
 }
 
-void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
+// ---- the table of slots: what the entries below share, each written once (block_solver.h) ----------------------------------
+constexpr BlockSolver::PgSlotDesc BlockSolver::kPgSlotDesc[BlockSolver::kPgSlots];
+
+// the pose-set type an edge type stands beside, and that pose type in words
+static int pg_pose_type_beside(int edge_type) {
+  switch (edge_type) {
+    case 3: case 7: case 8: case 18: case 20: case 21: case 22: return 1;
+    case 4: case 5: case 6: case 9: case 15: case 19: return 2;
+    case 11: return 10;
+    default: return 12;   // 13, 14, 16, 17
+  }
+}
+static const char* pg_edge_type_words(int edge_type) {
+  static const char* const words[] = {"EdgeSE2PointXY (3)", "EdgeSE3PointXYZ (4)", "EdgeSE3PointXYZDepth (5)", "EdgeSE3PointXYZDisparity (6)",
+                                      "EdgeSE2Prior (7)", "EdgeSE2XYPrior (8)", "EdgeSE3Prior (9)", "EdgeSim3 (10)", "EdgeSim3ProjectXYZ (11)",
+                                      "VertexCam (12)", "EdgeProjectP2MC (13)", "EdgeProjectP2SC (14)", "Edge_V_V_GICP (15)", "EdgeSBACam (16)",
+                                      "EdgeSBAScale (17)", "EdgeSE2Offset (18)", "EdgeSE3Offset (19)", "EdgeSE2PointXYBearing (20)",
+                                      "EdgeSE2SensorCalib (21)", "EdgeSE2OdomDifferentialCalib (22)"};
+  return edge_type >= 3 && edge_type <= 22 ? words[edge_type - 3] : "?";
+}
+static const char* pg_pose_type_words(int type) {
+  return type == 1 ? "an EdgeSE2 pose set (1)" : type == 2 ? "an EdgeSE3 pose set (2)" : type == 10 ? "an EdgeSim3 pose set (10)" : "a VertexCam set (12)";
+}
+
+int BlockSolver::pg_slot_of(int set) const {
+  for (int k = 0; k < kPgSlots; ++k)
+    if (pg_.slot[k].holds(set)) return k;
+  return -1;
+}
+
+void BlockSolver::pg_begin_bind(const char* who, PgSlotId slot, std::initializer_list<int> sets) {
   invalidate_graphs();
   require_structure();
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  const std::string w(who);
+  if (slot != kPose && !pg_.slot[kPose].bound())
+    throw StateFailure(w + ": call pg_set_edges first (the pose set " + kPgSlotDesc[slot].words + " stands beside; it may be empty)");
+  for (int id : sets)
+    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  for (int id : sets) {
+    const int owner = pg_slot_of(id);
+    if (owner >= 0 && owner != slot)
+      throw ArgFailure(w + ": set " + std::to_string(id) + " is bound " + (kPgSlotDesc[owner].sets == 3 ? "in " : "as ") + kPgSlotDesc[owner].words);
+  }
+}
+
+void BlockSolver::pg_commit(PgSlotId slot, std::initializer_list<int> sets, int type, std::initializer_list<const int*> idx, size_t n,
+                            const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info) {
+  const PgSlotDesc& ds = kPgSlotDesc[slot];
+  PgSlot& sl = pg_.slot[slot];
+  if (ds.sets == 3) {
+    pg_release_group(slot);
+  } else if (ds.clears_leaving && sl.bound() && sl.set[0] != *sets.begin()) {   // set_edge_data is the next source of the set that leaves
+    EdgeSet& old = *sets_[sl.set[0]];
+    old.has_data = old.has_err = false;
+  }
+  std::copy(sets.begin(), sets.end(), sl.set);
+  sl.type = type;
+  int a = 0;
+  for (const int* v : idx) {
+    sl.h_v[a].assign(v, v + n);
+    sl.v[a++].upload(v, n, st_);
+  }
+  sl.meas.upload(meas, n * meas_stride, st_);
+  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
+  chi2_valid_ = false;
+  EdgeSet& es = *sets_[sl.set[0]];
+  const size_t sd = (size_t)d;
+  es.own_omega.upload(info, n * sd * sd, st_);
+  es.own_J0.alloc(n * sd * d0);
+  if (d1 > 0) es.own_J1.alloc(n * sd * d1);
+  es.own_err.alloc(n * sd);
+  if (ds.sets == 3) {
+    sets_[sl.set[2]]->own_J1.alloc(n * sd * d1);
+    alias_triple(sl.set);
+  } else {
+    es.J0 = es.own_J0.p; es.J1 = d1 > 0 ? es.own_J1.p : nullptr; es.omega = es.own_omega.p; es.err = es.own_err.p;
+  }
+  for (int q = 0; q < ds.sets; ++q) {
+    EdgeSet& e = *sets_[sl.set[q]];
+    e.external = false;    // (the pointers are the set's own)
+    e.has_data = false;    // becomes valid with the first pg_linearize
+    e.has_err = false;
+  }
+  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void BlockSolver::pg_validate_slot(PgSlotId slot, const int* hidx, int nv, const int* pt_hidx, int np) const {
+  const PgSlotDesc& ds = kPgSlotDesc[slot];
+  const PgSlot& sl = pg_.slot[slot];
+  const int *a = sl.h_v[0].data(), *b = sl.h_v[1].data(), *c = sl.h_v[2].data();
+  if (ds.sets == 3) {   // (i, j), (i, x), (j, x)
+    pg_validate(*sets_[sl.set[0]], a, b, sl.n(), hidx, nv);
+    pg_validate(*sets_[sl.set[1]], a, c, sl.n(), hidx, nv);
+    pg_validate(*sets_[sl.set[2]], b, c, sl.n(), hidx, nv);
+  } else if (ds.arrays == 1) {
+    pg_validate_priors(*sets_[sl.set[0]], a, sl.n(), hidx, nv);
+  } else if (ds.points[1]) {
+    pg_validate_landmarks(*sets_[sl.set[0]], a, b, sl.n(), hidx, nv, pt_hidx, np);
+  } else {
+    pg_validate(*sets_[sl.set[0]], a, b, sl.n(), hidx, nv);
+  }
+}
+
+void BlockSolver::pg_release_group(PgSlotId slot) {
+  PgSlot& sl = pg_.slot[slot];
+  if (!sl.bound()) return;
+  release_triple(sl.set);
+  sl.set[0] = sl.set[1] = sl.set[2] = -1;
+  for (std::vector<int>& h : sl.h_v) h.clear();
+  pg_.err_valid = pg_.jac_valid = false;
+}
+
+void BlockSolver::pg_od_release() {
+  if (!pg_.slot[kOdom].bound()) return;
+  pg_release_group(kOdom);
+  pg_.od_rows.clear();
+  drop_graph_segments();
+}
+
+void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
+  pg_begin_bind("pg_set_edges", kPose, {set});
   if (type != 1 && type != 2 && type != 10 && type != 12)
     throw ArgFailure("pg_set_edges: type must be 1 (EdgeSE2), 2 (EdgeSE3), 10 (EdgeSim3) or 12 (the VertexCam table)");
   EdgeSet& es = *sets_[set];
@@ -5999,44 +6122,19 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
   if (type == 12 && (p_ != 6 || l_ != 3)) throw ArgFailure("pg_set_edges: the VertexCam table (12) needs a solver of (pose, landmark) dimensions (6, 3)");
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d) throw ArgFailure("pg_set_edges: the set must be a binary pose-pose set of matching dimension");
   const size_t n = (size_t)es.n, ms = (size_t)pg_pose_stride(type);
-  if (type != 2 && pg_.gicp_set >= 0)
-    throw ArgFailure("pg_set_edges: an Edge_V_V_GICP set (15) is bound: it stands beside an EdgeSE3 pose set (2) only");
-  if (set == pg_.gicp_set) throw ArgFailure("pg_set_edges: the set is bound as the GICP set");
-  if (type != 12 && (pg_.cam_set >= 0 || pg_.scale_set >= 0))
-    throw ArgFailure("pg_set_edges: an EdgeSBACam (16) or EdgeSBAScale (17) set is bound: it stands beside a VertexCam set (12) only");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (pg_.off_set >= 0 && type != pg_.off_type - 17)
-    throw ArgFailure("pg_set_edges: a sensor-offset set is bound: EdgeSE2Offset (18) stands beside an EdgeSE2 pose set (1) only, EdgeSE3Offset (19) beside EdgeSE3 (2)");
-  if (set == pg_.off_set) throw ArgFailure("pg_set_edges: the set is bound as the sensor-offset set");
-  if (pg_.br_set >= 0 && type != 1)
-    throw ArgFailure("pg_set_edges: an EdgeSE2PointXYBearing set (20) is bound: it stands beside an EdgeSE2 pose set (1) only");
-  if (set == pg_.br_set) throw ArgFailure("pg_set_edges: the set is bound as the bearing set");
-  if (pg_.cal_ij >= 0 && type != 1)
-    throw ArgFailure("pg_set_edges: an EdgeSE2SensorCalib group (21) is bound: it stands beside an EdgeSE2 pose set (1) only");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.od_ij >= 0 && type != 1)
-    throw ArgFailure("pg_set_edges: an EdgeSE2OdomDifferentialCalib group (22) is bound: it stands beside an EdgeSE2 pose set (1) only");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
+  for (int k = kPose + 1; k < kPgSlots; ++k) {   // what is bound beside the pose set fixes its type
+    const PgSlot& sl = pg_.slot[k];
+    if (sl.bound() && pg_pose_type_beside(sl.type) != type)
+      throw ArgFailure(std::string("pg_set_edges: ") + kPgSlotDesc[k].words + " is bound with " + pg_edge_type_words(sl.type) +
+                       " edges: it stands beside " + pg_pose_type_words(pg_pose_type_beside(sl.type)) + " only");
+  }
   if (type == 12 && n > 0)
     throw ArgFailure("pg_set_edges: a VertexCam set (12) must hold zero edges: EdgeSBACam (16) and EdgeSBAScale (17) are bound with pg_set_cam_edges, each as a set of its own beside it");
   // (a type-10 set may be empty -- keyframes and points with no Sim3 constraint between keyframes -- and then has no arrays; a
   // type-12 set is always empty: it is the anchor of the camera table that the landmark slot needs)
   if ((n > 0 || (type != 10 && type != 12)) && (!vi || !vj || !meas || !info)) throw ArgFailure("pg_set_edges: null array");
   pg_refuse_additive("pg_set_edges", pg_.od_rows, {{vi, n}, {vj, n}});
-  if (type == 12) {
-    // beside a VertexCam table stands an EdgeProjectP2MC (13) or EdgeProjectP2SC (14) landmark set or nothing
-    if ((pg_.lm_set >= 0 && !pg_cam_landmark(pg_.lm_type)) || pg_.pr_set >= 0)
-      throw ArgFailure("pg_set_edges: a VertexCam set (12) cannot be bound beside a prior set or a landmark set other than EdgeProjectP2MC (13) / EdgeProjectP2SC (14)");
-  } else if (pg_.lm_set >= 0 && pg_cam_landmark(pg_.lm_type)) {
-    throw ArgFailure("pg_set_edges: an EdgeProjectP2MC / EdgeProjectP2SC landmark set (13 / 14) is bound: it stands beside a VertexCam set (12) only");
-  } else if (type == 10) {
-    // beside a Sim3 set stands an EdgeSim3ProjectXYZ landmark set (11) or nothing: no other landmark, camera or prior set
-    if ((pg_.lm_set >= 0 && pg_.lm_type != 11) || pg_.pr_set >= 0)
-      throw ArgFailure("pg_set_edges: EdgeSim3 (10) cannot be bound beside a prior set or a landmark set other than EdgeSim3ProjectXYZ (11)");
-    pg_validate_sim3("pg_set_edges", meas, n);
-  } else if (pg_.lm_set >= 0 && pg_.lm_type == 11) {
-    throw ArgFailure("pg_set_edges: an EdgeSim3ProjectXYZ landmark set (11) is bound: it stands beside EdgeSim3 (10) only");
-  }
+  if (type == 10) pg_validate_sim3("pg_set_edges", meas, n);
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   // the committed pose table belongs to the committed type: a binding of another stride starts without estimates
   const bool keep_table = pg_.poses.n > 0 && pg_.poses.stride == (int)ms;
@@ -6045,22 +6143,7 @@ void BlockSolver::pg_set_edges(int set, int type, const int* vi, const int* vj, 
     pg_.poses.n = 0;
     pg_.has_backup = false;
   }
-  pg_.set = set;
-  pg_.type = type;
-  pg_.err_valid = pg_.jac_valid = false;
-  pg_.h_vi.assign(vi, vi + n);
-  pg_.h_vj.assign(vj, vj + n);
-  pg_.vi.upload(vi, n, st_);
-  pg_.vj.upload(vj, n, st_);
-  pg_.meas.upload(meas, n * ms, st_);
-  es.own_omega.upload(info, n * d * d, st_);
-  es.own_J0.alloc(n * d * d);
-  es.own_J1.alloc(n * d * d);
-  es.own_err.alloc(n * d);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kPose, {set}, type, {vi, vj}, n, meas, ms, d, d, d, info);
 }
 
 // VertexSim3Expmap::_fix_scale for the whole pose table (types_seven_dof_expmap.h:60-61, 78): the sigma entry of every step is
@@ -6074,38 +6157,28 @@ void BlockSolver::pg_set_sim3_fix_scale(bool fix_scale) {
 }
 
 void BlockSolver::pg_set_estimates(int nv, const double* poses, const int* hidx) {
-  if (pg_.type == 0) throw StateFailure("pg_set_estimates: call pg_set_edges first");
+  const int type = pg_.pose_type();
+  if (type == 0) throw StateFailure("pg_set_estimates: call pg_set_edges first");
   if (nv <= 0 || !poses || !hidx) throw ArgFailure("pg_set_estimates: bad arguments");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const int ps = pg_pose_stride(pg_.type);
-  if (pg_.type == 10) pg_validate_sim3("pg_set_estimates", poses, (size_t)nv);
-  if (pg_.type == 12) pg_validate_cams("pg_set_estimates", poses, (size_t)nv);
+  const int ps = pg_pose_stride(type);
+  if (type == 10) pg_validate_sim3("pg_set_estimates", poses, (size_t)nv);
+  if (type == 12) pg_validate_cams("pg_set_estimates", poses, (size_t)nv);
   const bool same = pg_.poses.same(nv, ps, hidx);   // (same tables, new values: see ba_set_estimates)
   if (!same) {
-    pg_validate(*sets_[pg_.set], pg_.h_vi.data(), pg_.h_vj.data(), pg_.h_vi.size(), hidx, nv);
-    if (pg_.lm_set >= 0 && (pg_.lm_type == 11 || pg_cam_landmark(pg_.lm_type)) && nv != pg_.n_cams)
+    const PgSlot& lm = pg_.slot[kLandmark];
+    if (lm.bound() && (lm.type == 11 || pg_cam_landmark(lm.type)) && nv != pg_.n_cams)
       throw ArgFailure("pg_set_estimates: " + std::to_string(nv) + " poses, but the projection set was bound with intrinsics of " +
                        std::to_string(pg_.n_cams) + " cameras");
-    if (pg_.lm_set >= 0)
-      pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), hidx, nv, pg_.points.h_hidx.data(),
-                            pg_.points.n);
-    if (pg_.pr_set >= 0) pg_validate_priors(*sets_[pg_.pr_set], pg_.h_vq.data(), pg_.h_vq.size(), hidx, nv);
-    if (pg_.gicp_set >= 0) pg_validate(*sets_[pg_.gicp_set], pg_.h_gi.data(), pg_.h_gj.data(), pg_.h_gi.size(), hidx, nv);
-    if (pg_.cam_set >= 0) pg_validate(*sets_[pg_.cam_set], pg_.h_ci.data(), pg_.h_cj.data(), pg_.h_ci.size(), hidx, nv);
-    if (pg_.scale_set >= 0) pg_validate(*sets_[pg_.scale_set], pg_.h_si.data(), pg_.h_sj.data(), pg_.h_si.size(), hidx, nv);
-    if (pg_.off_set >= 0) pg_validate(*sets_[pg_.off_set], pg_.h_oi.data(), pg_.h_oj.data(), pg_.h_oi.size(), hidx, nv);
-    if (pg_.br_set >= 0)
-      pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), hidx, nv, pg_.points.h_hidx.data(),
-                            pg_.points.n);
-    if (pg_.cal_ij >= 0) pg_validate_calib(pg_.h_cal_vi.data(), pg_.h_cal_vj.data(), pg_.h_cal_vl.data(), pg_.h_cal_vi.size(), hidx, nv);
-    if (pg_.od_ij >= 0) pg_validate_odom_calib(pg_.h_od_vi.data(), pg_.h_od_vj.data(), pg_.h_od_vp.data(), pg_.h_od_vi.size(), hidx, nv);
+    for (int k = 0; k < kPgSlots; ++k)
+      if (pg_.slot[k].bound()) pg_validate_slot((PgSlotId)k, hidx, nv, pg_.points.h_hidx.data(), pg_.points.n);
   }
   pg_.err_valid = pg_.jac_valid = false;
   chi2_valid_ = false;
   pg_.has_backup = false;
   if (same) pg_.poses.set_values(poses, st_);
   else pg_.poses.commit(nv, ps, poses, hidx, st_);
-  if (!same && pg_.od_ij >= 0) pg_od_build_mask();   // (the mask of additive rows has one entry per row of the table)
+  if (!same && pg_.slot[kOdom].bound()) pg_od_build_mask();   // (the mask of additive rows has one entry per row of the table)
   G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
@@ -6118,14 +6191,12 @@ void BlockSolver::pg_get_estimates(double* poses) {
 // VertexPointXY / VertexPointXYZ) -----------------------------------------------------------------------------------------
 void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                         const double* info, const double* offset) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type == 10) throw ArgFailure("pg_set_landmark_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
-  if (pg_.type == 12) throw ArgFailure("pg_set_landmark_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
+  pg_begin_bind("pg_set_landmark_edges", kLandmark, {set});
+  const int pt = pg_.pose_type();
+  if (pt == 10) throw ArgFailure("pg_set_landmark_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
+  if (pt == 12) throw ArgFailure("pg_set_landmark_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
   if (type != 3 && type != 4) throw ArgFailure("pg_set_landmark_edges: type must be 3 (EdgeSE2PointXY) or 4 (EdgeSE3PointXYZ)");
-  if (type != pg_.type + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
+  if (type != pt + 2) throw ArgFailure("pg_set_landmark_edges: EdgeSE2PointXY (3) goes with an EdgeSE2 pose set (1), EdgeSE3PointXYZ (4) with EdgeSE3 (2)");
   if (offset && type != 4) throw ArgFailure("pg_set_landmark_edges: an offset belongs to EdgeSE3PointXYZ (type 4) only");
   pg_bind_landmark_edges("pg_set_landmark_edges", set, type, pose_vertex, point_vertex, meas, info, offset, nullptr);
 }
@@ -6133,14 +6204,12 @@ void BlockSolver::pg_set_landmark_edges(int set, int type, const int* pose_verte
 // EdgeSE3PointXYZDepth (5) / EdgeSE3PointXYZDisparity (6) with ONE ParameterCamera (offset + Kcam) for the whole set
 void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                                const double* info, const double* offset, const double* kcam) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_landmark_camera_edges: call pg_set_edges first (the pose-pose set the landmark set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type == 10) throw ArgFailure("pg_set_landmark_camera_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
-  if (pg_.type == 12) throw ArgFailure("pg_set_landmark_camera_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
+  pg_begin_bind("pg_set_landmark_camera_edges", kLandmark, {set});
+  const int pt = pg_.pose_type();
+  if (pt == 10) throw ArgFailure("pg_set_landmark_camera_edges: no landmark set stands beside an EdgeSim3 pose set (10)");
+  if (pt == 12) throw ArgFailure("pg_set_landmark_camera_edges: beside a VertexCam set (12) stands EdgeProjectP2MC / P2SC only (pg_set_cam_project_edges)");
   if (type != 5 && type != 6) throw ArgFailure("pg_set_landmark_camera_edges: type must be 5 (EdgeSE3PointXYZDepth) or 6 (EdgeSE3PointXYZDisparity)");
-  if (pg_.type != 2) throw ArgFailure("pg_set_landmark_camera_edges: the camera edges go with an EdgeSE3 pose set (2)");
+  if (pt != 2) throw ArgFailure("pg_set_landmark_camera_edges: the camera edges go with an EdgeSE3 pose set (2)");
   if (!kcam) throw ArgFailure("pg_set_landmark_camera_edges: null kcam (fx, fy, cx, cy)");
   for (int i = 0; i < 4; ++i)
     if (!std::isfinite(kcam[i])) throw ArgFailure("pg_set_landmark_camera_edges: non-finite camera intrinsics");
@@ -6153,11 +6222,8 @@ void BlockSolver::pg_set_landmark_camera_edges(int set, int type, const int* pos
 // [n_cams][4] = (fx, fy, cx, cy) -- one row per entry of the pose table (pg_sim3_project.inc)
 void BlockSolver::pg_set_sim3_project_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas,
                                             const double* info, int n_cams, const double* intrinsics) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_sim3_project_edges: call pg_set_edges first (the EdgeSim3 set the landmark set stands beside; it may be empty)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type != 10) throw ArgFailure("pg_set_sim3_project_edges: EdgeSim3ProjectXYZ (11) goes with an EdgeSim3 pose set (10)");
+  pg_begin_bind("pg_set_sim3_project_edges", kLandmark, {set});
+  if (pg_.pose_type() != 10) throw ArgFailure("pg_set_sim3_project_edges: EdgeSim3ProjectXYZ (11) goes with an EdgeSim3 pose set (10)");
   if (n_cams <= 0 || !intrinsics) throw ArgFailure("pg_set_sim3_project_edges: no intrinsics (fx, fy, cx, cy per pose)");
   for (size_t i = 0; i < 4 * (size_t)n_cams; ++i)
     if (!std::isfinite(intrinsics[i])) throw ArgFailure("pg_set_sim3_project_edges: non-finite intrinsics of camera " + std::to_string(i / 4));
@@ -6175,12 +6241,9 @@ void BlockSolver::pg_set_sim3_project_edges(int set, const int* pose_vertex, con
 // baseline) -- one row per entry of the pose table (pg_cam_project.inc)
 void BlockSolver::pg_set_cam_project_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                            const double* info, int n_cams, const double* intrinsics) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_cam_project_edges: call pg_set_edges first (the empty VertexCam set (12) the landmark set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  pg_begin_bind("pg_set_cam_project_edges", kLandmark, {set});
   if (type != 13 && type != 14) throw ArgFailure("pg_set_cam_project_edges: type must be 13 (EdgeProjectP2MC) or 14 (EdgeProjectP2SC)");
-  if (pg_.type != 12) throw ArgFailure("pg_set_cam_project_edges: EdgeProjectP2MC / EdgeProjectP2SC go with a VertexCam set (12)");
+  if (pg_.pose_type() != 12) throw ArgFailure("pg_set_cam_project_edges: EdgeProjectP2MC / EdgeProjectP2SC go with a VertexCam set (12)");
   if (n_cams <= 0 || !intrinsics) throw ArgFailure("pg_set_cam_project_edges: no intrinsics (fx, fy, cx, cy, baseline per camera)");
   for (size_t i = 0; i < 5 * (size_t)n_cams; ++i)
     if (!std::isfinite(intrinsics[i])) throw ArgFailure("pg_set_cam_project_edges: non-finite intrinsics of camera " + std::to_string(i / 5));
@@ -6198,14 +6261,6 @@ void BlockSolver::pg_set_cam_project_edges(int set, int type, const int* pose_ve
 void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
                                          const double* meas, const double* info, const double* offset, const double* kcam, int n_cams) {
   const std::string w(who);
-  if (set == pg_.set) throw ArgFailure(w + ": the set is bound as the pose-pose set");
-  if (set == pg_.pr_set) throw ArgFailure(w + ": the set is bound as the prior set");
-  if (set == pg_.gicp_set) throw ArgFailure(w + ": the set is bound as the GICP set");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure(w + ": the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (set == pg_.off_set) throw ArgFailure(w + ": the set is bound as the sensor-offset set");
-  if (set == pg_.br_set) throw ArgFailure(w + ": the set is bound as the bearing set");
-  if (pg_.in_cal(set)) throw ArgFailure(w + ": the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure(w + ": the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   const bool table = type == 11 || type == 13 || type == 14;   // (intrinsics per entry of the pose table)
   const int ks = type == 11 ? 4 : 5;
@@ -6221,52 +6276,26 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
   if (table)   // (the kernels index the intrinsics by pose_vertex: in range also while no pose table is bound)
     for (size_t k = 0; k < n; ++k)
       if (pose_vertex[k] >= n_cams) throw ArgFailure(w + ": pose index of landmark edge " + std::to_string(k) + " outside the intrinsics table");
-  pg_.lm_set = set;
-  pg_.lm_type = type;
-  pg_.h_vp.assign(pose_vertex, pose_vertex + n);
-  pg_.h_vl.assign(point_vertex, point_vertex + n);
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
   for (int i = 0; i < 4; ++i) pg_.kcam[i] = (kcam && !table) ? kcam[i] : (i < 2 ? 1.0 : 0.0);
   pg_.n_cams = table ? n_cams : 0;
   if (table) pg_.cam_k.upload(kcam, ks * (size_t)n_cams, st_);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.vp.upload(pose_vertex, n, st_);
-  pg_.vl.upload(point_vertex, n, st_);
-  pg_.lm_meas.upload(meas, n * d, st_);
-  es.own_omega.upload(info, n * d * d, st_);
-  es.own_J0.alloc(n * d * dp);
-  es.own_J1.alloc(n * d * dl);
-  es.own_err.alloc(n * d);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kLandmark, {set}, type, {pose_vertex, point_vertex}, n, meas, d, d, dp, dl, info);
 }
 
 // ---- ... its unary pose priors (EdgeSE2Prior / EdgeSE2XYPrior / EdgeSE3Prior) -----------------------------------------------
 void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info,
                                      const double* offset) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_prior_edges: call pg_set_edges first (the pose-pose set the prior set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type == 10) throw ArgFailure("pg_set_prior_edges: no prior set stands beside an EdgeSim3 pose set (10)");
-  if (pg_.type == 12) throw ArgFailure("pg_set_prior_edges: no prior set stands beside a VertexCam set (12)");
+  pg_begin_bind("pg_set_prior_edges", kPrior, {set});
+  const int pt = pg_.pose_type();
+  if (pt == 10) throw ArgFailure("pg_set_prior_edges: no prior set stands beside an EdgeSim3 pose set (10)");
+  if (pt == 12) throw ArgFailure("pg_set_prior_edges: no prior set stands beside a VertexCam set (12)");
   if (type != 7 && type != 8 && type != 9) throw ArgFailure("pg_set_prior_edges: type must be 7 (EdgeSE2Prior), 8 (EdgeSE2XYPrior) or 9 (EdgeSE3Prior)");
-  if ((type == 9) != (pg_.type == 2)) throw ArgFailure("pg_set_prior_edges: EdgeSE2Prior (7) and EdgeSE2XYPrior (8) go with an EdgeSE2 pose set (1), EdgeSE3Prior (9) with EdgeSE3 (2)");
+  if ((type == 9) != (pt == 2)) throw ArgFailure("pg_set_prior_edges: EdgeSE2Prior (7) and EdgeSE2XYPrior (8) go with an EdgeSE2 pose set (1), EdgeSE3Prior (9) with EdgeSE3 (2)");
   if (offset && type != 9) throw ArgFailure("pg_set_prior_edges: an offset belongs to EdgeSE3Prior (type 9) only");
   if (offset)
     for (int i = 0; i < 12; ++i)
       if (!std::isfinite(offset[i])) throw ArgFailure("pg_set_prior_edges: non-finite offset");
-  if (set == pg_.set) throw ArgFailure("pg_set_prior_edges: the set is bound as the pose-pose set");
-  if (set == pg_.lm_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the landmark set");
-  if (set == pg_.gicp_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the GICP set");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (set == pg_.off_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the sensor-offset set");
-  if (set == pg_.br_set) throw ArgFailure("pg_set_prior_edges: the set is bound as the bearing set");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_prior_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_prior_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
   EdgeSet& es = *sets_[set];
   const int d = type == 7 ? 3 : type == 8 ? 2 : 6, dp = type == 9 ? 6 : 3;
   const size_t ms = type == 7 ? 3 : type == 8 ? 2 : 12;
@@ -6277,22 +6306,8 @@ void BlockSolver::pg_set_prior_edges(int set, int type, const int* pose_vertex, 
   const size_t n = (size_t)es.n;
   pg_validate_priors(es, pose_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   pg_refuse_additive("pg_set_prior_edges", pg_.od_rows, {{pose_vertex, n}});
-  pg_.pr_set = set;
-  pg_.pr_type = type;
-  pg_.h_vq.assign(pose_vertex, pose_vertex + n);
   for (int i = 0; i < 12; ++i) pg_.pr_offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.vq.upload(pose_vertex, n, st_);
-  pg_.pr_meas.upload(meas, n * ms, st_);
-  es.own_omega.upload(info, n * d * d, st_);
-  es.own_J0.alloc(n * d * dp);
-  es.own_err.alloc(n * d);
-  es.J0 = es.own_J0.p; es.J1 = nullptr; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.external = false;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kPrior, {set}, type, {pose_vertex}, n, meas, ms, d, dp, 0, info);
 }
 
 // ---- ... its GICP correspondences: Edge_V_V_GICP (type 15) as a second pose-pose set beside an EdgeSE3 one (pg_gicp.inc) -----
@@ -6313,19 +6328,8 @@ bool gicp_spd(const double* c) {
 }  // namespace
 
 void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_gicp_edges: call pg_set_edges first (the EdgeSE3 set the GICP set stands beside; it may be empty)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type != 2) throw ArgFailure("pg_set_gicp_edges: Edge_V_V_GICP (15) goes with an EdgeSE3 pose set (2)");
-  if (set == pg_.set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the pose-pose set");
-  if (set == pg_.lm_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the landmark set");
-  if (set == pg_.pr_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the prior set");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (set == pg_.off_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the sensor-offset set");
-  if (set == pg_.br_set) throw ArgFailure("pg_set_gicp_edges: the set is bound as the bearing set");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_gicp_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_gicp_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
+  pg_begin_bind("pg_set_gicp_edges", kGicp, {set});
+  if (pg_.pose_type() != 2) throw ArgFailure("pg_set_gicp_edges: Edge_V_V_GICP (15) goes with an EdgeSE3 pose set (2)");
   EdgeSet& es = *sets_[set];
   if (es.unary || es.d != 3 || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
     throw ArgFailure("pg_set_gicp_edges: the set must be a binary pose-pose set with (error, pose, pose) dimensions (3, 6, 6)");
@@ -6347,47 +6351,19 @@ void BlockSolver::pg_set_gicp_edges(int set, const int* vi, const int* vj, const
   }
   pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  pg_.gicp_set = set;
   pg_.gicp_plpl = cov != nullptr;
-  pg_.h_gi.assign(vi, vi + n);
-  pg_.h_gj.assign(vj, vj + n);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.gi.upload(vi, n, st_);
-  pg_.gj.upload(vj, n, st_);
-  pg_.gicp_meas.upload(meas, n * 6, st_);
   if (cov) pg_.gicp_cov.upload(cov, n * 18, st_);
-  es.own_omega.upload(info, n * 9, st_);
-  es.own_J0.alloc(n * 18);
-  es.own_J1.alloc(n * 18);
-  es.own_err.alloc(n * 3);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.external = false;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kGicp, {set}, 15, {vi, vj}, n, meas, 6, 3, 6, 6, info);
 }
 
 // ---- ... the pose-pose edges of a multi-sensor rig: EdgeSE2Offset (type 18) beside an EdgeSE2 set, EdgeSE3Offset (type 19) beside
 // an EdgeSE3 set, ONE set in a slot of its own (pg_offset.inc).  Every edge names two rows of the offsets table [n_params][3 | 12].
-// The contract of the GICP entry: validate everything, then commit; a later call replaces the slot's set and clears the data of
-// the set that leaves it; n = 0 is legal; the set owns no vertices.
+// n = 0 is legal.
 void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to,
                                       const double* meas, const double* info, int n_params, const double* offsets) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_offset_edges: call pg_set_edges first (the pose-pose set the sensor-offset set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  pg_begin_bind("pg_set_offset_edges", kOffset, {set});
   if (type != 18 && type != 19) throw ArgFailure("pg_set_offset_edges: type must be 18 (EdgeSE2Offset) or 19 (EdgeSE3Offset)");
-  if (pg_.type != type - 17) throw ArgFailure("pg_set_offset_edges: EdgeSE2Offset (18) goes with an EdgeSE2 pose set (1), EdgeSE3Offset (19) with EdgeSE3 (2)");
-  if (set == pg_.set) throw ArgFailure("pg_set_offset_edges: the set is bound as the pose-pose set");
-  if (set == pg_.lm_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the landmark set");
-  if (set == pg_.pr_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the prior set");
-  if (set == pg_.gicp_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the GICP set");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (set == pg_.br_set) throw ArgFailure("pg_set_offset_edges: the set is bound as the bearing set");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_offset_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_offset_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
+  if (pg_.pose_type() != type - 17) throw ArgFailure("pg_set_offset_edges: EdgeSE2Offset (18) goes with an EdgeSE2 pose set (1), EdgeSE3Offset (19) with EdgeSE3 (2)");
   EdgeSet& es = *sets_[set];
   const int d = type == 18 ? 3 : 6;
   if (es.unary || es.d != d || es.dim0 != d || es.dim1 != d || p_ != d)
@@ -6409,52 +6385,19 @@ void BlockSolver::pg_set_offset_edges(int set, int type, const int* vi, const in
   pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   pg_refuse_additive("pg_set_offset_edges", pg_.od_rows, {{vi, n}, {vj, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  if (pg_.off_set >= 0 && pg_.off_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
-    EdgeSet& old = *sets_[pg_.off_set];
-    old.has_data = old.has_err = false;
-  }
-  pg_.off_set = set;
-  pg_.off_type = type;
   pg_.off_params = n_params;
-  pg_.h_oi.assign(vi, vi + n);
-  pg_.h_oj.assign(vj, vj + n);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.oi.upload(vi, n, st_);
-  pg_.oj.upload(vj, n, st_);
   pg_.opf.upload(param_from, n, st_);
   pg_.opt.upload(param_to, n, st_);
-  pg_.off_meas.upload(meas, n * ms, st_);
   pg_.off_table.upload(offsets, ms * (size_t)n_params, st_);
-  es.own_omega.upload(info, n * d * d, st_);
-  es.own_J0.alloc(n * d * d);
-  es.own_J1.alloc(n * d * d);
-  es.own_err.alloc(n * d);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.external = false;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kOffset, {set}, type, {vi, vj}, n, meas, ms, d, d, d, info);
 }
 
 // ---- ... bearing-only observations of 2-D point landmarks: EdgeSE2PointXYBearing (type 20) beside an EdgeSE2 set, ONE set in a
 // slot of its own (pg_bearing.inc), with or without an EdgeSE2PointXY set (type 3) in the landmark slot: both index the landmark
-// table of pg_set_landmark_estimates.  The contract of the sensor-offset entry: validate everything, then commit; a later call
-// replaces the slot's set and clears the data of the set that leaves it; n = 0 is legal.
+// table of pg_set_landmark_estimates.  n = 0 is legal.
 void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_bearing_edges: call pg_set_edges first (the pose-pose set the bearing set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (pg_.type != 1) throw ArgFailure("pg_set_bearing_edges: EdgeSE2PointXYBearing (20) goes with an EdgeSE2 pose set (1)");
-  if (set == pg_.set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the pose-pose set");
-  if (set == pg_.lm_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the landmark set");
-  if (set == pg_.pr_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the prior set");
-  if (set == pg_.gicp_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the GICP set");
-  if (set == pg_.cam_set || set == pg_.scale_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the EdgeSBACam or EdgeSBAScale set");
-  if (set == pg_.off_set) throw ArgFailure("pg_set_bearing_edges: the set is bound as the sensor-offset set");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_bearing_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_bearing_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
+  pg_begin_bind("pg_set_bearing_edges", kBearing, {set});
+  if (pg_.pose_type() != 1) throw ArgFailure("pg_set_bearing_edges: EdgeSE2PointXYBearing (20) goes with an EdgeSE2 pose set (1)");
   EdgeSet& es = *sets_[set];
   // (a set of zero edges has no vertex classes: build_structure gives it pose dimensions on both sides)
   if (es.unary || es.d != 1 || p_ != 3 || l_ != 2 || (es.n > 0 && (es.dim0 != 3 || es.dim1 != 2)))
@@ -6468,258 +6411,102 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
   pg_validate_landmarks(es, pose_vertex, point_vertex, n, pg_.poses.h_hidx.data(), pg_.poses.n, pg_.points.h_hidx.data(), pg_.points.n);
   pg_refuse_additive("pg_set_bearing_edges", pg_.od_rows, {{pose_vertex, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  if (pg_.br_set >= 0 && pg_.br_set != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
-    EdgeSet& old = *sets_[pg_.br_set];
-    old.has_data = old.has_err = false;
-  }
-  pg_.br_set = set;
-  pg_.h_bp.assign(pose_vertex, pose_vertex + n);
-  pg_.h_bl.assign(point_vertex, point_vertex + n);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.bp.upload(pose_vertex, n, st_);
-  pg_.bl.upload(point_vertex, n, st_);
-  pg_.br_meas.upload(meas, n, st_);
-  es.own_omega.upload(info, n, st_);
-  es.own_J0.alloc(n * 3);
-  es.own_J1.alloc(n * 2);
-  es.own_err.alloc(n);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.external = false;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
+  pg_commit(kBearing, {set}, 20, {pose_vertex, point_vertex}, n, meas, 1, 1, 3, 2, info);
 }
 
-// ---- ... laser self-calibration: EdgeSE2SensorCalib (type 21), a THREE-vertex edge over two poses and the laser offset L, all
-// rows of the one pose table, beside an EdgeSE2 set (pg_calib.inc).  The edge is the three binary sets g2ohip_set_edge_set_parts
-// documents for three vertices, all of the same edge count, error dimension 3 and vertex dimensions (3, 3):
+// ---- ... the two calibration groups: EdgeSE2SensorCalib (type 21, pg_calib.inc) and EdgeSE2OdomDifferentialCalib (type 22,
+// pg_odom_calib.inc), THREE-vertex edges over two poses and a third row x of the one pose table (the laser offset L; a
+// VertexOdomDifferentialParams (k_l, k_r, b)), beside an EdgeSE2 set, each group in a slot of its own (both may be bound at once:
+// the graph of g2o/examples/calibration_odom_laser).  The edge is the three binary sets g2ohip_set_edge_set_parts documents for
+// three vertices, all of the same edge count, error dimension 3 and vertex dimensions (3, 3):
 //   set_ij  (i, j)  parts 0                                  terms of i and j, H(i, j), chi2
-//   set_il  (i, l)  parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  H(i, l)
-//   set_jl  (j, l)  parts NO_VERTEX0 | NO_CHI2               terms of l, H(j, l)
-// They occupy the calibration slot as ONE group (the PSI2UV sets of ba_set_inverse_depth_edges are the precedent): pg_linearize
-// writes J_i / J_j / information / errors into set_ij's buffers and J_l into set_jl's own_J1, and every other pointer of the three
-// aliases one of those (27 + 3 doubles per edge leave the producer, not 54 + 9).  Robust kernels: the caller sets the same kernel
-// on all three sets (the generic assembly weighs each set by its own).  Validate, then commit; a later call releases the previous
-// group (pg_cal_release).
+//   set_ix  (i, x)  parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  H(i, x)
+//   set_jx  (j, x)  parts NO_VERTEX0 | NO_CHI2               terms of x, H(j, x)
+// They occupy their slot as ONE group (the PSI2UV sets of ba_set_inverse_depth_edges are the precedent): pg_linearize writes J_i /
+// J_j / information / errors into set_ij's buffers and J_x into set_jx's own_J1, and every other pointer of the three aliases one
+// of those (27 + 3 doubles per edge leave the producer, not 54 + 9).  Robust kernels: the caller sets the same kernel on all three
+// sets (the generic assembly weighs each set by its own).  The checks the two entries share, up to the index validation:
+void BlockSolver::pg_check_group(const std::string& w, const int ids[3], const int* vi, const int* vj, const int* vx, const double* meas,
+                                 const double* info) const {
+  if (ids[0] == ids[1] || ids[0] == ids[2] || ids[1] == ids[2]) throw ArgFailure(w + ": the three sets must differ");
+  const EdgeSet &es = *sets_[ids[0]], &ea = *sets_[ids[1]], &ec = *sets_[ids[2]];
+  for (const EdgeSet* e : {&es, &ea, &ec})
+    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
+      throw ArgFailure(w + ": the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
+  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
+    throw ArgFailure(w + ": parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
+  if (ea.n != es.n || ec.n != es.n) throw ArgFailure(w + ": the three sets must hold the same number of edges");
+  if (!vi || !vj || !vx || !meas) throw ArgFailure(w + ": null array");
+  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
+    throw StateFailure(w + ": a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
+  const size_t n = (size_t)es.n;
+  for (size_t k = 0; k < n; ++k) {
+    if (vi[k] < 0 || vj[k] < 0 || vx[k] < 0) throw ArgFailure(w + ": negative vertex index in edge " + std::to_string(k));
+    if (vi[k] == vj[k] || vi[k] == vx[k] || vj[k] == vx[k]) throw ArgFailure(w + ": edge " + std::to_string(k) + " names one vertex twice");
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure(w + ": non-finite measurement in edge " + std::to_string(k));
+    if (info)
+      for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(info[9 * k + i])) throw ArgFailure(w + ": non-finite information in edge " + std::to_string(k));
+  }
+  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ea, vi, vx, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_validate(ec, vj, vx, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+}
+
+// information().setIdentity() of n three-dimensional edges
+static std::vector<double> pg_identity3(size_t n) {
+  std::vector<double> w(n * 9, 0.0);
+  for (size_t k = 0; k < n; ++k) w[9 * k] = w[9 * k + 4] = w[9 * k + 8] = 1.0;
+  return w;
+}
+
 void BlockSolver::pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, const int* vi, const int* vj, const int* vl,
                                             const double* meas, const double* info) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0)
-    throw StateFailure("pg_set_sensor_calib_edges: call pg_set_edges first (the pose-pose set the calibration group stands beside)");
+  pg_begin_bind("pg_set_sensor_calib_edges", kCalib, {set_ij, set_il, set_jl});
+  if (pg_.pose_type() != 1) throw ArgFailure("pg_set_sensor_calib_edges: EdgeSE2SensorCalib (21) goes with an EdgeSE2 pose set (1)");
   const int ids[3] = {set_ij, set_il, set_jl};
-  for (int id : ids)
-    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (set_ij == set_il || set_ij == set_jl || set_il == set_jl) throw ArgFailure("pg_set_sensor_calib_edges: the three sets must differ");
-  if (pg_.type != 1) throw ArgFailure("pg_set_sensor_calib_edges: EdgeSE2SensorCalib (21) goes with an EdgeSE2 pose set (1)");
-  for (int id : ids)
-    if (id == pg_.set || id == pg_.lm_set || id == pg_.pr_set || id == pg_.gicp_set || id == pg_.cam_set || id == pg_.scale_set ||
-        id == pg_.off_set || id == pg_.br_set || pg_.in_od(id))
-      throw ArgFailure("pg_set_sensor_calib_edges: set " + std::to_string(id) + " is bound in another slot");
-  EdgeSet &es = *sets_[set_ij], &ea = *sets_[set_il], &ec = *sets_[set_jl];
-  for (const EdgeSet* e : {&es, &ea, &ec})
-    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
-      throw ArgFailure("pg_set_sensor_calib_edges: the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
-  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
-    throw ArgFailure("pg_set_sensor_calib_edges: parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
-  if (ea.n != es.n || ec.n != es.n) throw ArgFailure("pg_set_sensor_calib_edges: the three sets must hold the same number of edges");
-  if (!vi || !vj || !vl || !meas) throw ArgFailure("pg_set_sensor_calib_edges: null array");
-  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
-    throw StateFailure("pg_set_sensor_calib_edges: a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
-  const size_t n = (size_t)es.n;
-  for (size_t k = 0; k < n; ++k) {
-    if (vi[k] < 0 || vj[k] < 0 || vl[k] < 0) throw ArgFailure("pg_set_sensor_calib_edges: negative vertex index in edge " + std::to_string(k));
-    if (vi[k] == vj[k] || vi[k] == vl[k] || vj[k] == vl[k])
-      throw ArgFailure("pg_set_sensor_calib_edges: edge " + std::to_string(k) + " names one vertex twice");
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure("pg_set_sensor_calib_edges: non-finite measurement in edge " + std::to_string(k));
-    if (info)
-      for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_sensor_calib_edges: non-finite information in edge " + std::to_string(k));
-  }
-  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ea, vi, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ec, vj, vl, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_check_group("pg_set_sensor_calib_edges", ids, vi, vj, vl, meas, info);
+  const size_t n = (size_t)sets_[set_ij]->n;
   pg_refuse_additive("pg_set_sensor_calib_edges", pg_.od_rows, {{vi, n}, {vj, n}, {vl, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  // commit: the previous group leaves the slot, with the data the device wrote for it
-  std::vector<double> identity;
-  if (!info) {   // information().setIdentity()
-    identity.assign(n * 9, 0.0);
-    for (size_t k = 0; k < n; ++k) identity[9 * k] = identity[9 * k + 4] = identity[9 * k + 8] = 1.0;
-    info = identity.data();
-  }
-  pg_cal_release();
-  pg_.cal_ij = set_ij;
-  pg_.cal_il = set_il;
-  pg_.cal_jl = set_jl;
-  pg_.h_cal_vi.assign(vi, vi + n);
-  pg_.h_cal_vj.assign(vj, vj + n);
-  pg_.h_cal_vl.assign(vl, vl + n);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.cal_vi.upload(vi, n, st_);
-  pg_.cal_vj.upload(vj, n, st_);
-  pg_.cal_vl.upload(vl, n, st_);
-  pg_.cal_meas.upload(meas, n * 3, st_);
-  es.own_omega.upload(info, n * 9, st_);
-  es.own_J0.alloc(n * 9);
-  es.own_J1.alloc(n * 9);
-  es.own_err.alloc(n * 3);
-  ec.own_J1.alloc(n * 9);
-  pg_cal_alias();
-  for (EdgeSet* e : {&es, &ea, &ec}) {
-    e->external = false;
-    e->has_data = false;   // becomes valid with the first pg_linearize
-    e->has_err = false;
-  }
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));   // (the identity staging buffer is read by the upload)
+  const std::vector<double> identity = info ? std::vector<double>() : pg_identity3(n);
+  pg_commit(kCalib, {set_ij, set_il, set_jl}, 21, {vi, vj, vl}, n, meas, 3, 3, 3, 3, info ? info : identity.data());
 }
 
-// the pointers of the three sets of a calibration group onto the buffers two of them own; a pointer that had to be repaired
-// (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences
-void BlockSolver::pg_cal_alias() {
-  EdgeSet &es = *sets_[pg_.cal_ij], &ea = *sets_[pg_.cal_il], &ec = *sets_[pg_.cal_jl];
-  const double *ji = es.own_J0.p, *jj = es.own_J1.p, *jl = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
-  const double* want[3][2] = {{ji, jj}, {ji, jl}, {jj, jl}};
-  EdgeSet* g[3] = {&es, &ea, &ec};
-  bool changed = false;
-  for (int i = 0; i < 3; ++i) {
-    EdgeSet& e = *g[i];
-    changed = changed || e.J0 != want[i][0] || e.J1 != want[i][1] || e.omega != om || e.err != er || e.external;
-    e.J0 = want[i][0];
-    e.J1 = want[i][1];
-    e.omega = om;
-    e.err = er;
-    e.external = false;
-  }
-  if (changed) drop_graph_segments();
-}
-
-// a calibration group leaves its slot: its sets keep no device-written data and no pointer into each other's buffers
-// (set_edge_data is their next source; build_system refuses them until then, unless they are empty)
-void BlockSolver::pg_cal_release() {
-  if (pg_.cal_ij < 0) return;
-  for (int id : {pg_.cal_ij, pg_.cal_il, pg_.cal_jl}) {
-    if (id < 0 || id >= (int)sets_.size()) continue;
-    EdgeSet& e = *sets_[id];
-    e.has_data = e.has_err = false;
-    e.J0 = e.J1 = e.omega = e.err = nullptr;
-  }
-  pg_.cal_ij = pg_.cal_il = pg_.cal_jl = -1;
-  pg_.h_cal_vi.clear();
-  pg_.h_cal_vj.clear();
-  pg_.h_cal_vl.clear();
-  pg_.err_valid = pg_.jac_valid = false;
-}
-
-// the three sets of a calibration group against a pose table
-void BlockSolver::pg_validate_calib(const int* vi, const int* vj, const int* vl, size_t n, const int* hidx, int nv) const {
-  pg_validate(*sets_[pg_.cal_ij], vi, vj, n, hidx, nv);
-  pg_validate(*sets_[pg_.cal_il], vi, vl, n, hidx, nv);
-  pg_validate(*sets_[pg_.cal_jl], vj, vl, n, hidx, nv);
-}
-
-// ---- ... odometry self-calibration: EdgeSE2OdomDifferentialCalib (type 22), a THREE-vertex edge over two poses and a
-// VertexOdomDifferentialParams (k_l, k_r, b), all rows of the one pose table, beside an EdgeSE2 set (pg_odom_calib.inc).  The
-// contract of pg_set_sensor_calib_edges, clause for clause, in a slot of its own (both groups may be bound at once: the graph of
-// g2o/examples/calibration_odom_laser):
-//   set_ij  (i, j)  parts 0                                  terms of i and j, H(i, j), chi2
-//   set_ip  (i, p)  parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  H(i, p)
-//   set_jp  (j, p)  parts NO_VERTEX0 | NO_CHI2               terms of p, H(j, p)
-// and one clause more: while the group is bound the rows its vp names are ADDITIVE rows of the table (pg_update adds all three
-// components, no angle wrap), so no other binding may read them as VertexSE2 -- refused here against everything bound, and in the
-// other pg_set_* entries against od_rows (pg_refuse_additive).  Validate, then commit.
+// One clause more than the type-21 group: while the group is bound the rows its vp names are ADDITIVE rows of the table (pg_update
+// adds all three components, no angle wrap), so no other binding may read them as VertexSE2 -- refused here against everything
+// bound, and in the other pg_set_* entries against od_rows (pg_refuse_additive).
 void BlockSolver::pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, const int* vi, const int* vj, const int* vp,
                                           const double* meas, const double* info) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0)
-    throw StateFailure("pg_set_odom_calib_edges: call pg_set_edges first (the pose-pose set the calibration group stands beside)");
+  pg_begin_bind("pg_set_odom_calib_edges", kOdom, {set_ij, set_ip, set_jp});
+  if (pg_.pose_type() != 1) throw ArgFailure("pg_set_odom_calib_edges: EdgeSE2OdomDifferentialCalib (22) goes with an EdgeSE2 pose set (1)");
   const int ids[3] = {set_ij, set_ip, set_jp};
-  for (int id : ids)
-    if (id < 0 || id >= (int)sets_.size()) throw ArgFailure("bad edge set id");
-  if (set_ij == set_ip || set_ij == set_jp || set_ip == set_jp) throw ArgFailure("pg_set_odom_calib_edges: the three sets must differ");
-  if (pg_.type != 1) throw ArgFailure("pg_set_odom_calib_edges: EdgeSE2OdomDifferentialCalib (22) goes with an EdgeSE2 pose set (1)");
-  for (int id : ids)
-    if (id == pg_.set || id == pg_.lm_set || id == pg_.pr_set || id == pg_.gicp_set || id == pg_.cam_set || id == pg_.scale_set ||
-        id == pg_.off_set || id == pg_.br_set || pg_.in_cal(id))
-      throw ArgFailure("pg_set_odom_calib_edges: set " + std::to_string(id) + " is bound in another slot");
-  EdgeSet &es = *sets_[set_ij], &ea = *sets_[set_ip], &ec = *sets_[set_jp];
-  for (const EdgeSet* e : {&es, &ea, &ec})
-    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
-      throw ArgFailure("pg_set_odom_calib_edges: the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
-  if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
-    throw ArgFailure("pg_set_odom_calib_edges: parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
-  if (ea.n != es.n || ec.n != es.n) throw ArgFailure("pg_set_odom_calib_edges: the three sets must hold the same number of edges");
-  if (!vi || !vj || !vp || !meas) throw ArgFailure("pg_set_odom_calib_edges: null array");
-  if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
-    throw StateFailure("pg_set_odom_calib_edges: a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
-  const size_t n = (size_t)es.n;
-  for (size_t k = 0; k < n; ++k) {
-    if (vi[k] < 0 || vj[k] < 0 || vp[k] < 0) throw ArgFailure("pg_set_odom_calib_edges: negative vertex index in edge " + std::to_string(k));
-    if (vi[k] == vj[k] || vi[k] == vp[k] || vj[k] == vp[k])
-      throw ArgFailure("pg_set_odom_calib_edges: edge " + std::to_string(k) + " names one vertex twice");
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure("pg_set_odom_calib_edges: non-finite measurement in edge " + std::to_string(k));
-    if (info)
-      for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_odom_calib_edges: non-finite information in edge " + std::to_string(k));
-  }
-  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ea, vi, vp, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ec, vj, vp, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  pg_check_group("pg_set_odom_calib_edges", ids, vi, vj, vp, meas, info);
+  const size_t n = (size_t)sets_[set_ij]->n;
   // the rows of vp become additive rows: none of them may be a pose of this group or a vertex of anything bound on the handle
   std::vector<int> rows(vp, vp + n);
   std::sort(rows.begin(), rows.end());
   rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-  const auto bound = [](bool on, const std::vector<int>& v) { return std::pair<const int*, size_t>(v.data(), on ? v.size() : 0); };
-  pg_refuse_additive("pg_set_odom_calib_edges", rows,
-                     {{vi, n}, {vj, n}, bound(true, pg_.h_vi), bound(true, pg_.h_vj), bound(pg_.lm_set >= 0, pg_.h_vp),
-                      bound(pg_.pr_set >= 0, pg_.h_vq), bound(pg_.off_set >= 0, pg_.h_oi), bound(pg_.off_set >= 0, pg_.h_oj),
-                      bound(pg_.br_set >= 0, pg_.h_bp), bound(pg_.cal_ij >= 0, pg_.h_cal_vi), bound(pg_.cal_ij >= 0, pg_.h_cal_vj),
-                      bound(pg_.cal_ij >= 0, pg_.h_cal_vl)});
+  std::vector<std::pair<const int*, size_t>> read_as_pose = {{vi, n}, {vj, n}};
+  for (int k = 0; k < kPgSlots; ++k) {
+    const PgSlot& sl = pg_.slot[k];
+    if (k == kOdom || !sl.bound()) continue;   // (the group this call replaces leaves)
+    for (int a = 0; a < kPgSlotDesc[k].arrays; ++a)
+      if (!kPgSlotDesc[k].points[a]) read_as_pose.emplace_back(sl.h_v[a].data(), sl.h_v[a].size());
+  }
+  pg_refuse_additive("pg_set_odom_calib_edges", rows, read_as_pose);
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  // commit: the previous group leaves the slot, with the data the device wrote for it
-  std::vector<double> identity;
-  if (!info) {   // information().setIdentity()
-    identity.assign(n * 9, 0.0);
-    for (size_t k = 0; k < n; ++k) identity[9 * k] = identity[9 * k + 4] = identity[9 * k + 8] = 1.0;
-    info = identity.data();
-  }
-  pg_od_release();
-  pg_.od_ij = set_ij;
-  pg_.od_ip = set_ip;
-  pg_.od_jp = set_jp;
-  pg_.h_od_vi.assign(vi, vi + n);
-  pg_.h_od_vj.assign(vj, vj + n);
-  pg_.h_od_vp.assign(vp, vp + n);
+  const std::vector<double> identity = info ? std::vector<double>() : pg_identity3(n);
+  pg_od_release();   // the previous group leaves the slot, with its additive rows
   pg_.od_rows = std::move(rows);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  pg_.od_vi.upload(vi, n, st_);
-  pg_.od_vj.upload(vj, n, st_);
-  pg_.od_vp.upload(vp, n, st_);
-  pg_.od_meas.upload(meas, n * 3, st_);
-  es.own_omega.upload(info, n * 9, st_);
-  es.own_J0.alloc(n * 9);
-  es.own_J1.alloc(n * 9);
-  es.own_err.alloc(n * 3);
-  ec.own_J1.alloc(n * 9);
-  pg_od_alias();
-  for (EdgeSet* e : {&es, &ea, &ec}) {
-    e->external = false;
-    e->has_data = false;   // becomes valid with the first pg_linearize
-    e->has_err = false;
-  }
   pg_od_build_mask();
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));   // (the identity staging buffer is read by the upload)
+  pg_commit(kOdom, {set_ij, set_ip, set_jp}, 22, {vi, vj, vp}, n, meas, 3, 3, 3, 3, info ? info : identity.data());
 }
 
 // the ONE check of row kinds: an index of `lists` (arrays a binding reads as VertexSE2) that names a row of `additive` (sorted)
 void BlockSolver::pg_refuse_additive(const std::string& who, const std::vector<int>& additive,
-                                     std::initializer_list<std::pair<const int*, size_t>> lists) {
+                                     const std::vector<std::pair<const int*, size_t>>& lists) {
   if (additive.empty()) return;
   for (const auto& l : lists)
     for (size_t k = 0; k < l.second; ++k)
@@ -6737,74 +6524,15 @@ void BlockSolver::pg_od_build_mask() {
   pg_.od_mask.upload(mask, st_);   // (pageable host memory: staged before return; both callers synchronise the stream)
 }
 
-// the pointers of the three sets of an odometry-calibration group onto the buffers two of them own (as pg_cal_alias)
-void BlockSolver::pg_od_alias() {
-  EdgeSet &es = *sets_[pg_.od_ij], &ea = *sets_[pg_.od_ip], &ec = *sets_[pg_.od_jp];
-  const double *ji = es.own_J0.p, *jj = es.own_J1.p, *jp = ec.own_J1.p, *om = es.own_omega.p, *er = es.own_err.p;
-  const double* want[3][2] = {{ji, jj}, {ji, jp}, {jj, jp}};
-  EdgeSet* g[3] = {&es, &ea, &ec};
-  bool changed = false;
-  for (int i = 0; i < 3; ++i) {
-    EdgeSet& e = *g[i];
-    changed = changed || e.J0 != want[i][0] || e.J1 != want[i][1] || e.omega != om || e.err != er || e.external;
-    e.J0 = want[i][0];
-    e.J1 = want[i][1];
-    e.omega = om;
-    e.err = er;
-    e.external = false;
-  }
-  if (changed) drop_graph_segments();
-}
-
-// an odometry-calibration group leaves its slot: its sets keep no device-written data and no pointer into each other's buffers,
-// and the rows its vp named are ordinary VertexSE2 rows again (pg_update wraps their third component)
-void BlockSolver::pg_od_release() {
-  if (pg_.od_ij < 0) return;
-  for (int id : {pg_.od_ij, pg_.od_ip, pg_.od_jp}) {
-    if (id < 0 || id >= (int)sets_.size()) continue;
-    EdgeSet& e = *sets_[id];
-    e.has_data = e.has_err = false;
-    e.J0 = e.J1 = e.omega = e.err = nullptr;
-  }
-  pg_.od_ij = pg_.od_ip = pg_.od_jp = -1;
-  pg_.h_od_vi.clear();
-  pg_.h_od_vj.clear();
-  pg_.h_od_vp.clear();
-  pg_.od_rows.clear();
-  pg_.err_valid = pg_.jac_valid = false;
-  drop_graph_segments();
-}
-
-// the three sets of an odometry-calibration group against a pose table
-void BlockSolver::pg_validate_odom_calib(const int* vi, const int* vj, const int* vp, size_t n, const int* hidx, int nv) const {
-  pg_validate(*sets_[pg_.od_ij], vi, vj, n, hidx, nv);
-  pg_validate(*sets_[pg_.od_ip], vi, vp, n, hidx, nv);
-  pg_validate(*sets_[pg_.od_jp], vj, vp, n, hidx, nv);
-}
-
 // ---- ... the SBA group's pose-pose constraints: EdgeSBACam (type 16) and EdgeSBAScale (type 17), each ONE set in a slot of its
-// own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  The contract of the GICP entry:
-// validate everything, then commit; a later call replaces the slot's set and clears the data of the set that leaves it; n = 0 is
-// legal; the sets own no vertices.  EdgeSBACam::setMeasurement: the measurement is normalised (SE3Quat(Vector7d)) and inverted
-// once, here, on the device and in the reference's operation order; pg_.cam_zinv holds the inverses.
+// own beside a type-12 pose set (pg_sbacam_edge.inc), with or without a projection set (13 / 14).  n = 0 is legal.
+// EdgeSBACam::setMeasurement: the measurement is normalised (SE3Quat(Vector7d)) and inverted once, here, on the device and in the
+// reference's operation order; the slot's meas holds the inverses.
 void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info) {
-  invalidate_graphs();
-  require_structure();
-  if (pg_.set < 0 || pg_.type == 0) throw StateFailure("pg_set_cam_edges: call pg_set_edges first (the empty VertexCam set (12) the set stands beside)");
-  if (set < 0 || set >= (int)sets_.size()) throw ArgFailure("bad edge set id");
+  const bool cam = type != 17;   // (any type but 16 / 17 is refused below: the slot matters for the ownership check only)
+  pg_begin_bind("pg_set_cam_edges", cam ? kCam : kScale, {set});
   if (type != 16 && type != 17) throw ArgFailure("pg_set_cam_edges: type must be 16 (EdgeSBACam) or 17 (EdgeSBAScale)");
-  if (pg_.type != 12) throw ArgFailure("pg_set_cam_edges: EdgeSBACam / EdgeSBAScale go with a VertexCam set (12)");
-  const bool cam = type == 16;
-  if (set == pg_.set) throw ArgFailure("pg_set_cam_edges: the set is bound as the pose-pose set");
-  if (set == pg_.lm_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the landmark set");
-  if (set == pg_.pr_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the prior set");
-  if (set == pg_.gicp_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the GICP set");
-  if (set == pg_.off_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the sensor-offset set");
-  if (set == pg_.br_set) throw ArgFailure("pg_set_cam_edges: the set is bound as the bearing set");
-  if (pg_.in_cal(set)) throw ArgFailure("pg_set_cam_edges: the set is bound in the EdgeSE2SensorCalib group");
-  if (pg_.in_od(set)) throw ArgFailure("pg_set_cam_edges: the set is bound in the EdgeSE2OdomDifferentialCalib group");
-  if (set == (cam ? pg_.scale_set : pg_.cam_set))
-    throw ArgFailure(std::string("pg_set_cam_edges: the set is bound as the ") + (cam ? "EdgeSBAScale" : "EdgeSBACam") + " set");
+  if (pg_.pose_type() != 12) throw ArgFailure("pg_set_cam_edges: EdgeSBACam / EdgeSBAScale go with a VertexCam set (12)");
   EdgeSet& es = *sets_[set];
   const int d = cam ? 6 : 1;
   if (es.unary || es.d != d || es.dim0 != 6 || es.dim1 != 6 || p_ != 6)
@@ -6826,49 +6554,25 @@ void BlockSolver::pg_set_cam_edges(int set, int type, const int* vi, const int* 
   }
   pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  int& slot = cam ? pg_.cam_set : pg_.scale_set;
-  if (slot >= 0 && slot != set) {   // the set that leaves the slot keeps no device-written data: set_edge_data is its next source
-    EdgeSet& old = *sets_[slot];
-    old.has_data = old.has_err = false;
+  pg_commit(cam ? kCam : kScale, {set}, type, {vi, vj}, n, meas, ms, d, 6, 6, info);
+  if (cam && n > 0) {
+    hipLaunchKernelGGL(pg_sbacam_invert_meas_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, (int)n, pg_.slot[kCam].meas.p);
+    G2OHIP_HIP_CHECK(hipGetLastError());
+    G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
   }
-  slot = set;
-  (cam ? pg_.h_ci : pg_.h_si).assign(vi, vi + n);
-  (cam ? pg_.h_cj : pg_.h_sj).assign(vj, vj + n);
-  pg_.err_valid = pg_.jac_valid = false;   // (new measurements: the last evaluation no longer stands)
-  chi2_valid_ = false;
-  (cam ? pg_.ci : pg_.si).upload(vi, n, st_);
-  (cam ? pg_.cj : pg_.sj).upload(vj, n, st_);
-  DevBuf<double>& dm = cam ? pg_.cam_zinv : pg_.scale_meas;
-  dm.upload(meas, n * ms, st_);
-  if (cam && n > 0)
-    hipLaunchKernelGGL(pg_sbacam_invert_meas_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st_, (int)n, dm.p);
-  es.own_omega.upload(info, n * d * d, st_);
-  es.own_J0.alloc(n * d * 6);
-  es.own_J1.alloc(n * d * 6);
-  es.own_err.alloc(n * d);
-  es.J0 = es.own_J0.p; es.J1 = es.own_J1.p; es.omega = es.own_omega.p; es.err = es.own_err.p;
-  es.external = false;
-  es.has_data = false;
-  es.has_err = false;
-  G2OHIP_HIP_CHECK(hipGetLastError());
-  G2OHIP_HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 void BlockSolver::pg_set_landmark_estimates(int n_points, const double* points, const int* hidx) {
   require_structure();
-  if (pg_.type == 0) throw StateFailure("pg_set_landmark_estimates: call pg_set_edges first");
+  if (pg_.pose_type() == 0) throw StateFailure("pg_set_landmark_estimates: call pg_set_edges first");
   if (n_points <= 0 || !points || !hidx) throw ArgFailure("pg_set_landmark_estimates: bad arguments");
-  const int l = pg_.type == 1 ? 2 : 3;
+  const int l = pg_.pose_type() == 1 ? 2 : 3;
   if (l != l_) throw ArgFailure("pg_set_landmark_estimates: the solver's landmark dimension does not fit the pose set's type");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   const bool same = pg_.points.same(n_points, l, hidx);   // (same tables, new values: see ba_set_estimates)
   if (!same) {
-    if (pg_.lm_set >= 0)
-      pg_validate_landmarks(*sets_[pg_.lm_set], pg_.h_vp.data(), pg_.h_vl.data(), pg_.h_vp.size(), pg_.poses.h_hidx.data(), pg_.poses.n,
-                            hidx, n_points);
-    if (pg_.br_set >= 0)   // (with or without a set in the landmark slot)
-      pg_validate_landmarks(*sets_[pg_.br_set], pg_.h_bp.data(), pg_.h_bl.data(), pg_.h_bp.size(), pg_.poses.h_hidx.data(), pg_.poses.n,
-                            hidx, n_points);
+    for (int k = 0; k < kPgSlots; ++k)   // every bound slot that names landmarks
+      if (pg_.slot[k].bound() && kPgSlotDesc[k].points[1]) pg_validate_slot((PgSlotId)k, pg_.poses.h_hidx.data(), pg_.poses.n, hidx, n_points);
     invalidate_graphs();
   }
   pg_.err_valid = pg_.jac_valid = false;
@@ -6885,225 +6589,183 @@ void BlockSolver::pg_get_landmark_estimates(double* points) {
 }
 
 void BlockSolver::pg_linearize(bool jacobians) {
-  if (pg_.set < 0 || pg_.poses.n <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
+  const PgSlot &s_pose = pg_.slot[kPose], &s_lm = pg_.slot[kLandmark], &s_prior = pg_.slot[kPrior], &s_gicp = pg_.slot[kGicp], &s_cam = pg_.slot[kCam],
+               &s_scale = pg_.slot[kScale], &s_off = pg_.slot[kOffset], &s_bear = pg_.slot[kBearing], &s_calib = pg_.slot[kCalib], &s_odom = pg_.slot[kOdom];
+  if (!s_pose.bound() || pg_.poses.n <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  EdgeSet& es = *sets_[pg_.set];
-  if ((int)pg_.h_vi.size() != es.n) throw StateFailure("pg_linearize: the edge set has grown since pg_set_edges (g2ohip_update_structure): call pg_set_edges again");
-  EdgeSet* el = pg_.lm_set >= 0 ? sets_[pg_.lm_set].get() : nullptr;
-  if (el) {
-    if (pg_.points.n <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
-    if ((int)pg_.h_vp.size() != el->n) throw StateFailure("pg_linearize: the landmark edge set has changed since pg_set_landmark_edges: call it again");
-  }
-  EdgeSet* ep = pg_.pr_set >= 0 ? sets_[pg_.pr_set].get() : nullptr;
-  if (ep && (int)pg_.h_vq.size() != ep->n)
-    throw StateFailure("pg_linearize: the prior edge set has grown since pg_set_prior_edges (g2ohip_update_structure): call pg_set_prior_edges again");
-  EdgeSet* eg = pg_.gicp_set >= 0 ? sets_[pg_.gicp_set].get() : nullptr;
-  if (eg && (int)pg_.h_gi.size() != eg->n)
-    throw StateFailure("pg_linearize: the GICP edge set has grown since pg_set_gicp_edges (g2ohip_update_structure): call pg_set_gicp_edges again");
-  EdgeSet* ec = pg_.cam_set >= 0 ? sets_[pg_.cam_set].get() : nullptr;
-  EdgeSet* esc = pg_.scale_set >= 0 ? sets_[pg_.scale_set].get() : nullptr;
-  if ((ec && (int)pg_.h_ci.size() != ec->n) || (esc && (int)pg_.h_si.size() != esc->n))
-    throw StateFailure("pg_linearize: the EdgeSBACam / EdgeSBAScale edge set has grown since pg_set_cam_edges (g2ohip_update_structure): call pg_set_cam_edges again");
-  EdgeSet* eo = pg_.off_set >= 0 ? sets_[pg_.off_set].get() : nullptr;
-  if (eo && (int)pg_.h_oi.size() != eo->n)
-    throw StateFailure("pg_linearize: the sensor-offset edge set has grown since pg_set_offset_edges (g2ohip_update_structure): call pg_set_offset_edges again");
-  EdgeSet* eb = pg_.br_set >= 0 ? sets_[pg_.br_set].get() : nullptr;
-  if (eb) {
-    if (pg_.points.n <= 0) throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
-    if ((int)pg_.h_bp.size() != eb->n)
-      throw StateFailure("pg_linearize: the bearing edge set has grown since pg_set_bearing_edges (g2ohip_update_structure): call pg_set_bearing_edges again");
-  }
-  EdgeSet* const ecal[3] = {pg_.cal_ij >= 0 ? sets_[pg_.cal_ij].get() : nullptr, pg_.cal_ij >= 0 ? sets_[pg_.cal_il].get() : nullptr,
-                            pg_.cal_ij >= 0 ? sets_[pg_.cal_jl].get() : nullptr};
-  if (ecal[0]) {
-    for (EdgeSet* e : ecal)
-      if ((int)pg_.h_cal_vi.size() != e->n)
-        throw StateFailure("pg_linearize: an EdgeSE2SensorCalib edge set has grown since pg_set_sensor_calib_edges: call it again");
-    pg_cal_alias();   // (before err_valid / jac_valid are read: a repaired pointer drops the captured launch sequences)
-  }
-  EdgeSet* const eod[3] = {pg_.od_ij >= 0 ? sets_[pg_.od_ij].get() : nullptr, pg_.od_ij >= 0 ? sets_[pg_.od_ip].get() : nullptr,
-                           pg_.od_ij >= 0 ? sets_[pg_.od_jp].get() : nullptr};
-  if (eod[0]) {
-    for (EdgeSet* e : eod)
-      if ((int)pg_.h_od_vi.size() != e->n)
-        throw StateFailure("pg_linearize: an EdgeSE2OdomDifferentialCalib edge set has grown since pg_set_odom_calib_edges: call it again");
-    pg_od_alias();
+  // the sets of every bound slot, as they were bound
+  EdgeSet* e[kPgSlots][3] = {};
+  for (int k = 0; k < kPgSlots; ++k) {
+    const PgSlot& sl = pg_.slot[k];
+    const PgSlotDesc& ds = kPgSlotDesc[k];
+    if (!sl.bound()) continue;
+    if (ds.points[1] && pg_.points.n <= 0)
+      throw StateFailure("pg_linearize: landmark edges are bound but no landmark estimates (pg_set_landmark_estimates)");
+    for (int q = 0; q < ds.sets; ++q) {
+      e[k][q] = sets_[sl.set[q]].get();
+      if ((int)sl.n() != e[k][q]->n)
+        throw StateFailure(std::string("pg_linearize: ") + ds.words + " has grown since " + ds.entry + " (g2ohip_update_structure): call " +
+                           ds.entry + " again");
+    }
+    if (ds.sets == 3) alias_triple(sl.set);   // (before err_valid / jac_valid are read: a repaired pointer drops the captured launch sequences)
   }
   if (pg_.err_valid && (!jacobians || pg_.jac_valid)) {   // the estimates have not moved since the last evaluation
-    for (EdgeSet* e : ecal)
-      if (jacobians && e) e->has_data = true;
-    for (EdgeSet* e : eod)
-      if (jacobians && e) e->has_data = true;
-    if (jacobians && eo) eo->has_data = true;
-    if (jacobians && eb) eb->has_data = true;
-    if (jacobians) es.has_data = true;
-    if (jacobians && el) el->has_data = true;
-    if (jacobians && ep) ep->has_data = true;
-    if (jacobians && eg) eg->has_data = true;
-    if (jacobians && ec) ec->has_data = true;
-    if (jacobians && esc) esc->has_data = true;
+    for (auto& slot_sets : e)
+      for (EdgeSet* s : slot_sets)
+        if (jacobians && s) s->has_data = true;
     return;
   }
   pg_.err_valid = true;
   if (jacobians) pg_.jac_valid = true;
   chi2_valid_ = false;
+  EdgeSet& es = *e[kPose][0];
+  EdgeSet *const el = e[kLandmark][0], *const ep = e[kPrior][0], *const eg = e[kGicp][0], *const ec = e[kCam][0];
+  EdgeSet *const esc = e[kScale][0], *const eo = e[kOffset][0], *const eb = e[kBearing][0];
+  EdgeSet *const *const ecal = e[kCalib], *const *const eod = e[kOdom];   // (the three sets of each group)
   // (a type-2 set may hold zero edges -- a pure registration, all constraints in the GICP set -- and then launches nothing; so
   // may a type-1 set: the graph of calibration_odom_laser has no EdgeSE2, all constraints in the two calibration groups)
-  if (pg_.type == 1 && es.n > 0)
-    hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
-                       pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  else if (pg_.type == 2 && es.n > 0)
-    hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
-                       pg_.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
-  else if (pg_.type == 10 && es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
+  if (s_pose.type == 1 && es.n > 0)
+    hipLaunchKernelGGL(pg_se2_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, s_pose.v[0].p, s_pose.v[1].p,
+                       s_pose.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
+  else if (s_pose.type == 2 && es.n > 0)
+    hipLaunchKernelGGL(pg_se3_linearize_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, s_pose.v[0].p, s_pose.v[1].p,
+                       s_pose.meas.p, es.own_J0.p, es.own_J1.p, es.own_err.p, jacobians ? 1 : 0);
+  else if (s_pose.type == 10 && es.n > 0) {   // EdgeSim3: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sim3.inc
     prof.begin(KernelProf::kPgSim3Error, st_);
-    hipLaunchKernelGGL(pg_sim3_error_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, pg_.vi.p, pg_.vj.p,
-                       pg_.meas.p, es.own_err.p);
+    hipLaunchKernelGGL(pg_sim3_error_kernel, dim3(grid_for(es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p, s_pose.v[0].p, s_pose.v[1].p,
+                       s_pose.meas.p, es.own_err.p);
     prof.end(KernelProf::kPgSim3Error, st_);
     if (jacobians) {
       prof.begin(KernelProf::kPgSim3Jacobian, st_);
       hipLaunchKernelGGL(pg_sim3_jacobian_kernel, dim3(grid_for(14 * (size_t)es.n)), dim3(kThreads), 0, st_, es.n, pg_.poses.val.p,
-                         pg_.poses.hidx.p, pg_.vi.p, pg_.vj.p, pg_.meas.p, pg_.fix_scale ? 1 : 0, es.own_J0.p, es.own_J1.p);
+                         pg_.poses.hidx.p, s_pose.v[0].p, s_pose.v[1].p, s_pose.meas.p, pg_.fix_scale ? 1 : 0, es.own_J0.p, es.own_J1.p);
       prof.end(KernelProf::kPgSim3Jacobian, st_);
     }
   }
-  const bool lm_launch = el && el->n > 0, pr_launch = ep && ep->n > 0, gicp_launch = eg && eg->n > 0;
-  const bool cam_launch = ec && ec->n > 0, scale_launch = esc && esc->n > 0, off_launch = eo && eo->n > 0;
-  const bool br_launch = eb && eb->n > 0, cal_launch = (ecal[0] && ecal[0]->n > 0) || (eod[0] && eod[0]->n > 0);
+  const auto launches = [&](int k) { return e[k][0] && e[k][0]->n > 0; };
+  bool beside = false;   // anything beside the pose-pose set to launch: one profiling slot for all of it
+  for (int k = kPose + 1; k < kPgSlots; ++k) beside = beside || launches(k);
   const int jac = jacobians ? 1 : 0;
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.begin(KernelProf::kPgLandmark, st_);   // (one slot for what stands beside the pose-pose set)
-  if (lm_launch && pg_.lm_type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
+  if (beside) prof.begin(KernelProf::kPgLandmark, st_);
+  if (launches(kLandmark) && s_lm.type == 11) {   // EdgeSim3ProjectXYZ: the errors by edge, the numeric Jacobian by (edge, column) -- pg_sim3_project.inc
     hipLaunchKernelGGL(pg_sim3_project_error_kernel, dim3(grid_for(el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
-                       pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_err.p);
+                       s_lm.v[0].p, s_lm.v[1].p, s_lm.meas.p, pg_.cam_k.p, el->own_err.p);
     if (jacobians)
       hipLaunchKernelGGL(pg_sim3_project_jacobian_kernel, dim3(grid_for(10 * (size_t)el->n)), dim3(kThreads), 0, st_, el->n, pg_.poses.val.p,
-                         pg_.points.val.p, pg_.poses.hidx.p, pg_.points.hidx.p, pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p,
+                         pg_.points.val.p, pg_.poses.hidx.p, pg_.points.hidx.p, s_lm.v[0].p, s_lm.v[1].p, s_lm.meas.p, pg_.cam_k.p,
                          pg_.fix_scale ? 1 : 0, el->own_J0.p, el->own_J1.p);
-  } else if (lm_launch && pg_cam_landmark(pg_.lm_type)) {   // EdgeProjectP2MC / EdgeProjectP2SC -- pg_cam_project.inc
+  } else if (launches(kLandmark) && pg_cam_landmark(s_lm.type)) {   // EdgeProjectP2MC / EdgeProjectP2SC -- pg_cam_project.inc
     const dim3 grid(grid_for(el->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      with_bool(pg_.lm_type == 14, [&](auto stereo) {
+      with_bool(s_lm.type == 14, [&](auto stereo) {
         constexpr bool STEREO = stereo;
         hipLaunchKernelGGL((pg_cam_project_linearize_kernel<STEREO, STAGED>), grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
-                           pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, pg_.cam_k.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+                           s_lm.v[0].p, s_lm.v[1].p, s_lm.meas.p, pg_.cam_k.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
       });
     });
-  } else if (lm_launch) {
+  } else if (launches(kLandmark)) {
     const dim3 grid(grid_for(el->n)), block(kThreads);
     PgIso off;
     for (int i = 0; i < 12; ++i) off.v[i] = pg_.offset[i];
     const PgKcam kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3]};
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      if (pg_.lm_type == 3)
-        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<STAGED>, grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p, pg_.vp.p,
-                           pg_.vl.p, pg_.lm_meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+      if (s_lm.type == 3)
+        hipLaunchKernelGGL(pg_se2_pointxy_linearize_kernel<STAGED>, grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p, s_lm.v[0].p,
+                           s_lm.v[1].p, s_lm.meas.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
       else
-        dispatch_value<4, 5, 6>(pg_.lm_type, [&](auto obs) {
+        dispatch_value<4, 5, 6>(s_lm.type, [&](auto obs) {
           constexpr int OBS = obs;
           hipLaunchKernelGGL((pg_se3_point_linearize_kernel<OBS, STAGED>), grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
-                             pg_.vp.p, pg_.vl.p, pg_.lm_meas.p, off, kc, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
+                             s_lm.v[0].p, s_lm.v[1].p, s_lm.meas.p, off, kc, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
         });
     });
   }
-  if (pr_launch) {
+  if (launches(kPrior)) {
     const dim3 grid(grid_for(ep->n)), block(kThreads);
     PgIso off;
     for (int i = 0; i < 12; ++i) off.v[i] = pg_.pr_offset[i];
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      if (pg_.pr_type == 9)
-        hipLaunchKernelGGL(pg_se3_prior_linearize_kernel<STAGED>, grid, block, 0, st_, ep->n, pg_.poses.val.p, pg_.vq.p, pg_.pr_meas.p, off,
+      if (s_prior.type == 9)
+        hipLaunchKernelGGL(pg_se3_prior_linearize_kernel<STAGED>, grid, block, 0, st_, ep->n, pg_.poses.val.p, s_prior.v[0].p, s_prior.meas.p, off,
                            ep->own_J0.p, ep->own_err.p, jac);
       else
-        dispatch_value<7, 8>(pg_.pr_type, [&](auto type) {
+        dispatch_value<7, 8>(s_prior.type, [&](auto type) {
           constexpr int TYPE = type;
-          hipLaunchKernelGGL((pg_se2_prior_linearize_kernel<TYPE, STAGED>), grid, block, 0, st_, ep->n, pg_.poses.val.p, pg_.vq.p,
-                             pg_.pr_meas.p, ep->own_J0.p, ep->own_err.p, jac);
+          hipLaunchKernelGGL((pg_se2_prior_linearize_kernel<TYPE, STAGED>), grid, block, 0, st_, ep->n, pg_.poses.val.p, s_prior.v[0].p,
+                             s_prior.meas.p, ep->own_J0.p, ep->own_err.p, jac);
         });
     });
   }
-  if (gicp_launch) {   // Edge_V_V_GICP; plane-to-plane: the set's information is rewritten with every evaluation -- pg_gicp.inc
+  if (launches(kGicp)) {   // Edge_V_V_GICP; plane-to-plane: the set's information is rewritten with every evaluation -- pg_gicp.inc
     const dim3 grid(grid_for(eg->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
       with_bool(pg_.gicp_plpl, [&](auto plpl) {
         constexpr bool PLPL = plpl;
-        hipLaunchKernelGGL((pg_gicp_linearize_kernel<PLPL, STAGED>), grid, block, 0, st_, eg->n, pg_.poses.val.p, pg_.gi.p, pg_.gj.p,
-                           pg_.gicp_meas.p, pg_.gicp_cov.p, eg->own_J0.p, eg->own_J1.p, eg->own_err.p, eg->own_omega.p, jac);
+        hipLaunchKernelGGL((pg_gicp_linearize_kernel<PLPL, STAGED>), grid, block, 0, st_, eg->n, pg_.poses.val.p, s_gicp.v[0].p, s_gicp.v[1].p,
+                           s_gicp.meas.p, pg_.gicp_cov.p, eg->own_J0.p, eg->own_J1.p, eg->own_err.p, eg->own_omega.p, jac);
       });
     });
   }
-  if (cam_launch) {   // EdgeSBACam: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sbacam_edge.inc
-    hipLaunchKernelGGL(pg_sbacam_error_kernel, dim3(grid_for(ec->n)), dim3(kThreads), 0, st_, ec->n, pg_.poses.val.p, pg_.ci.p, pg_.cj.p,
-                       pg_.cam_zinv.p, ec->own_err.p);
+  if (launches(kCam)) {   // EdgeSBACam: the errors by edge, the numeric Jacobian by (edge, side, column) -- pg_sbacam_edge.inc
+    hipLaunchKernelGGL(pg_sbacam_error_kernel, dim3(grid_for(ec->n)), dim3(kThreads), 0, st_, ec->n, pg_.poses.val.p, s_cam.v[0].p, s_cam.v[1].p,
+                       s_cam.meas.p, ec->own_err.p);
     if (jacobians)
       hipLaunchKernelGGL(pg_sbacam_jacobian_kernel, dim3(grid_for(12 * (size_t)ec->n)), dim3(kThreads), 0, st_, ec->n, pg_.poses.val.p,
-                         pg_.poses.hidx.p, pg_.ci.p, pg_.cj.p, pg_.cam_zinv.p, ec->own_J0.p, ec->own_J1.p);
+                         pg_.poses.hidx.p, s_cam.v[0].p, s_cam.v[1].p, s_cam.meas.p, ec->own_J0.p, ec->own_J1.p);
   }
-  if (scale_launch)   // EdgeSBAScale
+  if (launches(kScale))   // EdgeSBAScale
     hipLaunchKernelGGL(pg_sbascale_linearize_kernel, dim3(grid_for(esc->n)), dim3(kThreads), 0, st_, esc->n, pg_.poses.val.p,
-                       pg_.poses.hidx.p, pg_.si.p, pg_.sj.p, pg_.scale_meas.p, esc->own_J0.p, esc->own_J1.p, esc->own_err.p, jac);
-  if (off_launch) {   // EdgeSE2Offset / EdgeSE3Offset -- pg_offset.inc
+                       pg_.poses.hidx.p, s_scale.v[0].p, s_scale.v[1].p, s_scale.meas.p, esc->own_J0.p, esc->own_J1.p, esc->own_err.p, jac);
+  if (launches(kOffset)) {   // EdgeSE2Offset / EdgeSE3Offset -- pg_offset.inc
     const dim3 grid(grid_for(eo->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      if (pg_.off_type == 18)
-        hipLaunchKernelGGL(pg_se2_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, pg_.oi.p, pg_.oj.p, pg_.opf.p,
-                           pg_.opt.p, pg_.off_meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
+      if (s_off.type == 18)
+        hipLaunchKernelGGL(pg_se2_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, s_off.v[0].p, s_off.v[1].p, pg_.opf.p,
+                           pg_.opt.p, s_off.meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
       else
-        hipLaunchKernelGGL(pg_se3_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, pg_.oi.p, pg_.oj.p, pg_.opf.p,
-                           pg_.opt.p, pg_.off_meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
+        hipLaunchKernelGGL(pg_se3_offset_linearize_kernel<STAGED>, grid, block, 0, st_, eo->n, pg_.poses.val.p, s_off.v[0].p, s_off.v[1].p, pg_.opf.p,
+                           pg_.opt.p, s_off.meas.p, pg_.off_table.p, eo->own_J0.p, eo->own_J1.p, eo->own_err.p, jac);
     });
   }
-  if (br_launch) {   // EdgeSE2PointXYBearing -- pg_bearing.inc
+  if (launches(kBearing)) {   // EdgeSE2PointXYBearing -- pg_bearing.inc
     const dim3 grid(grid_for(eb->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      hipLaunchKernelGGL(pg_se2_bearing_linearize_kernel<STAGED>, grid, block, 0, st_, eb->n, pg_.poses.val.p, pg_.points.val.p, pg_.bp.p,
-                         pg_.bl.p, pg_.br_meas.p, eb->own_J0.p, eb->own_J1.p, eb->own_err.p, jac);
+      hipLaunchKernelGGL(pg_se2_bearing_linearize_kernel<STAGED>, grid, block, 0, st_, eb->n, pg_.poses.val.p, pg_.points.val.p, s_bear.v[0].p,
+                         s_bear.v[1].p, s_bear.meas.p, eb->own_J0.p, eb->own_J1.p, eb->own_err.p, jac);
     });
   }
-  if (ecal[0] && ecal[0]->n > 0) {   // EdgeSE2SensorCalib -- pg_calib.inc
+  if (launches(kCalib)) {   // EdgeSE2SensorCalib -- pg_calib.inc
     const dim3 grid(grid_for(ecal[0]->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
-      hipLaunchKernelGGL(pg_se2_calib_linearize_kernel<STAGED>, grid, block, 0, st_, ecal[0]->n, pg_.poses.val.p, pg_.poses.hidx.p, pg_.cal_vi.p,
-                         pg_.cal_vj.p, pg_.cal_vl.p, pg_.cal_meas.p, ecal[0]->own_J0.p, ecal[0]->own_J1.p, ecal[2]->own_J1.p, ecal[0]->own_err.p,
+      hipLaunchKernelGGL(pg_se2_calib_linearize_kernel<STAGED>, grid, block, 0, st_, ecal[0]->n, pg_.poses.val.p, pg_.poses.hidx.p, s_calib.v[0].p,
+                         s_calib.v[1].p, s_calib.v[2].p, s_calib.meas.p, ecal[0]->own_J0.p, ecal[0]->own_J1.p, ecal[2]->own_J1.p, ecal[0]->own_err.p,
                          jac);
     });
   }
-  if (eod[0] && eod[0]->n > 0) {   // EdgeSE2OdomDifferentialCalib -- pg_odom_calib.inc
+  if (launches(kOdom)) {   // EdgeSE2OdomDifferentialCalib -- pg_odom_calib.inc
     const dim3 grid(grid_for(eod[0]->n)), block(kThreads);
     with_bool(pg_landmark_staged, [&](auto staged) {
       constexpr bool STAGED = staged;
       hipLaunchKernelGGL(pg_se2_odom_calib_linearize_kernel<STAGED>, grid, block, 0, st_, eod[0]->n, pg_.poses.val.p, pg_.poses.hidx.p,
-                         pg_.od_vi.p, pg_.od_vj.p, pg_.od_vp.p, pg_.od_meas.p, eod[0]->own_J0.p, eod[0]->own_J1.p, eod[2]->own_J1.p,
+                         s_odom.v[0].p, s_odom.v[1].p, s_odom.v[2].p, s_odom.meas.p, eod[0]->own_J0.p, eod[0]->own_J1.p, eod[2]->own_J1.p,
                          eod[0]->own_err.p, jac);
     });
   }
-  if (lm_launch || pr_launch || gicp_launch || cam_launch || scale_launch || off_launch || br_launch || cal_launch) prof.end(KernelProf::kPgLandmark, st_);
+  if (beside) prof.end(KernelProf::kPgLandmark, st_);
   G2OHIP_HIP_CHECK(hipGetLastError());
-  es.has_err = true;
-  if (jacobians) es.has_data = true;
-  if (el) {
-    el->has_err = true;
-    if (jacobians) el->has_data = true;
-  }
-  if (ep) {
-    ep->has_err = true;
-    if (jacobians) ep->has_data = true;
-  }
-  if (eg) {
-    eg->has_err = true;
-    if (jacobians) eg->has_data = true;
-  }
-  for (EdgeSet* e : {ec, esc, eo, eb, ecal[0], ecal[1], ecal[2], eod[0], eod[1], eod[2]})
-    if (e) {
-      e->has_err = true;
-      if (jacobians) e->has_data = true;
-    }
+  for (auto& slot_sets : e)
+    for (EdgeSet* s : slot_sets)
+      if (s) {
+        s->has_err = true;
+        if (jacobians) s->has_data = true;
+      }
 }
 
 void BlockSolver::pg_update() {
@@ -7111,16 +6773,16 @@ void BlockSolver::pg_update() {
   if (pg_.poses.n <= 0) throw StateFailure("pg_update before pg_set_estimates");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   pg_.err_valid = pg_.jac_valid = false;
-  if (pg_.type == 1 && pg_.od_ij >= 0)   // (rows of VertexOdomDifferentialParams in the table: pg_set_odom_calib_edges)
+  if (pg_.pose_type() == 1 && pg_.slot[kOdom].bound())   // (rows of VertexOdomDifferentialParams in the table: pg_set_odom_calib_edges)
     hipLaunchKernelGGL(pg_se2_update_additive_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, pg_.od_mask.p, d_x.p);
-  else if (pg_.type == 1)
+  else if (pg_.pose_type() == 1)
     hipLaunchKernelGGL(pg_se2_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
-  else if (pg_.type == 2)
+  else if (pg_.pose_type() == 2)
     hipLaunchKernelGGL(pg_se3_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
-  else if (pg_.type == 12)
+  else if (pg_.pose_type() == 12)
     hipLaunchKernelGGL(pg_cam_update_kernel, dim3(grid_for(pg_.poses.n)), dim3(kThreads), 0, st_, pg_.poses.n, pg_.poses.val.p,
                        pg_.poses.hidx.p, d_x.p);
   else
@@ -7238,14 +6900,14 @@ void BlockSolver::device_array(int which, double** ptr, size_t* count) {
     case 106: *ptr = ex_.buf3.p; *count = (size_t)ex_.nh * p_ + 1; break;
     case 107: *ptr = d_mf_diag.p; *count = mf_ready_ ? (size_t)nP_ * p_ * p_ : 0; break;   // schur_operator_prepare: diagonal blocks
     case 108:   // the information matrices of the bound GICP set, [n][3x3]: what the last pg_linearize left there (pg_gicp.inc)
-      if (pg_.gicp_set < 0) throw StateFailure("device_array 108: no GICP set is bound (pg_set_gicp_edges)");
-      *ptr = sets_[pg_.gicp_set]->own_omega.p;
-      *count = pg_.h_gi.size() * 9;
+      if (!pg_.slot[kGicp].bound()) throw StateFailure("device_array 108: no GICP set is bound (pg_set_gicp_edges)");
+      *ptr = sets_[pg_.slot[kGicp].set[0]]->own_omega.p;
+      *count = pg_.slot[kGicp].n() * 9;
       break;
     case 109:   // the inverse measurements of the bound EdgeSBACam set, [n][7], as pg_set_cam_edges computed them (pg_sbacam_edge.inc)
-      if (pg_.cam_set < 0) throw StateFailure("device_array 109: no EdgeSBACam set is bound (pg_set_cam_edges)");
-      *ptr = pg_.cam_zinv.p;
-      *count = pg_.h_ci.size() * 7;
+      if (!pg_.slot[kCam].bound()) throw StateFailure("device_array 109: no EdgeSBACam set is bound (pg_set_cam_edges)");
+      *ptr = pg_.slot[kCam].meas.p;
+      *count = pg_.slot[kCam].n() * 7;
       break;
     default: throw ArgFailure("bad array selector");
   }
