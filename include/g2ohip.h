@@ -655,6 +655,46 @@ int g2ohip_pg_set_sim3_project_edges(g2ohip_solver* s, int set, const int32_t* p
  * these edges on its host path). */
 int g2ohip_pg_set_cam_project_edges(g2ohip_solver* s, int set, int type, const int32_t* pose_vertex, const int32_t* point_vertex,
                                     const double* meas, const double* info, int n_cams, const double* intrinsics);
+/* Stereo bundle adjustment over VertexSE3, the second half of the reference's icp type group: type 23 = Edge_XYZ_VSC
+ * (g2o/types/icp/types_icp.h:376-413 computeError) over a VertexSBAPointXYZ and a VertexSCam (types_icp.h:253-366; mapPoint
+ * :346-361), the edge of g2o/examples/sba/sba_demo.cpp and, beside Edge_V_V_GICP, of g2o/examples/icp/gicp_sba_demo.cpp.  A
+ * VertexSCam IS a VertexSE3: the cameras are rows of the type-2 pose table (isometries [12], camera-to-world) and move by
+ * VertexSE3::oplusImpl; the points are rows of the landmark table.  Bound to the SAME single landmark slot beside a type-2
+ * (EdgeSE3) pose set only, which may hold zero edges (sba_demo has no pose-pose edge: its gauge is two fixed cameras; the set's
+ * array pointers are non-null all the same), on a handle of (pose, landmark) dimensions (6, 3) and a set of error_dim 3.  With
+ * X = (R, t) and the point l:
+ *   q = R' (l - t),   e = ( fx q0 / q2 + cx,  fy q1 / q2 + cy,  fx (q0 - b) / q2 + cx ) - z,   z = (u_left, v_left, u_right)
+ * kcam[5] = fx, fy, cx, cy, baseline b (required, finite, fx and fy not zero): ONE for the whole set -- VertexSCam::Kcam and
+ * VertexSCam::baseline are static members in the reference.  meas [n][3], info [n][3x3].
+ * As in the whole landmark slot vertex 0 of the set is the POSE (the camera) and vertex 1 the landmark -- the reference's edge has
+ * the point as vertex 0 and the camera as vertex 1: J0 is [n][3 x 6] (the reference's _jacobianOplusXj), J1 [n][3 x 3]
+ * (_jacobianOplusXi), column-major; blocks of fixed vertices are written like the others.
+ * DELIBERATE DEVIATION: the reference differentiates this edge numerically (SCAM_ANALYTIC_JACOBIANS is commented out,
+ * types_icp.h:31; base_binary_edge.hpp:132-201, central difference, delta = 1e-9), and the analytic code under that macro
+ * (types_icp.cpp:242-321) belongs to an older parametrisation with world-frame translation -- it is not the derivative through
+ * VertexSE3::oplusImpl (X <- X * fromVectorMQT(u), translation in the camera frame) and is not used.  The device writes the exact
+ * derivative through that oplus, as types 18, 20, 21 and 22 do: with h a column of [-I | 2 [q]x | R'] (3 x 9: pose columns, then
+ * point columns) the output column is
+ *   ( fx (h0 q2 - q0 h2) / q2^2,  fy (h1 q2 - q1 h2) / q2^2,  fx (h0 q2 - (q0 - b) h2) / q2^2 ).
+ * Second deviation: VertexSCam refreshes its cached w2n / w2i in oplusImpl only, so after a pop() the reference's cache lags the
+ * restored estimate; the device always evaluates at the current estimate.  Like the reference there is no guard for a point on
+ * or behind the image plane (q2 <= 0): infinities / NaNs.  The reference registers no .g2o tag for either type and its read /
+ * write return false (types_icp.cpp:323-333): no file format is concerned.
+ * Call after g2ohip_build_structure and g2ohip_pg_set_edges (G2OHIP_ERR_STATE otherwise).  G2OHIP_ERR_ARG: a pose set of a type
+ * other than 2, a set of other dimensions than (3, 6, 3) or a unary one, a set bound in another slot, a null array, a negative
+ * index or one outside the pose or landmark table, a hessian index that differs from the set's, a non-finite measurement,
+ * information or intrinsic, fx == 0 or fy == 0 -- validated before anything is committed: a rejected call leaves the previous
+ * binding usable.  A later call of this or of another landmark entry replaces the binding; g2ohip_clear_edge_sets drops it; a set
+ * grown by g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is bound again.  Everything after
+ * the binding -- g2ohip_pg_set_landmark_estimates, g2ohip_pg_linearize / update / push / pop / discard_top,
+ * g2ohip_pg_get_landmark_estimates, chi2 and robust kernels (set-level and per-edge), do_schur 0 / 1, use_graph -- acts on it
+ * unchanged.  The GICP slot (type 15), the prior slot (type 9) and the offset slot (type 19) are independent of it: any of them
+ * may be bound beside it on one handle.  The kernel (csrc/pg_scam.inc) is timed in the pg_landmark_linearize slot and has the
+ * staged and direct store forms of option pg_landmark_staged.
+ * Not covered: the g2o plugin adapter (it keeps these edges on its host path), sharded solves, per-camera intrinsics (the
+ * reference has none: Kcam and baseline are static), more than one landmark set per handle. */
+int g2ohip_pg_set_scam_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex, const double* meas,
+                             const double* info, const double* kcam);
 /* ---- ... the SBA group's pose-pose constraints: odometry and loop closures between cameras, a known baseline -----------------
  * type 16 = EdgeSBACam (types_sba.h:287-334; tag EDGE_CAM): meas [n][7] = (tx, ty, tz, qx, qy, qz, qw), info [n][6x6], a binary
  *           set of error_dim 6.  e = (delta.t, delta.q.xyz), delta = Zinv * (Ci^-1 * Cj) with SE3Quat::inverse and operator*
@@ -740,8 +780,9 @@ int g2ohip_pg_set_prior_edges(g2ohip_solver* s, int set, int type, const int32_t
  * drops the binding; a GICP set grown by g2ohip_update_structure makes g2ohip_pg_linearize return G2OHIP_ERR_STATE until it is
  * bound again.  The assembly walks the edge list of one Hessian block with a fixed small group of lanes (one lane for an
  * off-diagonal block), in edge order and without a cap on the list's length.
- * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: VertexSCam / Edge_XYZ_VSC, more than one GICP set
- * per handle, sharded solves, the g2o plugin adapter. */
+ * The kernel is timed under the "pg_landmark_linearize" slot.  The other half of the icp group, Edge_XYZ_VSC over VertexSCam,
+ * binds beside it through g2ohip_pg_set_scam_edges (the joint graph of g2o/examples/icp/gicp_sba_demo.cpp).  Not covered: more
+ * than one GICP set per handle, sharded solves, the g2o plugin adapter. */
 int g2ohip_pg_set_gicp_edges(g2ohip_solver* s, int set, const int32_t* vi, const int32_t* vj, const double* meas, const double* info,
                              const double* cov);
 /* ---- ... the pose-pose edges of a multi-sensor rig: relative poses measured between sensor frames mounted off the body -----

@@ -65,7 +65,7 @@ EXPORTS = [
     "g2ohip_pg_set_landmark_camera_edges", "g2ohip_pg_set_prior_edges", "g2ohip_pg_set_sim3_fix_scale",
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
     "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges", "g2ohip_pg_set_bearing_edges",
-    "g2ohip_pg_set_sensor_calib_edges", "g2ohip_pg_set_odom_calib_edges",
+    "g2ohip_pg_set_sensor_calib_edges", "g2ohip_pg_set_odom_calib_edges", "g2ohip_pg_set_scam_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -178,6 +178,7 @@ def load():
     L.g2ohip_pg_set_gicp_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_offset_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]
     L.g2ohip_pg_set_bearing_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_scam_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_sensor_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_odom_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
@@ -872,6 +873,22 @@ class HipBlockSolver:
             raise ValueError("pgSetCamProjectEdges: intrinsics is [n_cams][5] = (fx, fy, cx, cy, baseline)")
         _check(self.L.g2ohip_pg_set_cam_project_edges(self.h, set_id, edge_type, _ip(pv), _ip(lv), _dp(meas), _dp(info), len(kc), _dp(kc)),
                "pgSetCamProjectEdges")
+        self._note_pg_owner(set_id)
+
+    def pgSetScamEdges(self, set_id, pose_vertex, point_vertex, meas, info, kcam):
+        """Stereo observations of 3-D points from VertexSCam cameras (Edge_XYZ_VSC, type 23) beside an EdgeSE3 pose set (type 2,
+        possibly with zero edges), in the landmark slot: pose_vertex indexes the table of pgSetEstimates (the cameras are
+        VertexSE3 isometries), point_vertex the table of pgSetLandmarkEstimates, meas [n][3] = (u_left, v_left, u_right), info
+        [n][3x3], kcam = (fx, fy, cx, cy, baseline), ONE for the whole set.  Vertex 0 of the set is the camera, vertex 1 the
+        point (the reference's edge has them the other way round).  After pgSetEdges."""
+        pv, lv, meas, info = _i32(pose_vertex), _i32(point_vertex), _f64(meas), _f64(info)
+        n = self._set_sizes[set_id]
+        if len(pv) != n or len(lv) != n or meas.size != n * 3 or info.size != n * 9:
+            raise ValueError("pgSetScamEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_id, n))
+        kc = _f64(kcam).reshape(-1)
+        if kc.size != 5:
+            raise ValueError("pgSetScamEdges: kcam is (fx, fy, cx, cy, baseline)")
+        _check(self.L.g2ohip_pg_set_scam_edges(self.h, set_id, _ip(pv), _ip(lv), _dp(meas), _dp(info), _dp(kc)), "pgSetScamEdges")
         self._note_pg_owner(set_id)
 
     def pgSetPriorEdges(self, set_id, edge_type, pose_vertex, meas, info, offset=None):

@@ -114,6 +114,13 @@ class HipBlockSolver {
                                 const double* info, const double* offset, const double* kcam) {
     return ok(g2ohip_pg_set_landmark_camera_edges(h_, set, type, poseVertex, pointVertex, meas, info, offset, kcam), "pgSetLandmarkCameraEdges");
   }
+  // Edge_XYZ_VSC stereo observations (type 23) of VertexSBAPointXYZ points from VertexSCam cameras, kept on the device beside an
+  // EdgeSE3 pose set (type 2, possibly with zero edges) of g2ohip_pg_set_edges (handle()): vertex 0 of the set is the camera,
+  // vertex 1 the point; meas [n][3] = u_left, v_left, u_right; kcam = fx, fy, cx, cy, baseline, one for the whole set
+  bool pgSetScamEdges(int set, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas, const double* info,
+                      const double* kcam) {
+    return ok(g2ohip_pg_set_scam_edges(h_, set, poseVertex, pointVertex, meas, info, kcam), "pgSetScamEdges");
+  }
   // EdgeSim3ProjectXYZ observations (type 11) beside an EdgeSim3 pose set (type 10) of g2ohip_pg_set_edges (handle()): vertex 0 of
   // the set is the pose, vertex 1 the point; intrinsics [nCams][4] = fx, fy, cx, cy per entry of the pose table
   bool pgSetSim3ProjectEdges(int set, const int32_t* poseVertex, const int32_t* pointVertex, const double* meas, const double* info,

@@ -105,6 +105,8 @@ class BlockSolver {
                                  int n_cams, const double* intrinsics);
   void pg_set_cam_project_edges(int set, int type, const int* pose_vertex, const int* point_vertex, const double* meas,
                                 const double* info, int n_cams, const double* intrinsics);
+  void pg_set_scam_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
+                         const double* kcam);
   void pg_set_prior_edges(int set, int type, const int* pose_vertex, const double* meas, const double* info, const double* offset);
   void pg_set_gicp_edges(int set, const int* vi, const int* vj, const double* meas, const double* info, const double* cov);
   void pg_set_offset_edges(int set, int type, const int* vi, const int* vj, const int* param_from, const int* param_to, const double* meas,
@@ -525,7 +527,8 @@ class BlockSolver {
     // one ParameterSE3Offset (beside type 2, landmarks (x, y, z)), 5 = EdgeSE3PointXYZDepth, 6 = EdgeSE3PointXYZDisparity with one
     // ParameterCamera (offset + Kcam; beside type 2, pg_set_landmark_camera_edges), 11 = EdgeSim3ProjectXYZ (beside type 10, one
     // (fx, fy, cx, cy) per entry of the pose table; pg_set_sim3_project_edges), 13 = EdgeProjectP2MC, 14 = EdgeProjectP2SC
-    // (beside type 12, one (fx, fy, cx, cy, baseline) per entry of the pose table; pg_set_cam_project_edges).  Vertex 0 of an
+    // (beside type 12, one (fx, fy, cx, cy, baseline) per entry of the pose table; pg_set_cam_project_edges), 23 = Edge_XYZ_VSC
+    // over VertexSCam (beside type 2, ONE (fx, fy, cx, cy, baseline) for the set; pg_set_scam_edges, pg_scam.inc).  Vertex 0 of an
     // observation is the pose (v[0] into `poses`), vertex 1 the landmark (v[1] into `points`); points.hidx[v] is the landmark's
     // index in the whole system (num_poses + its landmark number) or -1 when it is fixed.
     kLandmark,
@@ -604,7 +607,8 @@ class BlockSolver {
     bool err_valid = false, jac_valid = false;
     // the landmark slot
     double offset[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // ParameterSE3Offset of the set (type 4), the offset of its ParameterCamera (5, 6)
-    double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy
+    double kcam[4] = {1, 1, 0, 0};                              // ... and that camera's fx, fy, cx, cy; type 23: VertexSCam::Kcam
+    double baseline = 0.0;                                      // type 23: VertexSCam::baseline
     DevBuf<double> cam_k;          // type 11: (fx, fy, cx, cy) of every entry of `poses` (VertexSim3Expmap::_focal_length,
     int n_cams = 0;                // _principle_point), n_cams entries: == poses.n whenever both are bound; types 13 / 14: (fx,
                                    // fy, cx, cy, baseline) (SBACam::Kcam, baseline)

@@ -2330,6 +2330,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_bearing.inc"
 #include "pg_calib.inc"
 #include "pg_odom_calib.inc"
+#include "pg_scam.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
@@ -6000,7 +6001,7 @@ constexpr BlockSolver::PgSlotDesc BlockSolver::kPgSlotDesc[BlockSolver::kPgSlots
 static int pg_pose_type_beside(int edge_type) {
   switch (edge_type) {
     case 3: case 7: case 8: case 18: case 20: case 21: case 22: return 1;
-    case 4: case 5: case 6: case 9: case 15: case 19: return 2;
+    case 4: case 5: case 6: case 9: case 15: case 19: case 23: return 2;
     case 11: return 10;
     default: return 12;   // 13, 14, 16, 17
   }
@@ -6010,8 +6011,8 @@ static const char* pg_edge_type_words(int edge_type) {
                                       "EdgeSE2Prior (7)", "EdgeSE2XYPrior (8)", "EdgeSE3Prior (9)", "EdgeSim3 (10)", "EdgeSim3ProjectXYZ (11)",
                                       "VertexCam (12)", "EdgeProjectP2MC (13)", "EdgeProjectP2SC (14)", "Edge_V_V_GICP (15)", "EdgeSBACam (16)",
                                       "EdgeSBAScale (17)", "EdgeSE2Offset (18)", "EdgeSE3Offset (19)", "EdgeSE2PointXYBearing (20)",
-                                      "EdgeSE2SensorCalib (21)", "EdgeSE2OdomDifferentialCalib (22)"};
-  return edge_type >= 3 && edge_type <= 22 ? words[edge_type - 3] : "?";
+                                      "EdgeSE2SensorCalib (21)", "EdgeSE2OdomDifferentialCalib (22)", "Edge_XYZ_VSC (23)"};
+  return edge_type >= 3 && edge_type <= 23 ? words[edge_type - 3] : "?";
 }
 static const char* pg_pose_type_words(int type) {
   return type == 1 ? "an EdgeSE2 pose set (1)" : type == 2 ? "an EdgeSE3 pose set (2)" : type == 10 ? "an EdgeSim3 pose set (10)" : "a VertexCam set (12)";
@@ -6256,8 +6257,29 @@ void BlockSolver::pg_set_cam_project_edges(int set, int type, const int* pose_ve
   pg_bind_landmark_edges("pg_set_cam_project_edges", set, type, pose_vertex, point_vertex, meas, info, nullptr, intrinsics, n_cams);
 }
 
-// what the four entries share: the set's dimensions, index validation, the uploads (types 11 and 13 / 14: kcam is the table
-// [n_cams][4] and [n_cams][5])
+// Edge_XYZ_VSC (23) beside an EdgeSE3 pose set (2), which may hold zero edges: the stereo projection of a VertexSBAPointXYZ into
+// the VertexSCam pose_vertex[k] (a VertexSE3), ONE kcam = (fx, fy, cx, cy, baseline) for the whole set (pg_scam.inc)
+void BlockSolver::pg_set_scam_edges(int set, const int* pose_vertex, const int* point_vertex, const double* meas, const double* info,
+                                    const double* kcam) {
+  pg_begin_bind("pg_set_scam_edges", kLandmark, {set});
+  if (pg_.pose_type() != 2) throw ArgFailure("pg_set_scam_edges: Edge_XYZ_VSC (23) goes with an EdgeSE3 pose set (2)");
+  if (!kcam) throw ArgFailure("pg_set_scam_edges: null kcam (fx, fy, cx, cy, baseline)");
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(kcam[i])) throw ArgFailure("pg_set_scam_edges: non-finite camera intrinsics");
+  if (kcam[0] == 0.0 || kcam[1] == 0.0) throw ArgFailure("pg_set_scam_edges: fx and fy must not be zero");
+  const EdgeSet& es = *sets_[set];
+  if (!es.unary && es.d == 3 && meas && info)
+    for (size_t k = 0; k < (size_t)es.n; ++k) {
+      for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(meas[3 * k + i])) throw ArgFailure("pg_set_scam_edges: non-finite measurement in edge " + std::to_string(k));
+      for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(info[9 * k + i])) throw ArgFailure("pg_set_scam_edges: non-finite information in edge " + std::to_string(k));
+    }
+  pg_bind_landmark_edges("pg_set_scam_edges", set, 23, pose_vertex, point_vertex, meas, info, nullptr, kcam);
+}
+
+// what the five entries share: the set's dimensions, index validation, the uploads (types 11 and 13 / 14: kcam is the table
+// [n_cams][4] and [n_cams][5]; type 23: kcam[4] is the baseline)
 void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, const int* pose_vertex, const int* point_vertex,
                                          const double* meas, const double* info, const double* offset, const double* kcam, int n_cams) {
   const std::string w(who);
@@ -6278,6 +6300,7 @@ void BlockSolver::pg_bind_landmark_edges(const char* who, int set, int type, con
       if (pose_vertex[k] >= n_cams) throw ArgFailure(w + ": pose index of landmark edge " + std::to_string(k) + " outside the intrinsics table");
   for (int i = 0; i < 12; ++i) pg_.offset[i] = offset ? offset[i] : (i % 4 == 0 && i < 9 ? 1.0 : 0.0);
   for (int i = 0; i < 4; ++i) pg_.kcam[i] = (kcam && !table) ? kcam[i] : (i < 2 ? 1.0 : 0.0);
+  pg_.baseline = type == 23 ? kcam[4] : 0.0;
   pg_.n_cams = table ? n_cams : 0;
   if (table) pg_.cam_k.upload(kcam, ks * (size_t)n_cams, st_);
   pg_commit(kLandmark, {set}, type, {pose_vertex, point_vertex}, n, meas, d, d, dp, dl, info);
@@ -6663,6 +6686,14 @@ void BlockSolver::pg_linearize(bool jacobians) {
         hipLaunchKernelGGL((pg_cam_project_linearize_kernel<STEREO, STAGED>), grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p,
                            s_lm.v[0].p, s_lm.v[1].p, s_lm.meas.p, pg_.cam_k.p, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
       });
+    });
+  } else if (launches(kLandmark) && s_lm.type == 23) {   // Edge_XYZ_VSC -- pg_scam.inc
+    const dim3 grid(grid_for(el->n)), block(kThreads);
+    const PgScamK kc = {pg_.kcam[0], pg_.kcam[1], pg_.kcam[2], pg_.kcam[3], pg_.baseline};
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      hipLaunchKernelGGL(pg_scam_linearize_kernel<STAGED>, grid, block, 0, st_, el->n, pg_.poses.val.p, pg_.points.val.p, s_lm.v[0].p,
+                         s_lm.v[1].p, s_lm.meas.p, kc, el->own_J0.p, el->own_J1.p, el->own_err.p, jac);
     });
   } else if (launches(kLandmark)) {
     const dim3 grid(grid_for(el->n)), block(kThreads);

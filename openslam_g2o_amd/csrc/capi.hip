@@ -712,6 +712,10 @@ int g2ohip_pg_set_offset_edges(g2ohip_solver* s, int set, int type, const int32_
                                const int32_t* param_to, const double* meas, const double* info, int n_params, const double* offsets) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_offset_edges(set, type, vi, vj, param_from, param_to, meas, info, n_params, offsets); });
 }
+int g2ohip_pg_set_scam_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex, const double* meas,
+                             const double* info, const double* kcam) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_scam_edges(set, pose_vertex, point_vertex, meas, info, kcam); });
+}
 int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex, const double* meas,
                                 const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_bearing_edges(set, pose_vertex, point_vertex, meas, info); });

@@ -474,7 +474,14 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     solver.prior_set = its set id.  A prob of kind "se2" that carries bp, bl, zb and omega_b (synthetic.make_bearing_slam,
     g2o_io.bearing_problem) also gets its bearing-only observations bound (EdgeSE2PointXYBearing over the same landmark table):
     solver.bearing_set = their set id, huber_delta applies to them as well; the EdgeSE2PointXY set is then added only if
-    prob["vp"] is present and non-empty (bearing-only SLAM otherwise: solver.landmark_sets = (odometry set id, None))."""
+    prob["vp"] is present and non-empty (bearing-only SLAM otherwise: solver.landmark_sets = (odometry set id, None)).
+    A prob of kind "se3" with observation = "stereo_vsc" and kcam = (fx, fy, cx, cy, baseline) (synthetic.make_scam_ba: the graph
+    of g2o/examples/sba/sba_demo.cpp) has its observations bound as Edge_XYZ_VSC over VertexSCam cameras (pgSetScamEdges); the
+    EdgeSE3 set vi / vj / Z / omega may be empty (the gauge is then held by fixed cameras or by priors).  If it also carries gi,
+    gj, gmeas and ginfo (and gcov or None) -- the keys setup_device_gicp reads; the graph of g2o/examples/icp/gicp_sba_demo.cpp --
+    the Edge_V_V_GICP correspondences are bound beside them on the same handle: solver.gicp_set = their set id (no kernel on
+    them).  A prob that carries offset_edges = (19, vi, vj, pfrom, pto, meas, info, offsets) gets that EdgeSE3Offset set bound as
+    well: solver.offset_set = its set id."""
     import numpy as np
     from . import capi
     se2 = prob["kind"] == "se2"
@@ -483,6 +490,11 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     obs = prob.get("observation", "xyz")
     if obs in ("depth", "disparity") and prob.get("kcam") is None:
         raise ValueError("setup_device_landmark_slam: observation = %r needs kcam = (fx, fy, cx, cy)" % obs)
+    scam = obs == "stereo_vsc"
+    if scam and (se2 or prob.get("kcam") is None or np.asarray(prob["kcam"]).size != 5):
+        raise ValueError("setup_device_landmark_slam: observation = 'stereo_vsc' needs kind 'se3' and kcam = (fx, fy, cx, cy, baseline)")
+    gicp = scam and all(prob.get(k) is not None for k in ("gi", "gj", "gmeas", "ginfo"))
+    offs = prob.get("offset_edges") if scam else None
     p, l = (3, 2) if se2 else (6, 3)
     s = capi.HipBlockSolver(p, l, device)
     for name, value in (options or {}).items():
@@ -496,10 +508,24 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     if prior is not None:
         ptype = 9 if not se2 else (8 if prior == "xy" else 7)
         kq = s.addEdgeSet(PRIOR_ERROR_DIM[ptype], hidx[prob["vq"]], None)
+    if gicp:
+        kg = s.addEdgeSet(3, hidx[np.asarray(prob["gi"], np.int64)], hidx[np.asarray(prob["gj"], np.int64)])
+    if offs is not None:
+        ko = s.addEdgeSet(6, hidx[np.asarray(offs[1], np.int64)], hidx[np.asarray(offs[2], np.int64)])
     s.buildStructure(prob["nP"], prob["nL"], schur)
-    s.pgSetEdges(k0, 1 if se2 else 2, prob["vi"], prob["vj"], prob["Z"], prob["omega"])
+    if scam:   # (the EdgeSE3 set may be empty: its arrays still have their shapes)
+        s.pgSetEdges(k0, 2, prob["vi"], prob["vj"], np.asarray(prob["Z"], np.float64).reshape(-1, 12),
+                     np.asarray(prob["omega"], np.float64).reshape(-1, 36))
+    else:
+        s.pgSetEdges(k0, 1 if se2 else 2, prob["vi"], prob["vj"], prob["Z"], prob["omega"])
     s.pgSetEstimates(prob["poses"], hidx)
-    if obs in ("depth", "disparity"):
+    if scam:
+        s.pgSetScamEdges(k1, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob["kcam"])
+        if gicp:
+            s.pgSetGicpEdges(kg, prob["gi"], prob["gj"], prob["gmeas"], prob["ginfo"], prob.get("gcov"))
+        if offs is not None:
+            s.pgSetOffsetEdges(ko, *offs)
+    elif obs in ("depth", "disparity"):
         s.pgSetLandmarkCameraEdges(k1, 5 if obs == "depth" else 6, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"],
                                    prob.get("offset"), prob["kcam"])
     elif with_xy:

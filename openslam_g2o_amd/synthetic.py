@@ -1164,3 +1164,104 @@ def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.
     return dict(kind="se2", n=n + 1, n_poses=n, offset_row=n, nP=n - 1 + (0 if fix_offset else 1), poses=poses,
                 poses_true=np.concatenate([X, Lt]), hidx=hidx, vi=vi, vj=vj, Z=Z0, omega=np.tile(w.reshape(1, 9), (n - 1, 1)), ci=ci, cj=cj,
                 cl=np.full(m, n, np.int32), cmeas=Zc, cinfo=np.tile(w.reshape(1, 9), (m, 1)), offset_true=Lt[0].copy())
+
+
+SCAM_KCAM = (500.0, 500.0, 320.0, 240.0, 0.075)   # sba_demo.cpp:189-191: focal length, principal point (640 x 480 image), baseline
+
+
+def make_scam_ba(n_cams, n_points, fixed=2, gicp=False, outlier_frac=0.0, seed=0, pixel_noise=1.0, point_noise=1.0, spacing=0.04,
+                 perturb=(0.0, 0.0), fixed_points=0, gicp_pts_per_pair=20, gicp_noise=(0.01, 0.01), epsilon=0.01):
+    """Stereo bundle adjustment with Edge_XYZ_VSC between VertexSCam cameras and VertexSBAPointXYZ points, after
+    g2o/examples/sba/sba_demo.cpp:179-341 at any size: n_cams cameras on a line (camera i at (i * spacing - 1, 0, 0), identity
+    rotation, looking down +z; the first `fixed` of them are fixed -- the gauge, there is no pose-pose edge), n_points candidate
+    points 10 to 11 units ahead (x over the cameras' span widened by 0.5 to the left and 2.5 to the right, y in [-0.5, 0.5]), ONE
+    kcam = SCAM_KCAM = (fx, fy, cx, cy, baseline) = (500, 500, 320, 240, 0.075) for all cameras.  A camera observes a point when
+    the left projection lies inside the 640 x 480 image (0 <= u < 640, 0 <= v < 480); points seen by fewer than two cameras are
+    dropped and the table is renumbered.  Measurements (u_left, v_left, u_right) = VertexSCam::mapPoint of the true point +
+    pixel_noise * N(0, 1) on the first two rows and pixel_noise / 16 * N(0, 1) on the third; a fraction outlier_frac of them is
+    first replaced by (U(64, 640), U(0, 480), u - U(0, 64)) as the demo does.  Information: the identity.  Initial estimates: the
+    points at the truth + point_noise * N(0, 1) per coordinate, the free cameras at the truth multiplied from the right by a motion
+    of perturb[0] * N(0, 1) in t and the rotation vector perturb[1] * N(0, 1) (the demo: none).  The first fixed_points points
+    are fixed.  Edges are point-major, cameras ascending within a point.
+    gicp=True (the graph of g2o/examples/icp/gicp_sba_demo.cpp): gicp_pts_per_pair Edge_V_V_GICP correspondences between every two
+    consecutive cameras, as make_gicp makes them (points on its planes seen from both cameras with gicp_noise = (point, normal)
+    sigma, point-to-plane information EdgeGICP::prec0(epsilon)); the dict then also carries gi, gj, gmeas, ginfo, gcov = None,
+    normal0, normal1 -- the keys lm.setup_device_gicp reads.
+    Returns kind = "se3", observation = "stereo_vsc", kcam [5], n, nP, L, nL, M, E = 0, poses [n][12], poses_true, hidx, points
+    [L][3], points_true, pt_hidx, vp, vl, zl [M][3], omega_l [M][9], outlier [M] (bool) and an EMPTY EdgeSE3 set vi, vj, Z [0][12],
+    omega [0][36].  Deterministic from seed (counter-based RNG)."""
+    n, L0, fixed = int(n_cams), int(n_points), int(fixed)
+    if n < 2 or L0 < 1 or not 1 <= fixed < n:
+        raise ValueError("make_scam_ba: at least two cameras, one point and 1 <= fixed < n_cams")
+    rng = CounterRng(seed + 7)
+    fx, fy, cx, cy, b = SCAM_KCAM
+    tx = np.arange(n) * float(spacing) - 1.0
+    span = tx[-1] - tx[0]
+    P = np.stack([tx[0] - 0.5 + rng.uniform(1, L0) * (span + 3.0), rng.uniform(2, L0) - 0.5, rng.uniform(3, L0) + 10.0], axis=1)
+    # the cameras that see a point form a range of the line: candidates from the pinhole bounds, one camera wider on either side,
+    # then the projection itself decides
+    lo = np.floor((P[:, 0] - (640.0 - cx) * P[:, 2] / fx - tx[0]) / spacing).astype(np.int64) - 1
+    hi = np.ceil((P[:, 0] + cx * P[:, 2] / fx - tx[0]) / spacing).astype(np.int64) + 1
+    lo, hi = np.clip(lo, 0, n), np.clip(hi + 1, 0, n)
+    cnt = np.maximum(hi - lo, 0)
+    pl = np.repeat(np.arange(L0), cnt)
+    pc = (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(lo, cnt)).astype(np.int64)
+
+    def project(X, cams):
+        q0, q1, q2 = X[:, 0] - tx[cams], X[:, 1], X[:, 2]
+        return np.stack([fx * q0 / q2 + cx, fy * q1 / q2 + cy, fx * (q0 - b) / q2 + cx], axis=1)
+    z = project(P[pl], pc)
+    inside = (z[:, 0] >= 0) & (z[:, 1] >= 0) & (z[:, 0] < 640) & (z[:, 1] < 480)
+    pl, pc, z = pl[inside], pc[inside], z[inside]
+    keep = np.bincount(pl, minlength=L0) >= 2
+    sel = keep[pl]
+    pl, pc, z = pl[sel], pc[sel], z[sel]
+    L = int(keep.sum())
+    if L <= int(fixed_points):
+        raise ValueError("make_scam_ba: fewer points seen by two cameras than fixed_points + 1")
+    renum = np.cumsum(keep) - 1
+    vl, vp = renum[pl].astype(np.int32), pc.astype(np.int32)
+    pts_true = P[keep]
+    M = len(vp)
+    outlier = rng.uniform(4, M) < outlier_frac
+    zo = np.stack([64.0 + 576.0 * rng.uniform(5, M), 480.0 * rng.uniform(6, M), 64.0 * rng.uniform(7, M)], axis=1)
+    zo[:, 2] = zo[:, 0] - zo[:, 2]
+    z = np.where(outlier[:, None], zo, z)
+    z = z + pixel_noise * np.stack([rng.normal(8, M), rng.normal(9, M), rng.normal(10, M) / 16.0], axis=1)
+    pts = pts_true + point_noise * np.stack([rng.normal(11 + c, L) for c in range(3)], axis=1)
+    t = np.stack([tx, np.zeros(n), np.zeros(n)], axis=1)
+    R = np.tile(np.eye(3)[None], (n, 1, 1))
+    step = np.concatenate([perturb[0] * np.stack([rng.normal(14 + c, n) for c in range(3)], axis=1),
+                           perturb[1] * np.stack([rng.normal(17 + c, n) for c in range(3)], axis=1)], axis=1)
+    step[:fixed] = 0.0
+    Re, te = R @ _exp_so3(step[:, 3:])[0], np.einsum("nij,nj->ni", R, step[:, :3]) + t
+    hidx = np.where(np.arange(n) < fixed, -1, np.arange(n) - fixed).astype(np.int32)
+    nL = L - int(fixed_points)
+    pt_hidx = np.where(np.arange(L) < int(fixed_points), -1, n - fixed + np.arange(L) - int(fixed_points)).astype(np.int32)
+    out = dict(kind="se3", observation="stereo_vsc", kcam=np.array(SCAM_KCAM), n=n, nP=n - fixed, L=L, nL=nL, M=M, E=0,
+               poses=_iso_pack(Re, te), poses_true=_iso_pack(R, t), hidx=hidx, points=pts, points_true=pts_true, pt_hidx=pt_hidx,
+               vp=vp, vl=vl, zl=z, omega_l=np.tile(np.eye(3).reshape(1, 9), (M, 1)), outlier=outlier, vi=np.zeros(0, np.int32),
+               vj=np.zeros(0, np.int32), Z=np.zeros((0, 12)), omega=np.zeros((0, 36)))
+    if gicp:
+        from . import gicp as G
+        m = (n - 1) * int(gicp_pts_per_pair)
+        gi = np.repeat(np.arange(n - 1, dtype=np.int32), int(gicp_pts_per_pair))
+        gj = gi + 1
+        nrm = _GICP_PLANES[:, :3] / np.linalg.norm(_GICP_PLANES[:, :3], axis=1, keepdims=True)
+        pln = np.minimum((rng.uniform(20, m) * len(nrm)).astype(np.int64), len(nrm) - 1)
+        n_w = nrm[pln]
+        e1 = np.cross(n_w, [0.0, 1.0, 0.3])
+        e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+        e2 = np.cross(n_w, e1)
+        x_w = n_w * _GICP_PLANES[pln, 3:4] + e1 * (4.0 * rng.uniform(21, m) - 2.0)[:, None] + e2 * (4.0 * rng.uniform(22, m) - 2.0)[:, None]
+
+        def seen(v, k0):   # (identity rotations)
+            p = x_w - t[v] + gicp_noise[0] * np.stack([rng.normal(k0 + c, m) for c in range(3)], axis=1)
+            nn = n_w + gicp_noise[1] * np.stack([rng.normal(k0 + 3 + c, m) for c in range(3)], axis=1)
+            return p, nn / np.linalg.norm(nn, axis=1, keepdims=True)
+        pos0, normal0 = seen(gi, 30)
+        pos1, normal1 = seen(gj, 40)
+        out.update(gi=gi, gj=gj.astype(np.int32), gmeas=np.concatenate([pos0, pos1], axis=1),
+                   ginfo=np.stack([G.prec(nv, epsilon).T.reshape(9) for nv in normal0]), gcov=None, normal0=normal0, normal1=normal1,
+                   plane_to_plane=False)
+    return out
