@@ -846,8 +846,8 @@ int g2ohip_pg_set_offset_edges(g2ohip_solver* s, int set, int type, const int32_
  * The kernel is timed under the "pg_landmark_linearize" slot.  Not covered: EdgeSE2PointXYOffset (in the reference its
  * computeError reads the cache's w2lMatrix, the inverse of the vertex estimate WITHOUT the offset, while its linearizeOplus mixes
  * the offset's rotation into one column, parameter_se2_offset.cpp:87-96: which of the two is meant has to be decided first),
- * EdgeSE2PointXYCalib, more than one bearing set per handle, sharded solves, the g2o plugin adapter, a 3-D counterpart (the
- * reference has none). */
+ * more than one bearing set per handle, sharded solves, the g2o plugin adapter, a 3-D counterpart (the reference has none).
+ * EdgeSE2PointXYCalib: g2ohip_pg_set_pointxy_calib_edges below. */
 int g2ohip_pg_set_bearing_edges(g2ohip_solver* s, int set, const int32_t* pose_vertex, const int32_t* point_vertex,
                                 const double* meas, const double* info);
 /* ---- ... laser self-calibration (sclam2d): scan-match constraints that also estimate the sensor's mounting offset -----------
@@ -941,6 +941,52 @@ int g2ohip_pg_set_sensor_calib_edges(g2ohip_solver* s, int set_ij, int set_il, i
 int g2ohip_pg_set_odom_calib_edges(g2ohip_solver* s, int set_ij, int set_ip, int set_jp, const int32_t* vi, const int32_t* vj,
                                    const int32_t* vp, const double* meas /* [n][3] = vl, vr, dt */,
                                    const double* info /* [n][3x3], NULL = identity */);
+/* ---- ... landmark self-calibration (slam2d): point observations that also estimate the sensor's mounting offset ---------------
+ * ONE group of EdgeSE2PointXYCalib (type 24; tag EDGE_SE2_XY_CALIB, g2o/types/slam2d/edge_se2_pointxy_calib.h:46-52 computeError,
+ * edge_se2_pointxy_calib.cpp read / write): a THREE-vertex edge over a VertexSE2 pose x1 = (t1, th1), a VertexPointXY landmark l
+ * and the calibration c = (tc, thc), an ordinary VertexSE2.  The pose and the calibration vertex are rows of the pose table of
+ * g2ohip_pg_set_estimates -- so g2ohip_pg_update / push / pop / discard_top / get_estimates carry c like any pose --, the landmark
+ * is a row of the landmark table of g2ohip_pg_set_landmark_estimates: the one group that spans both tables.  Beside a type-1 pose
+ * set only (which may hold ZERO edges), in a slot of its own: independent of the landmark (type 3), prior, offset, bearing, type-21
+ * and type-22 slots, all of which read the one landmark table and the one pose table; a later call replaces the binding.
+ *   a = x1 * c,  w = a^-1,  e = R(w.th) l + w.t - z        (error dimension 2; SE2's product and inverse with normalize_theta, se2.h)
+ * DELIBERATE DEVIATION: the reference defines no linearizeOplus for this edge and differentiates numerically
+ * (base_multi_edge.hpp:63-116, central difference, delta = 1e-9); the device writes the exact derivative with respect to
+ * VertexSE2::oplusImpl (t += u[0:2], th += u[2]) and VertexPointXY::oplusImpl, as for types 7, 18, 20, 21 and 22: with
+ * Q = R(-(th1 + thc)), J = [0 -1; 1 0], d = l - t1 - R(th1) tc
+ *   d e / d t1 = -Q          d e / d th1 = -J Q d - Q J R(th1) tc        (J_pose  2 x 3)
+ *   d e / d l  =  Q                                                      (J_point 2 x 2)
+ *   d e / d tc = -R(-thc)    d e / d thc = -J Q d                        (J_calib 2 x 3)
+ * The Jacobian block of a fixed vertex (hessian index -1) is written as zeros.  No guard beyond the reference's.
+ * The edge is the three binary sets of g2ohip_set_edge_set_parts, added by the caller with error_dim 2 over the vertices' hessian
+ * indices (-1 = fixed), all of the same edge count, on a handle of (pose, landmark) dimensions (3, 2):
+ *   set_pl  (v0 = pose,     v1 = landmark)  parts 0                                                         dims (3, 2)
+ *   set_pc  (v0 = pose,     v1 = calib)     parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_VERTEX1 | G2OHIP_PART_NO_CHI2  dims (3, 3)
+ *   set_lc  (v0 = landmark, v1 = calib)     parts G2OHIP_PART_NO_VERTEX0 | G2OHIP_PART_NO_CHI2              dims (2, 3)
+ * (the generic assembly takes the landmark on either side of a set; a set all of whose landmarks are fixed has no landmark
+ * dimension and is refused).  They are bound and released as one group and share their buffers on the device: set_pl owns J_pose,
+ * J_point, the information and the errors, set_lc owns J_calib, every other pointer aliases one of those (18 + 2 doubles per edge
+ * leave the producer).  pose_vertex / calib_vertex index the pose table, point_vertex the landmark table; meas [n][2]; info
+ * [n][2x2], NULL = identity.  Robust kernels: set the same kernel on all three sets.  The calibration vertex is a neighbour of
+ * every edge: the pose Hessian gets a dense block row, and Hpl a dense row of (calib, landmark) blocks, each with as many terms as
+ * the landmark has observations (the generic (3, 2) Schur path has no cap on the edges of a vertex pair).
+ * G2OHIP_ERR_STATE: a call before g2ohip_build_structure or before g2ohip_pg_set_edges, a set that carries per-edge robust
+ * kernels.  G2OHIP_ERR_ARG: a bad or repeated set id, a set bound in another slot, a pose set of a type other than 1, wrong
+ * dimensions, parts or edge counts, a unary set, null pose_vertex / point_vertex / calib_vertex / meas, a non-finite value, an
+ * index outside its table, a hessian index that differs from the sets' own (pose and calibration vertex against the pose table's,
+ * the landmark against the landmark table's), pose_vertex[k] == calib_vertex[k], a pose or calibration row that is an additive
+ * row of a bound type-22 group (and that group's entry refuses a parameter row this group reads) -- validated before anything is
+ * committed: a rejected call leaves the previous binding usable.  While the group is bound the other g2ohip_pg_set_* entries
+ * refuse its set ids and g2ohip_pg_set_edges refuses pose types other than 1.  g2ohip_pg_linearize without a landmark table
+ * returns G2OHIP_ERR_STATE.  g2ohip_pg_set_estimates / g2ohip_pg_set_landmark_estimates with changed tables validate the group
+ * again; g2ohip_clear_edge_sets drops the binding.  g2ohip_update_structure refuses structures with landmarks, so the group
+ * cannot grow.  Captured launch sequences (use_graph) are dropped at binding and at release.  With do_schur = 0 the solver
+ * factorises Hpp alone, as for every landmark set.  The kernel is timed under the "pg_landmark_linearize" slot.
+ * Not covered: EdgeSE2PointXYOffset (see g2ohip_pg_set_bearing_edges), more than one such group per handle, sharded solves, the
+ * g2o plugin adapter. */
+int g2ohip_pg_set_pointxy_calib_edges(g2ohip_solver* s, int set_pl, int set_pc, int set_lc, const int32_t* pose_vertex,
+                                      const int32_t* point_vertex, const int32_t* calib_vertex, const double* meas /* [n][2] */,
+                                      const double* info /* [n][2x2], NULL = identity */);
 int g2ohip_pg_set_landmark_estimates(g2ohip_solver* s, int n_points, const double* points, const int32_t* hidx);
 int g2ohip_pg_get_landmark_estimates(g2ohip_solver* s, double* points);
 

@@ -66,6 +66,7 @@ EXPORTS = [
     "g2ohip_pg_set_sim3_project_edges", "g2ohip_pg_set_cam_project_edges", "g2ohip_pg_set_gicp_edges",
     "g2ohip_pg_set_cam_edges", "g2ohip_pg_set_offset_edges", "g2ohip_pg_set_bearing_edges",
     "g2ohip_pg_set_sensor_calib_edges", "g2ohip_pg_set_odom_calib_edges", "g2ohip_pg_set_scam_edges",
+    "g2ohip_pg_set_pointxy_calib_edges",
     "g2ohip_compute_marginals", "g2ohip_set_x", "g2ohip_copy_diagonal",
     "g2ohip_comm_unique_id", "g2ohip_comm_init_rccl", "g2ohip_comm_init_host", "g2ohip_comm_init_peer", "g2ohip_comm_destroy", "g2ohip_comm_all_reduce",
     "g2ohip_update_structure", "g2ohip_clear_edge_sets", "g2ohip_solve_sharded", "g2ohip_chi2_sharded", "g2ohip_max_diagonal_sharded", "g2ohip_compute_scale_sharded",
@@ -181,6 +182,7 @@ def load():
     L.g2ohip_pg_set_scam_edges.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_sensor_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_odom_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
+    L.g2ohip_pg_set_pointxy_calib_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_cam_edges.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p]
     L.g2ohip_pg_set_landmark_estimates.argtypes = [vp, C.c_int, c_dbl_p, c_int_p]
     L.g2ohip_pg_get_landmark_estimates.argtypes = [vp, c_dbl_p]
@@ -557,6 +559,7 @@ class HipBlockSolver:
         self.bearing_set = None
         self.calib_sets = None
         self.odom_calib_sets = None
+        self.pointxy_calib_sets = None
         self._pg_owner_sets = set()
         self.nP = self.nL = 0
 
@@ -581,11 +584,14 @@ class HipBlockSolver:
                 self.bearing_set = None
                 self.calib_sets = None
                 self.odom_calib_sets = None
+                self.pointxy_calib_sets = None
                 self._pg_owner_sets = set()
             if self.calib_sets is not None and set_id in self.calib_sets:   # (a calibration group goes as one)
                 self.calib_sets = None
             if self.odom_calib_sets is not None and set_id in self.odom_calib_sets:
                 self.odom_calib_sets = None
+            if self.pointxy_calib_sets is not None and set_id in self.pointxy_calib_sets:
+                self.pointxy_calib_sets = None
         return True
 
     def setProfiling(self, on):
@@ -1005,6 +1011,27 @@ class HipBlockSolver:
         _check(self.L.g2ohip_pg_set_odom_calib_edges(self.h, set_ij, set_ip, set_jp, _ip(vi), _ip(vj), _ip(vp), _dp(meas),
                                                      None if info is None else _dp(info)), "pgSetOdomCalibEdges")
         self.odom_calib_sets = (set_ij, set_ip, set_jp)
+
+    pointxy_calib_sets = None   # set ids (p-l, p-c, l-c) of the bound EdgeSE2PointXYCalib group (pgSetPointXYCalibEdges)
+
+    def pgSetPointXYCalibEdges(self, set_pl, set_pc, set_lc, pose_vertex, point_vertex, calib_vertex, meas, info=None):
+        """Landmark self-calibration (EdgeSE2PointXYCalib, type 24) beside an EdgeSE2 pose set: a three-vertex edge over the pose
+        pose_vertex and the sensor offset calib_vertex, both rows of the table of pgSetEstimates, and the landmark point_vertex, a
+        row of the table of pgSetLandmarkEstimates; meas [n][2], info [n][2x2] or None (identity).  The three sets are binary ones
+        with error_dim 2 over (pose, landmark), (pose, calib), (landmark, calib) with setEdgeSetParts 0, PART_NO_VERTEX0 |
+        PART_NO_VERTEX1 | PART_NO_CHI2 and PART_NO_VERTEX0 | PART_NO_CHI2 before buildStructure.  After pgSetEdges.  A robust
+        kernel goes on all three sets."""
+        vpp, vll, vcc, meas = _i32(pose_vertex), _i32(point_vertex), _i32(calib_vertex), _f64(meas)
+        n = self._set_sizes[set_pl]
+        if len(vpp) != n or len(vll) != n or len(vcc) != n or meas.size != n * 2:
+            raise ValueError("pgSetPointXYCalibEdges: arrays must hold one entry per edge of set %d (%d edges)" % (set_pl, n))
+        if info is not None:
+            info = _f64(info)
+            if info.size != n * 4:
+                raise ValueError("pgSetPointXYCalibEdges: info is [n][2x2]")
+        _check(self.L.g2ohip_pg_set_pointxy_calib_edges(self.h, set_pl, set_pc, set_lc, _ip(vpp), _ip(vll), _ip(vcc), _dp(meas),
+                                                        None if info is None else _dp(info)), "pgSetPointXYCalibEdges")
+        self.pointxy_calib_sets = (set_pl, set_pc, set_lc)
 
     cam_set = scale_set = None     # set ids of the bound EdgeSBACam / EdgeSBAScale sets (pgSetCamEdges)
 

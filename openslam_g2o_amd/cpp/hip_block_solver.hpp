@@ -175,6 +175,13 @@ class HipBlockSolver {
                              const double* info) {
     return ok(g2ohip_pg_set_sensor_calib_edges(h_, setIJ, setIL, setJL, vi, vj, vl, meas, info), "pgSetSensorCalibEdges");
   }
+  // Landmark self-calibration (g2ohip_pg_set_pointxy_calib_edges): three-vertex EdgeSE2PointXYCalib edges beside an EdgeSE2 set, as
+  // the binary sets (pose, landmark), (pose, calib), (landmark, calib) of setEdgeSetParts; poseVertex / calibVertex index the pose
+  // table, pointVertex the landmark table; meas [n][2], info [n][2x2] or null (identity)
+  bool pgSetPointXYCalibEdges(int setPL, int setPC, int setLC, const int32_t* poseVertex, const int32_t* pointVertex,
+                              const int32_t* calibVertex, const double* meas, const double* info) {
+    return ok(g2ohip_pg_set_pointxy_calib_edges(h_, setPL, setPC, setLC, poseVertex, pointVertex, calibVertex, meas, info), "pgSetPointXYCalibEdges");
+  }
   // Odometry self-calibration (g2ohip_pg_set_odom_calib_edges): three-vertex EdgeSE2OdomDifferentialCalib edges beside an EdgeSE2
   // set, as the three binary sets (i, j), (i, p), (j, p) with their parts; vi / vj / vp index the pose table (vp = the
   // VertexOdomDifferentialParams row, additive while bound), meas [n][3] = (vl, vr, dt), info [n][3x3] or null (identity)

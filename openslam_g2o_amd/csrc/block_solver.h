@@ -116,6 +116,8 @@ class BlockSolver {
                                  const double* info);
   void pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, const int* vi, const int* vj, const int* vp, const double* meas,
                                const double* info);
+  void pg_set_pointxy_calib_edges(int set_pl, int set_pc, int set_lc, const int* pose_vertex, const int* point_vertex,
+                                  const int* calib_vertex, const double* meas, const double* info);
   void pg_set_cam_edges(int set, int type, const int* vi, const int* vj, const double* meas, const double* info);
   void pg_set_landmark_estimates(int n_points, const double* points, const int* hidx);
   void pg_get_landmark_estimates(double* points);
@@ -370,7 +372,7 @@ class BlockSolver {
   // (set_edge_data on one of the sets repoints it to that set's own copy) drops the captured launch sequences.  release_triple:
   // the sets keep no device-written data and no pointer into each other's buffers (set_edge_data is their next source;
   // build_system refuses them until then, unless they are empty).  Used by the inverse-depth group of the BA front end and by the
-  // two calibration groups of the pose-graph front end; what else a group owns is released by its caller.
+  // three calibration groups of the pose-graph front end; what else a group owns is released by its caller.
   void alias_triple(const int ids[3]);
   void release_triple(const int ids[3]);
   void ba_psi_release();   // (release_triple of it, and its anchors)
@@ -387,8 +389,9 @@ class BlockSolver {
   bool ll_valid_ = true;   // Hll, b_l and the errors of the fused BA path match the last build_system
   bool ll_hbm_partial_ = false;   // ... but the Schur tiles that assembled them wrote b_l only (Hll and the errors stayed on chip)
   void pg_validate(const EdgeSet& es, const int* vi, const int* vj, size_t n, const int* hidx, int nv) const;
+  // (landmark_first: the set's vertex 0 is the landmark and its vertex 1 the pose -- the (landmark, calibration) set of type 24)
   void pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv, const int* pt_hidx,
-                             int np) const;
+                             int np, bool landmark_first = false) const;
   void pg_validate_priors(const EdgeSet& es, const int* vq, size_t n, const int* hidx, int nv) const;
   // a row of the SE2 pose table is read either as a VertexSE2 or as an additive row (VertexOdomDifferentialParams), never both:
   // throws ArgFailure where one of `lists` (index arrays read as VertexSE2) names a row of `additive` (sorted)
@@ -406,17 +409,29 @@ class BlockSolver {
   // What every bind entry ends with, after its LAST check: the set that leaves the slot gives up the data the device wrote for it (a
   // group: pg_release_group), the slot takes the ids, the type, the index arrays (host copy and device) and the measurements
   // [n][meas_stride]; the first set gets the information [n][d x d] and buffers for J0 [n][d x d0], J1 [n][d x d1] (d1 = 0: a
-  // unary set), errors [n][d] -- a group: the third set its J1, then alias_triple; the pointers of the sets are their own
-  // (external = false), no data and no errors until the first pg_linearize, the cached evaluation and chi2 are dropped; the stream
-  // is synchronised (every array handed in has been read).
+  // unary set), errors [n][d] -- a group: the third set its J1 [n][d x d2] (the third vertex; d2 < 0: as wide as d1), then
+  // alias_triple; the pointers of the sets are their own (external = false), no data and no errors until the first pg_linearize,
+  // the cached evaluation and chi2 are dropped; the stream is synchronised (every array handed in has been read).
   void pg_commit(PgSlotId slot, std::initializer_list<int> sets, int type, std::initializer_list<const int*> idx, size_t n,
-                 const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info);
+                 const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info, int d2 = -1);
   // a bound slot against candidate estimate tables (the descriptor says which validator: pose pairs, pose-landmark pairs, priors,
   // or the three pairs of a group)
   void pg_validate_slot(PgSlotId slot, const int* hidx, int nv, const int* pt_hidx, int np) const;
-  // what the entries of the two calibration groups check alike, up to the index validation against the pose table
-  void pg_check_group(const std::string& who, const int ids[3], const int* vi, const int* vj, const int* vx, const double* meas,
-                      const double* info) const;
+  // one binary set of a group, over the vertices (a, b) of its edges, against candidate tables: the descriptor's points[] flags say
+  // which of the two index arrays names landmarks (pg_validate / pg_validate_landmarks, in either vertex order)
+  void pg_validate_pair(const EdgeSet& es, const int* va, bool a_point, const int* vb, bool b_point, size_t n, const int* hidx, int nv,
+                        const int* pt_hidx, int np) const;
+  // What the entries of the three-vertex groups check alike, up to and including the index validation against the committed
+  // tables.  The group's shape: error dimension d (measurements [n][meas], information [n][d x d]) and, per vertex (a, b, x), its
+  // dimension; which vertices are landmarks is the slot's kPgSlotDesc[].points.  The sets are (a, b), (a, x), (b, x) with the
+  // dimensions and parts that follow from that; two vertices of one edge that are rows of the same table must differ.
+  struct PgGroupShape {
+    int d, meas;
+    int dim[3];
+    const char* words;   // the dimensions in the message
+  };
+  void pg_check_group(const std::string& who, PgSlotId slot, const PgGroupShape& shape, const int ids[3], const int* vi, const int* vj,
+                      const int* vx, const double* meas, const double* info) const;
   void pg_release_group(PgSlotId slot);   // a group leaves its slot: release_triple, the host index copies, the cached evaluation
   void pg_od_release();                   // ... the odometry group: its additive rows are VertexSE2 rows again, the captured launches go
   void pg_od_build_mask();
@@ -564,10 +579,17 @@ class BlockSolver {
     // are ADDITIVE rows: od_rows lists them (sorted, unique), od_mask [poses.n] marks them on the device for
     // pg_se2_update_additive_kernel.
     kOdom,
+    // ONE group of EdgeSE2PointXYCalib (type 24, error 2, THREE vertices: pose, landmark, sensor offset) beside type 1, with or
+    // without a type-3 or a bearing set over the same landmark table, independent of every other slot: the first group that spans
+    // BOTH tables.  v[0] (pose) and v[2] (the calibration vertex, an ordinary VertexSE2) index `poses`, v[1] indexes `points`; the
+    // binary sets (pose, landmark), (pose, calib), (landmark, calib) of dimensions (3, 2), (3, 3), (2, 3) share buffers as the
+    // type-21 group's do: the first owns J_pose [n][2 x 3], J_point [n][2 x 2], information and errors, the third J_calib
+    // [n][2 x 3].  meas [n][2] (pg_pointxy_calib.inc).
+    kPointCalib,
     kPgSlots
   };
   struct PgSlot {
-    int set[3] = {-1, -1, -1};   // single-set slots use set[0]; groups use (ij, il | ip, jl | jp)
+    int set[3] = {-1, -1, -1};   // single-set slots use set[0]; groups use (ij, il | ip, jl | jp), type 24 (pl, pc, lc)
     int type = 0;                // the edge type bound (PgSlotId above)
     std::vector<int> h_v[3];     // host copies of the index arrays: validation against the estimate tables
     DevBuf<int> v[3];
@@ -596,6 +618,7 @@ class BlockSolver {
       {"the bearing set", "pg_set_bearing_edges", 1, 2, {false, true, false}, true},
       {"the EdgeSE2SensorCalib group", "pg_set_sensor_calib_edges", 3, 3, {false, false, false}, true},
       {"the EdgeSE2OdomDifferentialCalib group", "pg_set_odom_calib_edges", 3, 3, {false, false, false}, true},
+      {"the EdgeSE2PointXYCalib group", "pg_set_pointxy_calib_edges", 3, 3, {false, true, false}, true},
   };
   struct PgFrontEnd {
     PgSlot slot[kPgSlots];

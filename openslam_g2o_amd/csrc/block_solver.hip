@@ -2330,6 +2330,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "pg_bearing.inc"
 #include "pg_calib.inc"
 #include "pg_odom_calib.inc"
+#include "pg_pointxy_calib.inc"
 #include "pg_scam.inc"
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
@@ -2597,8 +2598,10 @@ bool BlockSolver::update_structure(int new_poses, int set, int n, const int* v0,
     const int slot = pg_slot_of(set);
     if (slot == kCalib) pg_release_group(kCalib);
     if (slot == kOdom) pg_od_release();
+    if (slot == kPointCalib) pg_release_group(kPointCalib);
     if (slot == kPose || slot == kLandmark) {
       pg_release_group(kCalib);
+      pg_release_group(kPointCalib);
       pg_od_release();
       const bool fix_scale = pg_.fix_scale;   // (a property of the vertices, not of the edge arrays that are dropped)
       pg_ = PgFrontEnd();
@@ -5695,8 +5698,9 @@ void BlockSolver::pg_validate_priors(const EdgeSet& es, const int* vq, size_t n,
 // the landmark half: hidx[vp[k]] == v0[k] and pt_hidx[vl[k]] == v1[k] of the observation set (whatever of the tables has been
 // handed over so far: nv == 0 / np == 0 = not yet)
 void BlockSolver::pg_validate_landmarks(const EdgeSet& es, const int* vp, const int* vl, size_t n, const int* hidx, int nv,
-                                        const int* pt_hidx, int np) const {
+                                        const int* pt_hidx, int np, bool landmark_first) const {
   if (n == 0) return;
+  const std::vector<int>&pose_side = landmark_first ? es.v1 : es.v0, &point_side = landmark_first ? es.v0 : es.v1;
   for (int v = 0; v < np; ++v) {
     const int h = pt_hidx[v];
     if (h != -1 && (h < nP_ || h >= nP_ + nL_)) throw ArgFailure("pg: hessian index of landmark " + std::to_string(v) + " outside the landmark range of the structure");
@@ -5708,13 +5712,13 @@ void BlockSolver::pg_validate_landmarks(const EdgeSet& es, const int* vp, const 
       if (a >= nv) throw ArgFailure("pg: pose index of landmark edge " + std::to_string(k) + " outside the estimate table");
       const int ha = hidx[a];
       if (ha >= nP_) throw ArgFailure("pg: hessian index of an estimate outside the structure");
-      if (es.v0[k] != (ha < 0 ? -1 : ha))
+      if (pose_side[k] != (ha < 0 ? -1 : ha))
         throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the pose's hessian index differs from the edge set's");
     }
     if (np > 0) {
       if (b >= np) throw ArgFailure("pg: landmark index of landmark edge " + std::to_string(k) + " outside the landmark table");
       const int hb = pt_hidx[b];
-      if (es.v1[k] != (hb < 0 ? -1 : hb))
+      if (point_side[k] != (hb < 0 ? -1 : hb))
         throw ArgFailure("pg: landmark edge " + std::to_string(k) + ": the landmark's hessian index differs from the edge set's");
     }
   }
@@ -6000,7 +6004,7 @@ constexpr BlockSolver::PgSlotDesc BlockSolver::kPgSlotDesc[BlockSolver::kPgSlots
 // the pose-set type an edge type stands beside, and that pose type in words
 static int pg_pose_type_beside(int edge_type) {
   switch (edge_type) {
-    case 3: case 7: case 8: case 18: case 20: case 21: case 22: return 1;
+    case 3: case 7: case 8: case 18: case 20: case 21: case 22: case 24: return 1;
     case 4: case 5: case 6: case 9: case 15: case 19: case 23: return 2;
     case 11: return 10;
     default: return 12;   // 13, 14, 16, 17
@@ -6011,8 +6015,9 @@ static const char* pg_edge_type_words(int edge_type) {
                                       "EdgeSE2Prior (7)", "EdgeSE2XYPrior (8)", "EdgeSE3Prior (9)", "EdgeSim3 (10)", "EdgeSim3ProjectXYZ (11)",
                                       "VertexCam (12)", "EdgeProjectP2MC (13)", "EdgeProjectP2SC (14)", "Edge_V_V_GICP (15)", "EdgeSBACam (16)",
                                       "EdgeSBAScale (17)", "EdgeSE2Offset (18)", "EdgeSE3Offset (19)", "EdgeSE2PointXYBearing (20)",
-                                      "EdgeSE2SensorCalib (21)", "EdgeSE2OdomDifferentialCalib (22)", "Edge_XYZ_VSC (23)"};
-  return edge_type >= 3 && edge_type <= 23 ? words[edge_type - 3] : "?";
+                                      "EdgeSE2SensorCalib (21)", "EdgeSE2OdomDifferentialCalib (22)", "Edge_XYZ_VSC (23)",
+                                      "EdgeSE2PointXYCalib (24)"};
+  return edge_type >= 3 && edge_type <= 24 ? words[edge_type - 3] : "?";
 }
 static const char* pg_pose_type_words(int type) {
   return type == 1 ? "an EdgeSE2 pose set (1)" : type == 2 ? "an EdgeSE3 pose set (2)" : type == 10 ? "an EdgeSim3 pose set (10)" : "a VertexCam set (12)";
@@ -6040,7 +6045,7 @@ void BlockSolver::pg_begin_bind(const char* who, PgSlotId slot, std::initializer
 }
 
 void BlockSolver::pg_commit(PgSlotId slot, std::initializer_list<int> sets, int type, std::initializer_list<const int*> idx, size_t n,
-                            const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info) {
+                            const double* meas, size_t meas_stride, int d, int d0, int d1, const double* info, int d2) {
   const PgSlotDesc& ds = kPgSlotDesc[slot];
   PgSlot& sl = pg_.slot[slot];
   if (ds.sets == 3) {
@@ -6066,7 +6071,7 @@ void BlockSolver::pg_commit(PgSlotId slot, std::initializer_list<int> sets, int 
   if (d1 > 0) es.own_J1.alloc(n * sd * d1);
   es.own_err.alloc(n * sd);
   if (ds.sets == 3) {
-    sets_[sl.set[2]]->own_J1.alloc(n * sd * d1);
+    sets_[sl.set[2]]->own_J1.alloc(n * sd * (d2 < 0 ? d1 : d2));
     alias_triple(sl.set);
   } else {
     es.J0 = es.own_J0.p; es.J1 = d1 > 0 ? es.own_J1.p : nullptr; es.omega = es.own_omega.p; es.err = es.own_err.p;
@@ -6085,9 +6090,9 @@ void BlockSolver::pg_validate_slot(PgSlotId slot, const int* hidx, int nv, const
   const PgSlot& sl = pg_.slot[slot];
   const int *a = sl.h_v[0].data(), *b = sl.h_v[1].data(), *c = sl.h_v[2].data();
   if (ds.sets == 3) {   // (i, j), (i, x), (j, x)
-    pg_validate(*sets_[sl.set[0]], a, b, sl.n(), hidx, nv);
-    pg_validate(*sets_[sl.set[1]], a, c, sl.n(), hidx, nv);
-    pg_validate(*sets_[sl.set[2]], b, c, sl.n(), hidx, nv);
+    pg_validate_pair(*sets_[sl.set[0]], a, ds.points[0], b, ds.points[1], sl.n(), hidx, nv, pt_hidx, np);
+    pg_validate_pair(*sets_[sl.set[1]], a, ds.points[0], c, ds.points[2], sl.n(), hidx, nv, pt_hidx, np);
+    pg_validate_pair(*sets_[sl.set[2]], b, ds.points[1], c, ds.points[2], sl.n(), hidx, nv, pt_hidx, np);
   } else if (ds.arrays == 1) {
     pg_validate_priors(*sets_[sl.set[0]], a, sl.n(), hidx, nv);
   } else if (ds.points[1]) {
@@ -6095,6 +6100,13 @@ void BlockSolver::pg_validate_slot(PgSlotId slot, const int* hidx, int nv, const
   } else {
     pg_validate(*sets_[sl.set[0]], a, b, sl.n(), hidx, nv);
   }
+}
+
+void BlockSolver::pg_validate_pair(const EdgeSet& es, const int* va, bool a_point, const int* vb, bool b_point, size_t n, const int* hidx,
+                                   int nv, const int* pt_hidx, int np) const {
+  if (a_point) pg_validate_landmarks(es, vb, va, n, hidx, nv, pt_hidx, np, true);
+  else if (b_point) pg_validate_landmarks(es, va, vb, n, hidx, nv, pt_hidx, np);
+  else pg_validate(es, va, vb, n, hidx, nv);
 }
 
 void BlockSolver::pg_release_group(PgSlotId slot) {
@@ -6449,38 +6461,49 @@ void BlockSolver::pg_set_bearing_edges(int set, const int* pose_vertex, const in
 // J_j / information / errors into set_ij's buffers and J_x into set_jx's own_J1, and every other pointer of the three aliases one
 // of those (27 + 3 doubles per edge leave the producer, not 54 + 9).  Robust kernels: the caller sets the same kernel on all three
 // sets (the generic assembly weighs each set by its own).  The checks the two entries share, up to the index validation:
-void BlockSolver::pg_check_group(const std::string& w, const int ids[3], const int* vi, const int* vj, const int* vx, const double* meas,
-                                 const double* info) const {
+void BlockSolver::pg_check_group(const std::string& w, PgSlotId slot, const PgGroupShape& sh, const int ids[3], const int* vi,
+                                 const int* vj, const int* vx, const double* meas, const double* info) const {
   if (ids[0] == ids[1] || ids[0] == ids[2] || ids[1] == ids[2]) throw ArgFailure(w + ": the three sets must differ");
-  const EdgeSet &es = *sets_[ids[0]], &ea = *sets_[ids[1]], &ec = *sets_[ids[2]];
-  for (const EdgeSet* e : {&es, &ea, &ec})
-    if (p_ != 3 || e->unary || e->d != 3 || e->dim0 != 3 || e->dim1 != 3)
-      throw ArgFailure(w + ": the sets must be binary pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)");
+  const bool* pt = kPgSlotDesc[slot].points;
+  const EdgeSet* g[3] = {sets_[ids[0]].get(), sets_[ids[1]].get(), sets_[ids[2]].get()};
+  const int side[3][2] = {{0, 1}, {0, 2}, {1, 2}};   // the vertices of (a, b), (a, x), (b, x)
+  bool handle_fits = true;   // the handle's (pose, landmark) dimensions against those of the group's vertices
+  for (int a = 0; a < 3; ++a) handle_fits = handle_fits && (pt[a] ? l_ : p_) == sh.dim[a];
+  for (int q = 0; q < 3; ++q)
+    if (!handle_fits || g[q]->unary || g[q]->d != sh.d || g[q]->dim0 != sh.dim[side[q][0]] ||
+        g[q]->dim1 != sh.dim[side[q][1]])
+      throw ArgFailure(w + ": the sets must be binary " + sh.words);
+  const EdgeSet &es = *g[0], &ea = *g[1], &ec = *g[2];
   if (es.parts != 0 || ea.parts != 7 || ec.parts != 5)
     throw ArgFailure(w + ": parts must be 0, NO_VERTEX0 | NO_VERTEX1 | NO_CHI2 and NO_VERTEX0 | NO_CHI2 (set_edge_set_parts)");
   if (ea.n != es.n || ec.n != es.n) throw ArgFailure(w + ": the three sets must hold the same number of edges");
   if (!vi || !vj || !vx || !meas) throw ArgFailure(w + ": null array");
   if (es.rk.p || ea.rk.p || ec.rk.p)   // (the rule of ba_set_edges: a binding starts from the set-level kernel)
     throw StateFailure(w + ": a set carries per-edge robust kernels (set_robust_kernel_per_edge) -- clear them first and set them again on the bound sets");
-  const size_t n = (size_t)es.n;
+  const size_t n = (size_t)es.n, ms = (size_t)sh.meas, dd = (size_t)(sh.d * sh.d);
+  const int* v[3] = {vi, vj, vx};
   for (size_t k = 0; k < n; ++k) {
     if (vi[k] < 0 || vj[k] < 0 || vx[k] < 0) throw ArgFailure(w + ": negative vertex index in edge " + std::to_string(k));
-    if (vi[k] == vj[k] || vi[k] == vx[k] || vj[k] == vx[k]) throw ArgFailure(w + ": edge " + std::to_string(k) + " names one vertex twice");
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(meas[3 * k + i])) throw ArgFailure(w + ": non-finite measurement in edge " + std::to_string(k));
+    for (int q = 0; q < 3; ++q)   // (rows of different tables are different vertices whatever their numbers)
+      if (pt[side[q][0]] == pt[side[q][1]] && v[side[q][0]][k] == v[side[q][1]][k])
+        throw ArgFailure(w + ": edge " + std::to_string(k) + " names one vertex twice");
+    for (size_t i = 0; i < ms; ++i)
+      if (!std::isfinite(meas[ms * k + i])) throw ArgFailure(w + ": non-finite measurement in edge " + std::to_string(k));
     if (info)
-      for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(info[9 * k + i])) throw ArgFailure(w + ": non-finite information in edge " + std::to_string(k));
+      for (size_t i = 0; i < dd; ++i)
+        if (!std::isfinite(info[dd * k + i])) throw ArgFailure(w + ": non-finite information in edge " + std::to_string(k));
   }
-  pg_validate(es, vi, vj, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ea, vi, vx, n, pg_.poses.h_hidx.data(), pg_.poses.n);
-  pg_validate(ec, vj, vx, n, pg_.poses.h_hidx.data(), pg_.poses.n);
+  for (int q = 0; q < 3; ++q)
+    pg_validate_pair(*g[q], v[side[q][0]], pt[side[q][0]], v[side[q][1]], pt[side[q][1]], n, pg_.poses.h_hidx.data(), pg_.poses.n,
+                     pg_.points.h_hidx.data(), pg_.points.n);
 }
 
-// information().setIdentity() of n three-dimensional edges
-static std::vector<double> pg_identity3(size_t n) {
-  std::vector<double> w(n * 9, 0.0);
-  for (size_t k = 0; k < n; ++k) w[9 * k] = w[9 * k + 4] = w[9 * k + 8] = 1.0;
+// information().setIdentity() of n d-dimensional edges
+static std::vector<double> pg_identity(size_t n, int d) {
+  const size_t dd = (size_t)d * d;
+  std::vector<double> w(n * dd, 0.0);
+  for (size_t k = 0; k < n; ++k)
+    for (int i = 0; i < d; ++i) w[dd * k + (size_t)i * (d + 1)] = 1.0;
   return w;
 }
 
@@ -6489,11 +6512,12 @@ void BlockSolver::pg_set_sensor_calib_edges(int set_ij, int set_il, int set_jl, 
   pg_begin_bind("pg_set_sensor_calib_edges", kCalib, {set_ij, set_il, set_jl});
   if (pg_.pose_type() != 1) throw ArgFailure("pg_set_sensor_calib_edges: EdgeSE2SensorCalib (21) goes with an EdgeSE2 pose set (1)");
   const int ids[3] = {set_ij, set_il, set_jl};
-  pg_check_group("pg_set_sensor_calib_edges", ids, vi, vj, vl, meas, info);
+  static constexpr PgGroupShape shape = {3, 3, {3, 3, 3}, "pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)"};
+  pg_check_group("pg_set_sensor_calib_edges", kCalib, shape, ids, vi, vj, vl, meas, info);
   const size_t n = (size_t)sets_[set_ij]->n;
   pg_refuse_additive("pg_set_sensor_calib_edges", pg_.od_rows, {{vi, n}, {vj, n}, {vl, n}});
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const std::vector<double> identity = info ? std::vector<double>() : pg_identity3(n);
+  const std::vector<double> identity = info ? std::vector<double>() : pg_identity(n, 3);
   pg_commit(kCalib, {set_ij, set_il, set_jl}, 21, {vi, vj, vl}, n, meas, 3, 3, 3, 3, info ? info : identity.data());
 }
 
@@ -6505,7 +6529,8 @@ void BlockSolver::pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, co
   pg_begin_bind("pg_set_odom_calib_edges", kOdom, {set_ij, set_ip, set_jp});
   if (pg_.pose_type() != 1) throw ArgFailure("pg_set_odom_calib_edges: EdgeSE2OdomDifferentialCalib (22) goes with an EdgeSE2 pose set (1)");
   const int ids[3] = {set_ij, set_ip, set_jp};
-  pg_check_group("pg_set_odom_calib_edges", ids, vi, vj, vp, meas, info);
+  static constexpr PgGroupShape shape = {3, 3, {3, 3, 3}, "pose-pose sets with (error, pose, pose) dimensions (3, 3, 3)"};
+  pg_check_group("pg_set_odom_calib_edges", kOdom, shape, ids, vi, vj, vp, meas, info);
   const size_t n = (size_t)sets_[set_ij]->n;
   // the rows of vp become additive rows: none of them may be a pose of this group or a vertex of anything bound on the handle
   std::vector<int> rows(vp, vp + n);
@@ -6520,11 +6545,36 @@ void BlockSolver::pg_set_odom_calib_edges(int set_ij, int set_ip, int set_jp, co
   }
   pg_refuse_additive("pg_set_odom_calib_edges", rows, read_as_pose);
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
-  const std::vector<double> identity = info ? std::vector<double>() : pg_identity3(n);
+  const std::vector<double> identity = info ? std::vector<double>() : pg_identity(n, 3);
   pg_od_release();   // the previous group leaves the slot, with its additive rows
   pg_.od_rows = std::move(rows);
   pg_od_build_mask();
   pg_commit(kOdom, {set_ij, set_ip, set_jp}, 22, {vi, vj, vp}, n, meas, 3, 3, 3, 3, info ? info : identity.data());
+}
+
+// ---- ... landmark self-calibration: EdgeSE2PointXYCalib (type 24, pg_pointxy_calib.inc), THREE-vertex edges over a pose, a
+// landmark and the sensor's mounting offset (a VertexSE2, a row of the POSE table), beside an EdgeSE2 set, in a slot of its own,
+// with or without a type-3 or a bearing set over the same landmark table.  The edge is the three binary sets of
+// g2ohip_set_edge_set_parts, all of the same edge count and error dimension 2:
+//   set_pl  (pose, landmark)   parts 0                                  dims (3, 2)   terms of pose and landmark, H(p, l), chi2
+//   set_pc  (pose, calib)      parts NO_VERTEX0 | NO_VERTEX1 | NO_CHI2  dims (3, 3)   H(p, c)
+//   set_lc  (landmark, calib)  parts NO_VERTEX0 | NO_CHI2               dims (2, 3)   terms of calib, H(l, c)
+// (the generic assembly takes the landmark on either side of a set, as the PSI2UV group's (point, pose) set shows).  The group
+// shares buffers as the type-21 group does: J_pose / J_point / information / errors in set_pl's buffers, J_calib in set_lc's own_J1.
+void BlockSolver::pg_set_pointxy_calib_edges(int set_pl, int set_pc, int set_lc, const int* pose_vertex, const int* point_vertex,
+                                             const int* calib_vertex, const double* meas, const double* info) {
+  pg_begin_bind("pg_set_pointxy_calib_edges", kPointCalib, {set_pl, set_pc, set_lc});
+  if (pg_.pose_type() != 1) throw ArgFailure("pg_set_pointxy_calib_edges: EdgeSE2PointXYCalib (24) goes with an EdgeSE2 pose set (1)");
+  const int ids[3] = {set_pl, set_pc, set_lc};
+  static constexpr PgGroupShape shape = {2, 2, {3, 2, 3},
+                                         "sets with error dimension 2 and vertex dimensions (3, 2), (3, 3), (2, 3): (pose, landmark), (pose, calib), (landmark, calib)"};
+  pg_check_group("pg_set_pointxy_calib_edges", kPointCalib, shape, ids, pose_vertex, point_vertex, calib_vertex, meas, info);
+  const size_t n = (size_t)sets_[set_pl]->n;
+  pg_refuse_additive("pg_set_pointxy_calib_edges", pg_.od_rows, {{pose_vertex, n}, {calib_vertex, n}});
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const std::vector<double> identity = info ? std::vector<double>() : pg_identity(n, 2);
+  pg_commit(kPointCalib, {set_pl, set_pc, set_lc}, 24, {pose_vertex, point_vertex, calib_vertex}, n, meas, 2, 2, 3, 2,
+            info ? info : identity.data(), 3);
 }
 
 // the ONE check of row kinds: an index of `lists` (arrays a binding reads as VertexSE2) that names a row of `additive` (sorted)
@@ -6613,7 +6663,8 @@ void BlockSolver::pg_get_landmark_estimates(double* points) {
 
 void BlockSolver::pg_linearize(bool jacobians) {
   const PgSlot &s_pose = pg_.slot[kPose], &s_lm = pg_.slot[kLandmark], &s_prior = pg_.slot[kPrior], &s_gicp = pg_.slot[kGicp], &s_cam = pg_.slot[kCam],
-               &s_scale = pg_.slot[kScale], &s_off = pg_.slot[kOffset], &s_bear = pg_.slot[kBearing], &s_calib = pg_.slot[kCalib], &s_odom = pg_.slot[kOdom];
+               &s_scale = pg_.slot[kScale], &s_off = pg_.slot[kOffset], &s_bear = pg_.slot[kBearing], &s_calib = pg_.slot[kCalib], &s_odom = pg_.slot[kOdom],
+               &s_pcal = pg_.slot[kPointCalib];
   if (!s_pose.bound() || pg_.poses.n <= 0) throw StateFailure("pg_linearize: call pg_set_edges and pg_set_estimates first");
   G2OHIP_HIP_CHECK(hipSetDevice(device_));
   // the sets of every bound slot, as they were bound
@@ -6644,7 +6695,7 @@ void BlockSolver::pg_linearize(bool jacobians) {
   EdgeSet& es = *e[kPose][0];
   EdgeSet *const el = e[kLandmark][0], *const ep = e[kPrior][0], *const eg = e[kGicp][0], *const ec = e[kCam][0];
   EdgeSet *const esc = e[kScale][0], *const eo = e[kOffset][0], *const eb = e[kBearing][0];
-  EdgeSet *const *const ecal = e[kCalib], *const *const eod = e[kOdom];   // (the three sets of each group)
+  EdgeSet *const *const ecal = e[kCalib], *const *const eod = e[kOdom], *const *const epc = e[kPointCalib];   // (the three sets of each group)
   // (a type-2 set may hold zero edges -- a pure registration, all constraints in the GICP set -- and then launches nothing; so
   // may a type-1 set: the graph of calibration_odom_laser has no EdgeSE2, all constraints in the two calibration groups)
   if (s_pose.type == 1 && es.n > 0)
@@ -6787,6 +6838,15 @@ void BlockSolver::pg_linearize(bool jacobians) {
       hipLaunchKernelGGL(pg_se2_odom_calib_linearize_kernel<STAGED>, grid, block, 0, st_, eod[0]->n, pg_.poses.val.p, pg_.poses.hidx.p,
                          s_odom.v[0].p, s_odom.v[1].p, s_odom.v[2].p, s_odom.meas.p, eod[0]->own_J0.p, eod[0]->own_J1.p, eod[2]->own_J1.p,
                          eod[0]->own_err.p, jac);
+    });
+  }
+  if (launches(kPointCalib)) {   // EdgeSE2PointXYCalib -- pg_pointxy_calib.inc
+    const dim3 grid(grid_for(epc[0]->n)), block(kThreads);
+    with_bool(pg_landmark_staged, [&](auto staged) {
+      constexpr bool STAGED = staged;
+      hipLaunchKernelGGL(pg_se2_pointxy_calib_linearize_kernel<STAGED>, grid, block, 0, st_, epc[0]->n, pg_.poses.val.p, pg_.points.val.p,
+                         pg_.poses.hidx.p, pg_.points.hidx.p, s_pcal.v[0].p, s_pcal.v[1].p, s_pcal.v[2].p, s_pcal.meas.p, epc[0]->own_J0.p,
+                         epc[0]->own_J1.p, epc[2]->own_J1.p, epc[0]->own_err.p, jac);
     });
   }
   if (beside) prof.end(KernelProf::kPgLandmark, st_);

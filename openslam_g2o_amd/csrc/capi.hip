@@ -724,6 +724,10 @@ int g2ohip_pg_set_sensor_calib_edges(g2ohip_solver* s, int set_ij, int set_il, i
                                      const int32_t* vl, const double* meas, const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_sensor_calib_edges(set_ij, set_il, set_jl, vi, vj, vl, meas, info); });
 }
+int g2ohip_pg_set_pointxy_calib_edges(g2ohip_solver* s, int set_pl, int set_pc, int set_lc, const int32_t* pose_vertex,
+                                      const int32_t* point_vertex, const int32_t* calib_vertex, const double* meas, const double* info) {
+  return entry(s, [&](BlockSolver& b) { b.pg_set_pointxy_calib_edges(set_pl, set_pc, set_lc, pose_vertex, point_vertex, calib_vertex, meas, info); });
+}
 int g2ohip_pg_set_odom_calib_edges(g2ohip_solver* s, int set_ij, int set_ip, int set_jp, const int32_t* vi, const int32_t* vj,
                                    const int32_t* vp, const double* meas, const double* info) {
   return entry(s, [&](BlockSolver& b) { b.pg_set_odom_calib_edges(set_ij, set_ip, set_jp, vi, vj, vp, meas, info); });

@@ -87,7 +87,11 @@ def read_g2o(path):
     vertex_odom_differential_params.cpp) become rows of the same estimate table, listed in odom_param_rows (ADDITIVE rows: they
     are no SE2), and EDGE_SE2_ODOM_DIFFERENTIAL_CALIB lines (i j p vl vr dt + 6: EdgeSE2OdomDifferentialCalib::read,
     edge_se2_odom_differential_calib.cpp:39-61) give odo_vi / odo_vj / odo_vp (table indices), odo_meas [m][3] = (vl, vr, dt) and
-    odo_info [m][3][3] (odom_calib_problem turns them into a problem dict); a file without them gives none of these keys."""
+    odo_info [m][3][3] (odom_calib_problem turns them into a problem dict); a file without them gives none of these keys.
+    A file with EDGE_SE2_XY_CALIB lines (id_pose id_point id_calib z0 z1 i00 i01 i11: EdgeSE2PointXYCalib::read,
+    g2o/types/slam2d/edge_se2_pointxy_calib.cpp; the calibration vertex is a plain VERTEX_SE2) also gives pc_vp / pc_vc (pose-table
+    indices), pc_vl (point-table index), pc_meas [m][2] and pc_info [m][2][2] (pointxy_calib_problem turns them into a problem
+    dict); a file without them gives none of these keys."""
     from . import sim3 as S3
     c_i, c_j, c_l, c_meas, c_info = [], [], [], [], []
     d_i, d_j, d_p, d_meas, d_info, d_params = [], [], [], [], [], []
@@ -102,6 +106,7 @@ def read_g2o(path):
     qv, qkind, qmeas, qinfo, qparam = [], [], [], [], []
     o_i, o_j, o_from, o_to, o_meas, o_info, o_kind, offsets2 = [], [], [], [], [], [], None, {}
     b_p, b_l, b_meas, b_info = [], [], [], []
+    x_p, x_l, x_c, x_meas, x_info = [], [], [], [], []
     kind = None
     with open(path) as f:
         for line in f:
@@ -217,6 +222,12 @@ def read_g2o(path):
                 ll.append(int(t[2]))
                 lmeas.append([float(x) for x in t[3:5]])
                 linfo.append(_upper_to_full([float(x) for x in t[5:8]], 2))
+            elif tag == "EDGE_SE2_XY_CALIB":
+                x_p.append(int(t[1]))
+                x_l.append(int(t[2]))
+                x_c.append(int(t[3]))
+                x_meas.append([float(x) for x in t[4:6]])
+                x_info.append(_upper_to_full([float(x) for x in t[6:9]], 2))
             elif tag == "EDGE_BEARING_SE2_XY":
                 b_p.append(int(t[1]))
                 b_l.append(int(t[2]))
@@ -299,7 +310,7 @@ def read_g2o(path):
         if cs_i:
             out.update(cam_scale_vi=np.asarray([lut[a] for a in cs_i], np.int32), cam_scale_vj=np.asarray([lut[a] for a in cs_j], np.int32),
                        cam_scale_meas=np.asarray(cs_meas, np.float64), cam_scale_info=np.asarray(cs_info, np.float64))
-    if pid or lp or offsets or cameras or b_p:
+    if pid or lp or offsets or cameras or b_p or x_p:
         pid = np.asarray(pid, np.int64)
         po = np.argsort(pid, kind="stable")
         pid = pid[po]
@@ -313,6 +324,10 @@ def read_g2o(path):
         if b_p:
             out.update(br_vp=np.asarray([lut[a] for a in b_p], np.int32), br_vl=np.asarray([plut[a] for a in b_l], np.int32),
                        br_meas=np.asarray(b_meas, np.float64), br_info=np.asarray(b_info, np.float64))
+        if x_p:
+            out.update(pc_vp=np.asarray([lut[a] for a in x_p], np.int32), pc_vl=np.asarray([plut[a] for a in x_l], np.int32),
+                       pc_vc=np.asarray([lut[a] for a in x_c], np.int32), pc_meas=np.asarray(x_meas, np.float64).reshape(-1, 2),
+                       pc_info=np.asarray(x_info, np.float64).reshape(-1, 2, 2))
     if g_i:
         gv = np.asarray(g_vals, np.float64).reshape(-1, 12)
         out.update(gicp_vi=np.asarray([lut[a] for a in g_i], np.int32), gicp_vj=np.asarray([lut[a] for a in g_j], np.int32),
@@ -846,6 +861,38 @@ def write_g2o_bearing(path, prob):
     with open(path, "a") as f:
         for e in range(len(prob["bp"])):
             f.write("EDGE_BEARING_SE2_XY %d %d %.17g %.17g\n" % (prob["bp"][e], n + prob["bl"][e], prob["zb"][e], prob["omega_b"][e]))
+
+
+def pointxy_calib_problem(rd, fixed_poses=None, fixed_points=None):
+    """read_g2o() result of a 2-D file with EDGE_SE2_XY_CALIB lines -> the problem dict of
+    openslam_g2o_amd.synthetic.make_pointxy_calib_slam (what lm.setup_device_landmark_slam takes): landmark_problem's dict -- its
+    EDGE_SE2_XY observations may be none -- plus qp, ql, qc, zq [m][2], omega_q [m][4] and Q = m.  The calibration vertices are rows
+    of the pose table like any VERTEX_SE2."""
+    if "pc_vp" not in rd or rd.get("kind") != "se2":
+        raise ValueError("the file has no EDGE_SE2_XY_CALIB edges over VERTEX_SE2 / VERTEX_XY")
+    if len(rd["lm_vp"]) == 0:   # (no plain observations: the empty arrays in the shapes landmark_problem reads)
+        rd = dict(rd, lm_meas=np.zeros((0, 2)), lm_info=np.zeros((0, 2, 2)))
+    out = landmark_problem(rd, fixed_poses, fixed_points)
+    m = len(rd["pc_vp"])
+    out.update(qp=rd["pc_vp"], ql=rd["pc_vl"], qc=rd["pc_vc"], zq=rd["pc_meas"].copy(),
+               omega_q=np.asarray(rd["pc_info"]).transpose(0, 2, 1).reshape(m, 4).copy(), Q=m)
+    return out
+
+
+def write_g2o_pointxy_calib(path, prob):
+    """make_pointxy_calib_slam-style problem -> `.g2o` text: what write_g2o_landmarks writes for the rows of the pose table (the
+    calibration vertex among them, a VERTEX_SE2), the landmarks, the odometry and (if any) the EDGE_SE2_XY observations, followed by
+    one EDGE_SE2_XY_CALIB id_pose id_point id_calib z0 z1 i00 i01 i11 line per edge (landmark j has the id n + j)."""
+    if prob["kind"] != "se2":
+        raise ValueError("write_g2o_pointxy_calib: EdgeSE2PointXYCalib belongs to kind 'se2'")
+    write_g2o_landmarks(path, prob)
+    n, m = len(prob["poses"]), len(prob["qp"])
+    om = np.tile(np.eye(2).reshape(1, 4), (m, 1)) if prob.get("omega_q") is None else np.asarray(prob["omega_q"], np.float64).reshape(m, 2, 2)
+    om = om.reshape(m, 2, 2)
+    with open(path, "a") as f:
+        for e in range(m):
+            f.write("EDGE_SE2_XY_CALIB %d %d %d %.17g %.17g %.17g %.17g %.17g\n" % (prob["qp"][e], n + prob["ql"][e], prob["qc"][e], prob["zq"][e][0],
+                                                                                prob["zq"][e][1], om[e][0, 0], om[e][0, 1], om[e][1, 1]))
 
 
 # ---- bundle-adjustment tags (SURVEY.md 8f.2) --------------------------------------------------------------

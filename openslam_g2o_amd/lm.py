@@ -481,12 +481,22 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     gj, gmeas and ginfo (and gcov or None) -- the keys setup_device_gicp reads; the graph of g2o/examples/icp/gicp_sba_demo.cpp --
     the Edge_V_V_GICP correspondences are bound beside them on the same handle: solver.gicp_set = their set id (no kernel on
     them).  A prob that carries offset_edges = (19, vi, vj, pfrom, pto, meas, info, offsets) gets that EdgeSE3Offset set bound as
-    well: solver.offset_set = its set id."""
+    well: solver.offset_set = its set id.
+    A prob of kind "se2" that carries qp, ql, qc, zq and omega_q (synthetic.make_pointxy_calib_slam, g2o_io.pointxy_calib_problem;
+    omega_q may be None = identity) also gets its EdgeSE2PointXYCalib edges bound: three-vertex edges over the pose qp, the
+    landmark ql and the calibration vertex qc (a row of the pose table), added as the binary sets (pose, landmark), (pose, calib),
+    (landmark, calib) with their parts (pgSetPointXYCalibEdges); solver.pointxy_calib_sets = their ids, huber_delta goes on all
+    three; the EdgeSE2PointXY set is then added only if prob["vp"] is present and non-empty, as with bearings.  Such a prob must
+    not carry `prior` as well (the priors' measurements use the keys zq / omega_q too): ValueError."""
     import numpy as np
     from . import capi
     se2 = prob["kind"] == "se2"
     bearing = se2 and all(prob.get(k) is not None for k in ("bp", "bl", "zb", "omega_b"))
-    with_xy = not bearing or (prob.get("vp") is not None and len(prob["vp"]) > 0)
+    pcal = se2 and all(prob.get(k) is not None for k in ("qp", "ql", "qc"))
+    if pcal and prob.get("prior") is not None:
+        raise ValueError("setup_device_landmark_slam: a problem with pose priors and EdgeSE2PointXYCalib edges is not supported: "
+                         "both read the keys zq / omega_q")
+    with_xy = not (bearing or pcal) or (prob.get("vp") is not None and len(prob["vp"]) > 0)
     obs = prob.get("observation", "xyz")
     if obs in ("depth", "disparity") and prob.get("kcam") is None:
         raise ValueError("setup_device_landmark_slam: observation = %r needs kcam = (fx, fy, cx, cy)" % obs)
@@ -504,6 +514,13 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
     k1 = s.addEdgeSet(l, hidx[prob["vp"]], pt_hidx[prob["vl"]]) if with_xy else None
     if bearing:
         kb = s.addEdgeSet(1, hidx[np.asarray(prob["bp"], np.int64)], pt_hidx[np.asarray(prob["bl"], np.int64)])
+    if pcal:
+        qp, ql, qc = (np.asarray(prob[k], np.int64) for k in ("qp", "ql", "qc"))
+        parts = (0, capi.PART_NO_VERTEX0 | capi.PART_NO_VERTEX1 | capi.PART_NO_CHI2, capi.PART_NO_VERTEX0 | capi.PART_NO_CHI2)
+        kc3 = []
+        for (a, b), pt in zip(((hidx[qp], pt_hidx[ql]), (hidx[qp], hidx[qc]), (pt_hidx[ql], hidx[qc])), parts):
+            kc3.append(s.addEdgeSet(2, a, b))
+            s.setEdgeSetParts(kc3[-1], pt)
     prior = prob.get("prior")
     if prior is not None:
         ptype = 9 if not se2 else (8 if prior == "xy" else 7)
@@ -532,6 +549,8 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
         s.pgSetLandmarkEdges(k1, 3 if se2 else 4, prob["vp"], prob["vl"], prob["zl"], prob["omega_l"], prob.get("offset"))
     if bearing:
         s.pgSetBearingEdges(kb, prob["bp"], prob["bl"], prob["zb"], prob["omega_b"])
+    if pcal:
+        s.pgSetPointXYCalibEdges(*kc3, qp, ql, qc, prob["zq"], prob.get("omega_q"))
     s.pgSetLandmarkEstimates(prob["points"], pt_hidx)
     if prior is not None:
         s.pgSetPriorEdges(kq, ptype, prob["vq"], prob["zq"], prob["omega_q"], prob.get("prior_offset"))
@@ -540,6 +559,9 @@ def setup_device_landmark_slam(prob, huber_delta=0.0, schur=True, device=0, opti
         s.setRobustKernel(k1, capi.KERNEL_HUBER, huber_delta)
     if huber_delta > 0 and bearing:
         s.setRobustKernel(kb, capi.KERNEL_HUBER, huber_delta)
+    if huber_delta > 0 and pcal:
+        for k in kc3:
+            s.setRobustKernel(k, capi.KERNEL_HUBER, huber_delta)
     s.landmark_sets = (k0, k1)
     return s, DevicePoseGraph(s)
 

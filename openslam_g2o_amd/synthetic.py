@@ -1065,6 +1065,42 @@ def make_bearing_slam(n_poses, n_landmarks, with_xy=False, seed=42, noise=0.02, 
     return out
 
 
+def make_pointxy_calib_slam(n_poses, n_landmarks, offset=(0.3, 0.1, 0.2), fix_offset=False, with_xy=False, seed=42, noise=0.05,
+                            **landmark_args):
+    """2-D landmark SLAM whose point sensor is mounted off the robot's centre by an unknown offset that is estimated with the map
+    (EdgeSE2PointXYCalib), built on make_landmark_slam("se2", n_poses, n_landmarks, seed=seed, **landmark_args): the same
+    trajectory -- laps round a loop, so it keeps turning and the offset is observable --, odometry, landmarks and observing pairs.
+    The calibration vertex c is ONE extra row of the pose table, behind the poses (row n_poses; calib_row); its true value is
+    `offset`, its initial estimate the identity (fix_offset=True: it is fixed at the truth, hessian index -1).  Every Cartesian
+    observation (vp, vl) becomes a three-vertex edge (qp, ql, qc): zq = (x_true c_true)^-1 l_true + noise * N(0, 1), omega_q =
+    I / noise^2.  with_xy=True keeps the plain observations beside them (a second, centred point sensor); with_xy=False drops
+    them (vp, vl of length 0, zl [0][2], omega_l [0][4], M = 0).
+    Returns the dict of make_landmark_slam (n, nP, hidx, poses, poses_true one row longer, pt_hidx moved behind the new free
+    vertex) plus qp, ql, qc, zq [m][2], omega_q [m][4], Q = m, calib_row, offset_true."""
+    g = make_landmark_slam("se2", n_poses, n_landmarks, seed=seed, **landmark_args)
+    rng = CounterRng(seed)
+    n = g["n"]
+    off = np.asarray(offset, np.float64)
+    free = 0 if fix_offset else 1
+    out = dict(g)
+    out.update(n=n + 1, nP=g["nP"] + free, poses=np.vstack([g["poses"], off if fix_offset else np.zeros(3)]),
+               poses_true=np.vstack([g["poses_true"], off]), hidx=np.append(g["hidx"], -1 if fix_offset else g["nP"]).astype(np.int32),
+               pt_hidx=np.where(g["pt_hidx"] >= 0, g["pt_hidx"] + free, -1).astype(np.int32))
+    qp, ql = g["vp"].astype(np.int32), g["vl"].astype(np.int32)
+    m = len(qp)
+    X, Lm = g["poses_true"][qp], g["points_true"][ql]                     # (x_true c_true)^-1 l_true, all edges at once
+    c1, s1 = np.cos(X[:, 2]), np.sin(X[:, 2])
+    dx, dy = Lm[:, 0] - (X[:, 0] + c1 * off[0] - s1 * off[1]), Lm[:, 1] - (X[:, 1] + s1 * off[0] + c1 * off[1])
+    cq, sq = np.cos(X[:, 2] + off[2]), np.sin(X[:, 2] + off[2])
+    zq = np.stack([cq * dx + sq * dy, -sq * dx + cq * dy], axis=1)
+    zq = zq + noise * np.stack([rng.normal(280, m), rng.normal(281, m)], axis=1)
+    if not with_xy:
+        out.update(vp=np.zeros(0, np.int32), vl=np.zeros(0, np.int32), zl=np.zeros((0, 2)), omega_l=np.zeros((0, 4)), M=0)
+    out.update(qp=qp, ql=ql, qc=np.full(m, n, np.int32), zq=zq, omega_q=np.tile((np.eye(2) / noise ** 2).reshape(1, 4), (m, 1)), Q=m,
+               calib_row=n, offset_true=off)
+    return out
+
+
 def make_calib_rig(n_poses=40, loops=21, seed=0, noise=(0.02, 0.01), perturb=(0.1, 0.03), offset=(0.3, 0.1, 0.2), fix_offset=False,
                    wrap_every=0, pairs=None, odom_calib=False, n_params=1, params=(1.06, 0.93, 1.25)):
     """Simultaneous calibration, localisation and mapping in 2-D (what g2o/examples/calibration_odom_laser optimises): n_poses
