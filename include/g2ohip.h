@@ -520,6 +520,27 @@ int g2ohip_ba_update(g2ohip_solver* s);
 int g2ohip_ba_push(g2ohip_solver* s);
 int g2ohip_ba_pop(g2ohip_solver* s);
 int g2ohip_ba_discard_top(g2ohip_solver* s);
+/* StructureOnlySolver<3>::calc(points, num_iters, num_max_trials) on the bound projection set
+ * (g2o/solvers/structure_only/structure_only_solver.h:72-194; what ba_demo.cpp:261-269 and sba_demo.cpp:351-359 run before the
+ * joint optimisation, g2o_cli's structure_only_3): a Levenberg-Marquardt per landmark with every pose frozen, for every free
+ * point (point_hidx >= 0) in ONE kernel launch -- all outer iterations and damping trials on the device.  mu = 0.01, nu = 2
+ * (:86-87, hard-coded there too); chi2 = sum e' Omega e over the point's track, observations from fixed cameras included
+ * (:89-93); per outer iteration H = sum w J' Omega J, b = -sum w J' Omega e with the robust weight of the set's kernel
+ * (:106-135), stop when |b| < 0.001 (:139-142); trials: H + mu I factorised, the candidate accepted iff chi2 - new_chi2 > 0
+ * and new_chi2 is finite (:145-170; the RAW chi2, as e->chi2() there), then mu *= 1/3, nu = 2, else mu *= nu, nu *= 2 and the
+ * point stops after num_max_trials rejections in one outer iteration (:173-186).  Deviation: an unpivoted 3 x 3 LDL' with the
+ * test "every pivot > 0" in place of Eigen's pivoted LDLT::isPositive() (:148-150); with mu > 0 they differ on non-finite
+ * input only.  Bound to EdgeProjectXYZ2UV (g2ohip_ba_set_edges*, edge classes included) or EdgeProjectXYZ2UVU
+ * (g2ohip_ba_set_stereo_edges); an EdgeProjectPSI2UV binding is refused with G2OHIP_ERR_STATE.
+ * point_trace: NULL or [n_points][4] = (outer iterations started, accepted steps, rejected trials, stop reason: 0 ran
+ * num_iters, 1 |b| < 1e-3, 2 num_max_trials reached, 3 not optimised -- the point is fixed or its track is empty);
+ * point_chi2: NULL or [n_points][2] = (chi2 before, chi2 after), (0, 0) for stop reason 3; both indexed like `points` of
+ * g2ohip_ba_set_estimates.  G2OHIP_ERR_STATE before g2ohip_ba_set_edges* / g2ohip_ba_set_stereo_edges and
+ * g2ohip_ba_set_estimates, G2OHIP_ERR_ARG for num_iters < 0 or num_max_trials < 1; num_iters == 0 is legal (chi2 only, the
+ * points stay untouched).  The call is a writer of the estimates like g2ohip_ba_update: errors, Jacobians and chi2 of the set
+ * are stale afterwards and the next g2ohip_build_system assembles anew.  Between g2ohip_ba_push and g2ohip_ba_pop it is legal,
+ * and pop restores the points. */
+int g2ohip_ba_structure_only(g2ohip_solver* s, int num_iters, int num_max_trials, int32_t* point_trace, double* point_chi2);
 
 /* ---- device-resident pose-graph front end ----------------------------
  * Error + Jacobian producers and vertex updates for pose graphs, so a Gauss-Newton / LM iteration needs no

@@ -55,7 +55,7 @@ EXPORTS = [
     "g2ohip_ls_destroy", "g2ohip_ls_init", "g2ohip_ls_solve", "g2ohip_ls_solve_pattern", "g2ohip_ls_get_stats", "g2ohip_ls_set_option",
     "g2ohip_kernel_slots", "g2ohip_kernel_name", "g2ohip_kernel_time", "g2ohip_add_schur_pattern", "g2ohip_set_edge_set_parts",
     "g2ohip_set_lambda_split", "g2ohip_host_register", "g2ohip_host_unregister", "g2ohip_ba_set_edges", "g2ohip_ba_set_edges_classes", "g2ohip_ba_set_stereo_edges", "g2ohip_ba_set_pose_edges", "g2ohip_ba_set_inverse_depth_edges", "g2ohip_ba_set_estimates", "g2ohip_ba_get_estimates", "g2ohip_ba_get_estimates_of", "g2ohip_ba_fetch_estimates_begin", "g2ohip_ba_fetch_estimates_wait",
-    "g2ohip_ba_linearize", "g2ohip_ba_update", "g2ohip_ba_push", "g2ohip_ba_pop", "g2ohip_ba_discard_top",
+    "g2ohip_ba_linearize", "g2ohip_ba_structure_only", "g2ohip_ba_update", "g2ohip_ba_push", "g2ohip_ba_pop", "g2ohip_ba_discard_top",
     "g2ohip_set_partition", "g2ohip_solve_reduced_local", "g2ohip_solve_reduced_shared", "g2ohip_solve_reduced_finish",
     "g2ohip_schur_operator_prepare", "g2ohip_schur_operator_apply", "g2ohip_solve_async", "g2ohip_trial_stats_begin", "g2ohip_trial_stats", "g2ohip_solve_reduced_finish_async", "g2ohip_exchange_setup", "g2ohip_exchange_pack", "g2ohip_exchange_unpack", "g2ohip_exchange_status",
     "g2ohip_get_partition", "g2ohip_partition_poses",
@@ -163,6 +163,7 @@ def load():
     L.g2ohip_ba_fetch_estimates_begin.argtypes = [vp, c_dbl_p, c_dbl_p, C.c_int]
     L.g2ohip_ba_fetch_estimates_wait.argtypes = [vp, C.c_int]
     L.g2ohip_ba_linearize.argtypes = [vp, C.c_int]
+    L.g2ohip_ba_structure_only.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_dbl_p]
     for n in ("g2ohip_ba_update", "g2ohip_ba_push", "g2ohip_ba_pop", "g2ohip_ba_discard_top", "g2ohip_pg_update", "g2ohip_pg_push",
               "g2ohip_pg_pop", "g2ohip_pg_discard_top"):
         getattr(L, n).argtypes = [vp]
@@ -698,6 +699,20 @@ class HipBlockSolver:
 
     def baUpdate(self):
         _check(self.L.g2ohip_ba_update(self.h), "baUpdate")
+
+    def baStructureOnly(self, num_iters=10, num_max_trials=10, trace=False):
+        """StructureOnlySolver<3>::calc on the bound projection set (g2ohip_ba_structure_only): every free point, all outer
+        iterations and damping trials in one kernel launch.  trace=True returns (point_trace [n_points][4] = outer iterations,
+        accepted steps, rejected trials, stop reason; point_chi2 [n_points][2] = chi2 before, after), indexed like the points of
+        baSetEstimates; otherwise nothing is read back."""
+        if not trace:
+            _check(self.L.g2ohip_ba_structure_only(self.h, int(num_iters), int(num_max_trials), None, None), "baStructureOnly")
+            return None
+        npts = getattr(self, "_ba_n", (0, 0))[1]
+        tr = np.zeros((max(npts, 1), 4), np.int32)
+        chi = np.zeros((max(npts, 1), 2))
+        _check(self.L.g2ohip_ba_structure_only(self.h, int(num_iters), int(num_max_trials), _ip(tr), _dp(chi)), "baStructureOnly")
+        return tr[:npts], chi[:npts]
 
     def baPush(self):
         _check(self.L.g2ohip_ba_push(self.h), "baPush")

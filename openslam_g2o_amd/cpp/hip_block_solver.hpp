@@ -92,6 +92,12 @@ class HipBlockSolver {
                         double focalLength, double cx, double cy, double baseline) {
     return ok(g2ohip_ba_set_stereo_edges(h_, set, camVertex, pointVertex, meas, info, focalLength, cx, cy, baseline), "baSetStereoEdges");
   }
+  // StructureOnlySolver<3>::calc(points, numIters, numMaxTrials) on the bound projection set, every free point in one kernel launch
+  // (g2ohip_ba_structure_only): pointTrace nullptr or [nPoints][4] = (outer iterations, accepted, rejected, stop reason), pointChi2
+  // nullptr or [nPoints][2] = (chi2 before, after), indexed like the points of g2ohip_ba_set_estimates
+  bool baStructureOnly(int numIters = 10, int numMaxTrials = 10, int32_t* pointTrace = nullptr, double* pointChi2 = nullptr) {
+    return ok(g2ohip_ba_structure_only(h_, numIters, numMaxTrials, pointTrace, pointChi2), "baStructureOnly");
+  }
   // EdgeSE3Expmap constraints between two cameras in the second slot of the device-resident BA front end (g2ohip_ba_set_pose_edges,
   // after baSetStereoEdges / g2ohip_ba_set_edges): `set` was added as a binary set with errorDim 6 over two 6-dof poses; vi / vj index
   // the camera table (vertex 0 / vertex 1), meas [n][12] = the measurement as an isometry, info [n][6x6] or nullptr (identity)

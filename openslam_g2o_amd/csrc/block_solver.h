@@ -172,6 +172,7 @@ class BlockSolver {
   static constexpr int kFetchMaxPieces = 17;
   void ba_linearize(bool jacobians);
   void ba_update();
+  void ba_structure_only(int num_iters, int num_max_trials, int* point_trace, double* point_chi2);
   void ba_push();
   void ba_pop();
   void ba_discard_top();
@@ -504,6 +505,8 @@ class BlockSolver {
     DevBuf<double> sel_out;
     bool ll_slots_ok = false;
     bool has_backup = false;
+    DevBuf<int> so_trace;     // ba_structure_only: per point (iterations, accepted, rejected, stop reason)
+    DevBuf<double> so_chi;    // ... (chi2 before, chi2 after)
     // ONE binary set of EdgeSE3Expmap constraints `pose_set` between two cameras beside the projection slot (ba_set_pose_edges,
     // ba_pose_edge.inc): pvi / pvj index `cams` (vertex 0 / vertex 1), pose_meas [n][12] = the measurement as an isometry.  The
     // set owns no vertices: ba_linearize fills its own_J0 / own_J1 / own_err, nothing else knows of it.  Its Jacobians are

@@ -2335,6 +2335,7 @@ __global__ void __launch_bounds__(kThreads) pg_se3_update_kernel(int nv, double*
 #include "ba_stereo.inc"
 #include "ba_pose_edge.inc"
 #include "ba_psi.inc"
+#include "ba_structure_only.inc"
 #undef PG_R
 
 inline int grid_for(size_t n, int threads = kThreads) { return (int)((n + threads - 1) / threads); }
@@ -5967,6 +5968,60 @@ void BlockSolver::ba_pop() {
 void BlockSolver::ba_discard_top() {
   if (!ba_.has_backup) throw StateFailure("ba_discard_top without push");
   ba_.has_backup = false;
+}
+
+
+// StructureOnlySolver<3>::calc on the bound projection set (ba_structure_only.inc): one launch on the solver's stream, outside the
+// captured launch sequences.  A writer of the estimates like ba_update (the fused path's sys_version check then forces a rebuild);
+// legal between ba_push and ba_pop, which restores the points.  num_iters == 0: chi2 only, nothing is written and nothing invalidated.
+// point_trace [n_points][4] / point_chi2 [n_points][2] (either may be null) are indexed like `points` of ba_set_estimates.
+void BlockSolver::ba_structure_only(int num_iters, int num_max_trials, int* point_trace, double* point_chi2) {
+  if (ba_.set < 0 || ba_.cams.n <= 0) throw StateFailure("ba_structure_only: call ba_set_edges* / ba_set_stereo_edges and ba_set_estimates first");
+  if (ba_.psi) throw StateFailure("ba_structure_only: the projection slot holds EdgeProjectPSI2UV observations (no 3-dof XYZ point)");
+  if (num_iters < 0) throw ArgFailure("ba_structure_only: num_iters must not be negative");
+  if (num_max_trials < 1) throw ArgFailure("ba_structure_only: num_max_trials must be at least 1");
+  require_structure();
+  EdgeSet& es = *sets_[ba_.set];
+  if (ba_.n_edges != es.n) throw StateFailure("ba_structure_only: the projection set has changed since it was bound: bind it again");
+  G2OHIP_HIP_CHECK(hipSetDevice(device_));
+  const int np = ba_.pts.n;
+  if (es.parts & 1) throw StateFailure("ba_structure_only: the landmark side of the projection set is assembled from another set (set_edge_set_parts)");
+  if (es.touches_lm && (int)es.h_vl_ptr.size() != nL_ + 1)
+    throw StateFailure("ba_structure_only: the observation lists of the projection set do not match the structure: build the structure and bind the set again");
+  if (!es.touches_lm) {   // every edge of the set names a fixed point: no free point has an observation, nothing to optimise
+    for (int v = 0; v < np; ++v) {
+      if (point_trace) {
+        point_trace[4 * (size_t)v] = point_trace[4 * (size_t)v + 1] = point_trace[4 * (size_t)v + 2] = 0;
+        point_trace[4 * (size_t)v + 3] = 3;
+      }
+      if (point_chi2) point_chi2[2 * (size_t)v] = point_chi2[2 * (size_t)v + 1] = 0.0;
+    }
+    return;
+  }
+  ba_.so_trace.alloc((size_t)np * 4);
+  ba_.so_chi.alloc((size_t)np * 2);
+  if (num_iters > 0) {
+    ba_fetch_fence();
+    ++ba_.est_version;
+    ba_.err_valid = ba_.jac_valid = ba_.pose_jac_valid = false;
+    chi2_valid_ = false;
+  }
+  const int G = pick_group((double)es.n_vl_ent / std::max(1, nL_));
+  const int mode = ba_.stereo ? 2 : (ba_.n_classes > 1 ? 1 : 0);
+  with_lane_group<1, 4, 8>(G, [&](auto g) {
+    dispatch_value<0, 1, 2>(mode, [&](auto m) {
+      constexpr int GG = g, MODE = m;
+      const bool st = MODE == 2;
+      hipLaunchKernelGGL((ba_structure_only_kernel<GG, MODE>), dim3(grid_for((size_t)np * GG)), dim3(kThreads), 0, st_, np, ba_.pts.hidx.p,
+                         es.vl_ptr.p, es.vl_ent.p, ba_.cams.val.p, ba_.pts.val.p, st ? ba_.cam_v.p : ba_.cam_lm.p,
+                         st ? ba_.meas.p : ba_.meas_lm.p, st ? es.omega : ba_.omega_lm.p, ba_.omega_identity ? 1 : 0, ba_.f, ba_.cx, ba_.cy,
+                         ba_.baseline, es.kernel_kind, es.delta, st ? es.rk.p : (const double*)nullptr,
+                         MODE == 1 ? ba_.ctab.p : (const double*)nullptr, num_iters, num_max_trials, ba_.so_trace.p, ba_.so_chi.p);
+    });
+  });
+  G2OHIP_HIP_CHECK(hipGetLastError());
+  if (point_trace) ba_.so_trace.download(point_trace, (size_t)np * 4, st_);   // (synchronises)
+  if (point_chi2) ba_.so_chi.download(point_chi2, (size_t)np * 2, st_);
 }
 
 

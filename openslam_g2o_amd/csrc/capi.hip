@@ -573,6 +573,9 @@ int g2ohip_ba_linearize(g2ohip_solver* s, int jacobians) {
 int g2ohip_ba_update(g2ohip_solver* s) {
   return entry(s, [&](BlockSolver& b) { b.ba_update(); });
 }
+int g2ohip_ba_structure_only(g2ohip_solver* s, int num_iters, int num_max_trials, int32_t* point_trace, double* point_chi2) {
+  return entry(s, [&](BlockSolver& b) { b.ba_structure_only(num_iters, num_max_trials, point_trace, point_chi2); });
+}
 int g2ohip_ba_push(g2ohip_solver* s) {
   return entry(s, [&](BlockSolver& b) { b.ba_push(); });
 }

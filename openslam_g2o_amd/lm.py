@@ -337,6 +337,13 @@ def setup_device_ba(prob, huber_delta=0.0, device=0, options=None, huber_delta_p
     return s, DeviceBAGraph(s)
 
 
+def structure_only(solver, num_iters=10, num_max_trials=10, trace=False):
+    """StructureOnlySolver<3>::calc(points, num_iters, num_max_trials) on the solver's bound projection set (ba_demo.cpp:261-269:
+    the pre-step of the joint optimisation), every free point in one kernel launch.  trace=True returns (point_trace, point_chi2)
+    of HipBlockSolver.baStructureOnly."""
+    return solver.baStructureOnly(num_iters, num_max_trials, trace)
+
+
 class DevicePoseGraph:
     """The graph protocol over HipBlockSolver's device-resident pose-graph front end (EdgeSE2 / EdgeSE3 / EdgeSim3, and the
     landmark observations bound beside them: setup_device_landmark_slam, setup_device_sim3_ba, setup_device_sbacam_ba)."""
